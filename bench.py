@@ -25,6 +25,13 @@ synthetic single-block messages that is already resident in HBM.
                 columns that north_star also asks for is timed separately on a
                 bounded shard ("extra.multi_gpu") -- it never enters `value`.
 
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline needs:
+set-up (including the placement choice of the output buffers), warm-up, the
+N timed steps, the outputs of the last step if `--dump-outputs DIR` is given,
+and the result line.  Everything else -- the engine-event cross-check, the
+calibrated fill, the digest spot-check, the extras above, the CPU baselines --
+runs only with `--full`.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -877,6 +884,29 @@ def extra_multi_gpu(dist, sh, eng, blocks, pre, out, n, world, rank, value):
     return res
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_ROWS = {"gate": 1 << 18, "dense": 1 << 16, "spread": 1 << 16, "next_states": 1 << 16}   # rows of 64 B: 28 MiB at most
+
+
+def dump_outputs(path, out):
+    """What the last timed step handed its caller, as DIR/<name>.npy in float64: gate, dense and spread hold one
+    row per cell (its eight 32-bit words, least significant first), next_states one row per block (its eight state
+    words).  Every 32-bit word is exact in float64.  A stream with more rows than DUMP_ROWS is sampled at fixed,
+    seeded, sorted row indices (the whole gate stream of 4,096 blocks is 8.7 GB), so two builds run with the same
+    arguments dump the same rows."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for i, name in enumerate(("gate", "dense", "spread", "next_states")):
+        t = out[name]
+        rows = t.reshape(-1, t.shape[-1])                   # cells: (n, 4) int64 limbs; next_states: (n, 8) int32
+        k = DUMP_ROWS[name]
+        if rows.shape[0] > k:
+            idx = np.sort(np.random.default_rng([0xD0, i]).integers(0, rows.shape[0], k))
+            rows = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+        words = rows.cpu().numpy().view(np.uint32)
+        np.save(os.path.join(path, name + ".npy"), words.astype(np.float64))
+
+
 # ------------------------------------------------------------------ one rank
 def run_rank(args):
     # ONE JSON line on stdout: libraries that print there on their own (RCCL's version banner) go to stderr
@@ -967,22 +997,26 @@ def run_rank(args):
     elapsed = time.perf_counter() - t0
     kernel_ms_avg = float(np.mean([a.elapsed_time(b) for a, b in ev]))     # avg launch duration over the timed region
     launched = eng.last_launch()                                          # the instantiation that was timed
-    # cross-check with the engine's own event pair (hsw_last_kernel_ms) on one more launch
-    step()
-    kernel_ms_engine = eng.last_kernel_ms()
-    # practical write ceiling of this device/allocation: plain 16 B/lane fill of the same gate buffer
-    fill_ms = min(eng.fill_calibrate(out["gate"]) for _ in range(3))
-    fill_gbs = out["gate"].numel() * 8 / (fill_ms * 1e-3) / 1e9
-    for _ in range(2):     # the fill clobbered the stream: regenerate before the checks below
-        step()
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
-    # spot-check (size-independent property): digest from next_states == hashlib
-    import hashlib
-    ns = out["next_states"][:4].cpu().numpy().view(np.uint32)
-    for i in range(4):
-        dig = b"".join(int(x).to_bytes(4, "big") for x in ns[i])
-        assert dig == hashlib.sha256(msgs[i].tobytes()).digest(), "GPU digest mismatch"
+    if args.full:
+        # cross-check with the engine's own event pair (hsw_last_kernel_ms) on one more launch
+        step()
+        kernel_ms_engine = eng.last_kernel_ms()
+        # practical write ceiling of this device/allocation: plain 16 B/lane fill of the same gate buffer
+        fill_ms = min(eng.fill_calibrate(out["gate"]) for _ in range(3))
+        fill_gbs = out["gate"].numel() * 8 / (fill_ms * 1e-3) / 1e9
+        for _ in range(2):     # the fill clobbered the stream: regenerate before the checks below
+            step()
+        torch.cuda.synchronize()
+
+        # spot-check (size-independent property): digest from next_states == hashlib
+        import hashlib
+        ns = out["next_states"][:4].cpu().numpy().view(np.uint32)
+        for i in range(4):
+            dig = b"".join(int(x).to_bytes(4, "big") for x in ns[i])
+            assert dig == hashlib.sha256(msgs[i].tobytes()).digest(), "GPU digest mismatch"
 
     t_el = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
     # every rank's own kernel time (HIP events on its launch stream), gathered with one collective of a float each:
@@ -999,7 +1033,8 @@ def run_rank(args):
     value = total_blocks / elapsed
 
     extra = {}
-    if not args.no_extra and rank == 0:
+    with_extra = args.full and not args.no_extra
+    if with_extra and rank == 0:
         extra.update(extra_representations(hsw, eng, blocks, pre, cursor0, out, n, alg_bytes, step))
         try:
             extra["config1_1KiB_message_16_blocks"] = extra_config1(hsw, eng, dev, local_rank, alg_bytes)
@@ -1017,7 +1052,7 @@ def run_rank(args):
             extra["config4_substitute_k20"] = extra_config4_substitute(hsw, eng, local_rank, blocks_h, pre_h, alg_bytes)
         except Exception as ex:
             extra["config4_substitute_k20"] = {"error": repr(ex)}
-    if distributed and not args.no_extra:
+    if distributed and with_extra:
         mg = extra_multi_gpu(dist, sh, eng, blocks, pre, out, n, world, rank, value)
         if rank == 0:
             extra["multi_gpu"] = mg
@@ -1074,9 +1109,6 @@ def run_rank(args):
                 "achievable": HBM_ACHIEVABLE_GBS,
                 "traffic": traffic,
                 "traffic_source": traffic_src,
-                "calibrated_fill_GBps": fill_gbs,
-                "calibrated_fill_note": "hsw_fill_calibrate on the same gate buffer: every wave streams its own contiguous 64 KiB "
-                                        "chunks, the best pure-write pattern found on this part (tools/fillbench)",
                 "placement": dict(placement, note="rank 0's: the launch timed on every combination of the candidate gate buffers "
                                   "(rows of kernel_ms) and candidate chip-column allocations (columns), the fastest kept: on MI355X the "
                                   "same launch takes between 1.58 and 1.78 ms depending on where its buffers sit "
@@ -1089,16 +1121,22 @@ def run_rank(args):
                                                          ", split phases" if launched["split"] else ""),
                 "launch": launched,
                 "kernel_ms": kernel_ms_avg,
-                "kernel_ms_engine_events": kernel_ms_engine,
                 "algorithmic_bytes_per_launch": alg_bytes * n,
             },
+            "full": args.full,
             "extra": extra,
         }
+        if args.full:
+            result["roofline"].update({
+                "calibrated_fill_GBps": fill_gbs,
+                "calibrated_fill_note": "hsw_fill_calibrate on the same gate buffer: every wave streams its own contiguous 64 KiB "
+                                        "chunks, the best pure-write pattern found on this part (tools/fillbench)",
+                "kernel_ms_engine_events": kernel_ms_engine})
         mont = extra.get("montgomery_repr", {})
         if "kernel_ms" in mont:      # halo2curves' in-memory Fr: the form a Rust shim copies straight into the Region
             result["roofline"]["montgomery"] = {"kernel": mont["kernel"], "kernel_ms": mont["kernel_ms"],
                                                 "achieved": mont["GBps"], "frac": mont["frac_of_peak"]}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(blocks_h, pre_h)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(result) + "\n").encode())
@@ -1110,13 +1148,20 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--messages-per-gpu", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the checks and side measurements: engine-event cross-check, calibrated fill, digest spot-check, "
+                         "extras (other cell forms, configs 0/1/4, multi-GPU all-gather) and CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64, see dump_outputs)")
     ap.add_argument("--placement-candidates", type=int, default=6,
                     help="candidate allocations of the chip columns (x 3 candidate gate buffers) timed before the run; 1 = plain buffers as they come")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))      # before anything touches HIP in this process
     run_rank(args)

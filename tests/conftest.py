@@ -3,6 +3,10 @@ import os
 import sys
 
 import pytest
+# torch ships its own HIP runtime (torch/lib/libamdhip64.so, same soname as the system one).  Loaded first, it is
+# the runtime libhsw.so binds to; loaded after libhsw.so, the process holds two HIP runtimes and libhsw.so's sees
+# no device.  A whole-suite run loads libhsw.so in host-only tests long before any GPU test imports torch.
+import torch  # noqa: F401
 
 # glibc writes its fatal messages (heap corruption, double free) to the controlling terminal unless told
 # otherwise: a GPU-box run has no use for that -- keep them in the captured stderr.

@@ -1,6 +1,7 @@
 // Host-only entry points of libhsw under AddressSanitizer + UBSan (CPU build only:
 // GPU sanitizers are not available on the pool).  Built and run by
-// tests/test_host_sanitizers.py; exits non-zero on any mismatch, and the
+// tests/test_host_sanitizers.py against the stand-in HIP runtime of hip_stub.cpp
+// (no real HIP runtime is linked); exits non-zero on any mismatch, and the
 // sanitizers abort on any memory / UB error.
 #include <cstdio>
 #include <cstdlib>
@@ -124,7 +125,7 @@ int main() {
         CHECK(info.precomputed_round == 2 && info.target_round == 2 && info.num_round == 4);
         CHECK(hsw_digest_prepare(msg.data(), 192, 100, 128, nullptr, nullptr, nullptr) == HSW_ERR_SHAPE);
     }
-    // engine creation without a device must fail cleanly (or succeed on a GPU box)
+    // engine creation must fail cleanly without a device (or succeed, as it does against the stand-in runtime)
     hsw_engine *e = nullptr;
     int rc = hsw_engine_create(0, nullptr, 8, 2, &e);
     CHECK(rc == HSW_OK || rc == HSW_ERR_NO_DEVICE);

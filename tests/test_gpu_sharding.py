@@ -85,7 +85,7 @@ def test_bench_gpus_2_starts_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HSW_BENCH_BACKEND="gloo", HSW_BENCH_SAME_DEVICE="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--messages-per-gpu", "512", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                        "--messages-per-gpu", "512", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -12,15 +12,15 @@ done
 python3 tools/profile_extract.py traffic $(find $OUT/pmc_WRITE_SIZE -name "*.db" | head -1) $(find $OUT/pmc_FETCH_SIZE -name "*.db" | head -1) $OUT/pmc_traffic.json hsw_expand_kernel 9771679744 $COMMIT
 echo "pmc traffic done"
 cp $OUT/pmc_traffic.json profiles/${TAG}_pmc_traffic.json
-python3 bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err || exit 1
+python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err || exit 1
 echo "bench line done"
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 bench.py > $OUT/bench_line_under_rocprof.json 2> $OUT/rocprof_kt.log || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt -- python3 bench.py --full > $OUT/bench_line_under_rocprof.json 2> $OUT/rocprof_kt.log || exit 1
 DB=$(find $OUT/kt -name "*.db" | head -1)
 python3 tools/profile_extract.py stats_by_grid $DB $OUT/bench_kernel_stats.csv 1048576
 python3 tools/profile_extract.py stats_by_grid $DB $OUT/bench_all_kernels_stats.csv 0
 echo "kernel trace done"
-rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS -d $OUT/sq1 -o s -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/sq1.json 2> $OUT/sq1.log || exit 1
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $OUT/sq2 -o s -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/sq2.json 2> $OUT/sq2.log || exit 1
+rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS -d $OUT/sq1 -o s -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > $OUT/sq1.json 2> $OUT/sq1.log || exit 1
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE -d $OUT/sq2 -o s -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --full > $OUT/sq2.json 2> $OUT/sq2.log || exit 1
 python3 tools/profile_extract.py sq $OUT/sq_counters.json $(find $OUT/sq1 -name "*.db" | head -1) $(find $OUT/sq2 -name "*.db" | head -1)
 echo "sq counters done"
 # the three cell forms of the 4,096-block launch side by side: canonical, Montgomery converted at write-out, Montgomery

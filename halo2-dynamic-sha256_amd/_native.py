@@ -33,6 +33,7 @@ HSW_MAX_BREAKS = 16
 HSW_CELL_BYTES = 32
 HSW_GADGET_WHOLE_DIGEST = 1
 HSW_GADGET_INDEPENDENT = 2
+HSW_GADGET_CONTEXT_IMAGES = 4
 NO_CELL = (1 << 64) - 1
 
 
@@ -170,6 +171,15 @@ class GadgetView(C.Structure):
                 ("origin_zero_loaded", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class ContextRegion(C.Structure):
+    """hsw_context_region: where proof h of an HSW_GADGET_CONTEXT_IMAGES gadget lives on the device."""
+    _fields_ = [("d_image", C.c_void_p), ("d_lookup", C.c_void_p), ("d_chip_dense", C.c_void_p), ("d_chip_spread", C.c_void_p)] + \
+               [(n, C.c_uint64) for n in ("columns", "max_rows", "last_column_rows", "stream_cells", "first_stream_cell",
+                                          "lookup_cells", "chip_rows", "chip_col_stride", "origin_column", "origin_row",
+                                          "origin_lookups")] + \
+               [("assigned", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -187,6 +197,7 @@ SYMBOLS = (
     "hsw_verify_frames", "hsw_gadget_verify", "hsw_last_launch", "hsw_witness_digests",
     "hsw_gadget_download_region_compact", "hsw_region_widen", "hsw_gadget_result_cells",
     "hsw_gadget_set_origin", "hsw_gadget_region_tape", "hsw_gadget_download_region_distinct", "hsw_gadget_replay_region",
+    "hsw_gadget_context_region",
 )
 
 
@@ -334,6 +345,8 @@ def lib():
         L.hsw_gadget_reset.argtypes = [vp]
         L.hsw_gadget_cell_position.restype = C.c_int
         L.hsw_gadget_cell_position.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.hsw_gadget_context_region.restype = C.c_int
+        L.hsw_gadget_context_region.argtypes = [vp, C.c_size_t, C.POINTER(ContextRegion)]
         L.hsw_gadget_create_ex.restype = C.c_int
         L.hsw_gadget_create_ex.argtypes = [vp, C.POINTER(C.c_size_t), C.c_size_t, C.c_int, C.c_uint32,
                                            C.POINTER(vp)]

@@ -356,7 +356,7 @@ int hsw_witness_blocks(hsw_engine *e, const uint8_t *d_blocks, const uint32_t *d
 } HSW_NO_UNWIND
 
 int hsw_witness_blocks_ex(hsw_engine *e, const hsw_witness_args *args) try {
-    return hsw_witness_blocks_impl(e, args, nullptr, nullptr);
+    return hsw_witness_blocks_impl(e, args, nullptr, nullptr, nullptr);
 } HSW_NO_UNWIND
 
 }  // extern "C"
@@ -372,7 +372,7 @@ bool hsw_small_eligible(const hsw_engine *e, size_t n_blocks) {
 // hsw_witness_blocks_ex, plus (small-batch launches only) the digest frames written by waves of the same
 // launch and a second copy of the next states in pinned host memory.
 int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const hsw::SmallFrames *frames,
-                            uint32_t *host_next_states) {
+                            uint32_t *host_next_states, const hsw::ContextPeriod *period) {
     if (!e || !args) return HSW_ERR_INVALID_ARG;
     const uint8_t *d_blocks = args->d_blocks;
     const uint32_t *d_pre_states = args->d_pre_states;
@@ -423,6 +423,9 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
         if (n_blocks > ((size_t)1 << 20))
             return set_err(e, HSW_ERR_UNSUPPORTED, "more than 2^20 blocks in one framed call");
     }
+    if (period && period->image_cells &&      // context images: one Context per frame_every blocks, each of image_cells cells
+        (!args->frame_every || n_blocks % args->frame_every != 0))
+        return set_err(e, HSW_ERR_INVALID_ARG, "context images: whole Contexts of frame_every blocks each");
     if ((frames || host_next_states) && !hsw_small_eligible(e, n_blocks))
         return set_err(e, HSW_ERR_INVALID_ARG, "frames / host next states ride on small-batch launches only");
     DeviceScope ds(e->device);
@@ -462,6 +465,7 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
         p.frame_every = args->frame_every;
         p.frame_cells = args->frame_cells;
         p.frame_lookups = args->frame_lookups;
+        p.ctx_cells = period ? period->image_cells : 0;
         const int tile = choose_tile(e, flags);
         p.parts = (uint32_t)choose_parts(e, n_blocks, tile, flags);
         // tiny batches are latency-bound: the small-batch kernel (37 waves per block, one sub-unit program

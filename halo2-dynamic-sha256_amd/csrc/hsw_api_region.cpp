@@ -143,6 +143,13 @@ static int ensure_structure(hsw_engine *e) {
 }
 
 int hsw_verify_blocks(hsw_engine *e, const hsw_witness_args *args, hsw_verify_report *report) try {
+    return hsw_verify_blocks_impl(e, args, report, nullptr);
+} HSW_NO_UNWIND
+
+}  // extern "C"
+
+int hsw_verify_blocks_impl(hsw_engine *e, const hsw_witness_args *args, hsw_verify_report *report,
+                           const hsw::ContextPeriod *period) {
     if (!e || !args || !report) return HSW_ERR_INVALID_ARG;
     std::memset(report, 0, sizeof *report);
     if (args->n_blocks == 0) return HSW_OK;
@@ -151,6 +158,8 @@ int hsw_verify_blocks(hsw_engine *e, const hsw_witness_args *args, hsw_verify_re
     if (args->pack && args->pack->n_breaks > HSW_MAX_BREAKS) return set_err(e, HSW_ERR_INVALID_ARG, "too many column breaks");
     if (args->frame_every && e->mode != HSW_MODE_HALO2_INTERNALS)
         return set_err(e, HSW_ERR_INVALID_ARG, "digest frames need an engine created with HSW_MODE_HALO2_INTERNALS");
+    if (period && period->image_cells && (!args->frame_every || args->n_blocks % args->frame_every != 0))
+        return set_err(e, HSW_ERR_INVALID_ARG, "context images: whole Contexts of frame_every blocks each");
     if ((args->d_chip_dense == nullptr) != (args->d_chip_spread == nullptr)) return set_err(e, HSW_ERR_INVALID_ARG, "both chip families or none");
     if (args->d_lookup && e->mode != HSW_MODE_HALO2_INTERNALS) return set_err(e, HSW_ERR_INVALID_ARG, "d_lookup needs HSW_MODE_HALO2_INTERNALS");
     // the kernel reads cells as 16-byte pieces at (N % ncols) * chip_col_stride + row: the same alignment and
@@ -174,6 +183,7 @@ int hsw_verify_blocks(hsw_engine *e, const hsw_witness_args *args, hsw_verify_re
     p.montgomery = (args->flags & HSW_REPR_MONTGOMERY) ? 1u : 0u;
     p.gate_cell0 = p.lookup_cell0 = 0;
     p.frame_every = args->frame_every; p.frame_cells = args->frame_cells; p.frame_lookups = args->frame_lookups;
+    p.ctx_cells = period ? period->image_cells : 0;
     p.n_breaks = args->pack ? args->pack->n_breaks : 0;
     for (uint32_t k = 0; k < p.n_breaks; k++) { p.break_cell[k] = args->pack->break_cell[k]; p.break_gap[k] = args->pack->break_gap[k]; }
     p.report = e->d_report;
@@ -204,11 +214,23 @@ int hsw_verify_blocks(hsw_engine *e, const hsw_witness_args *args, hsw_verify_re
         report->first_class = (uint32_t)(got.first_key & 15u);
     }
     return HSW_OK;
-} HSW_NO_UNWIND
+}
+
+extern "C" {
 
 int hsw_verify_frames(hsw_engine *e, const hsw_frame_desc *descs, size_t n, const uint8_t *d_blocks,
                       const uint32_t *d_pre_states, const uint32_t *d_next_states, const void *d_gate,
                       const void *d_lookup, const hsw_pack_plan *pack, uint32_t flags, hsw_verify_report *report) try {
+    return hsw_verify_frames_impl(e, descs, n, d_blocks, d_pre_states, d_next_states, d_gate, d_lookup, pack, flags, report,
+                                  nullptr);
+} HSW_NO_UNWIND
+
+}  // extern "C"
+
+int hsw_verify_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n, const uint8_t *d_blocks,
+                           const uint32_t *d_pre_states, const uint32_t *d_next_states, const void *d_gate,
+                           const void *d_lookup, const hsw_pack_plan *pack, uint32_t flags, hsw_verify_report *report,
+                           const hsw::ContextPeriod *period) {
     if (!e || !report) return HSW_ERR_INVALID_ARG;
     std::memset(report, 0, sizeof *report);
     if (n == 0) return HSW_OK;
@@ -269,6 +291,7 @@ int hsw_verify_frames(hsw_engine *e, const hsw_frame_desc *descs, size_t n, cons
     p.n_breaks = pack ? pack->n_breaks : 0;
     p.montgomery = (flags & HSW_REPR_MONTGOMERY) ? 1u : 0u;
     for (uint32_t k = 0; k < p.n_breaks; k++) { p.break_cell[k] = pack->break_cell[k]; p.break_gap[k] = pack->break_gap[k]; }
+    if (period && period->stream_cells) { p.ctx_stream = period->stream_cells; p.ctx_image = period->image_cells; }
     uint64_t checks = 0;
     for (int s2 = 0; s2 < 2; s2++) {
         hsw::FrameVerifyParams::Section &S = s2 ? p.epi : p.pro;
@@ -309,7 +332,9 @@ int hsw_verify_frames(hsw_engine *e, const hsw_frame_desc *descs, size_t n, cons
         report->first_class = (uint32_t)(got.first_key & 15u);
     }
     return HSW_OK;
-} HSW_NO_UNWIND
+}
+
+extern "C" {
 
 int hsw_frame_structure(const hsw_shape *shape, size_t max_variable_byte_size, int is_input_range_check,
                         int section, hsw_frame_structure_counts *counts, uint8_t *cell_kind, int64_t *cell_ref,
@@ -431,7 +456,7 @@ static int stage_frame_descs(hsw_engine *e, const hsw_frame_desc *descs, size_t 
 
 static int check_frame_args(hsw_engine *e, const hsw_frame_desc *descs, const uint8_t *d_blocks,
                             const uint32_t *d_pre_states, void *d_gate, void *d_lookup, const hsw_pack_plan *pack,
-                            uint32_t flags, hsw::FrameBreaks *brk) {
+                            uint32_t flags, const hsw::ContextPeriod *period, hsw::FrameBreaks *brk) {
     if (!descs || !d_blocks || !d_pre_states || !d_gate) return set_err(e, HSW_ERR_INVALID_ARG, "null pointer");
     if (e->mode != HSW_MODE_HALO2_INTERNALS)
         return set_err(e, HSW_ERR_INVALID_ARG, "digest frames need an engine created with HSW_MODE_HALO2_INTERNALS");
@@ -447,17 +472,30 @@ static int check_frame_args(hsw_engine *e, const hsw_frame_desc *descs, const ui
         brk->n = pack->n_breaks;
         for (uint32_t k = 0; k < pack->n_breaks; k++) { brk->cell[k] = pack->break_cell[k]; brk->gap[k] = pack->break_gap[k]; }
     }
+    if (period && period->stream_cells) {     // context images: the break table is one Context's
+        if (!period->image_cells) return set_err(e, HSW_ERR_INVALID_ARG, "context images: image_cells = 0");
+        brk->ctx_stream = period->stream_cells;
+        brk->ctx_image = period->image_cells;
+    }
     return HSW_OK;
 }
 
 int hsw_witness_frames(hsw_engine *e, const hsw_frame_desc *descs, size_t n, const uint8_t *d_blocks,
                        const uint32_t *d_pre_states, const uint32_t *d_next_states, void *d_gate,
                        void *d_lookup, const hsw_pack_plan *pack, uint32_t flags) try {
+    return hsw_witness_frames_impl(e, descs, n, d_blocks, d_pre_states, d_next_states, d_gate, d_lookup, pack, flags, nullptr);
+} HSW_NO_UNWIND
+
+}  // extern "C"
+
+int hsw_witness_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n, const uint8_t *d_blocks,
+                            const uint32_t *d_pre_states, const uint32_t *d_next_states, void *d_gate, void *d_lookup,
+                            const hsw_pack_plan *pack, uint32_t flags, const hsw::ContextPeriod *period) {
     if (!e) return HSW_ERR_INVALID_ARG;
     if (n == 0) return HSW_OK;
     if (!d_next_states) return set_err(e, HSW_ERR_INVALID_ARG, "null pointer");
     hsw::FrameBreaks brk{};
-    int rc = check_frame_args(e, descs, d_blocks, d_pre_states, d_gate, d_lookup, pack, flags, &brk);
+    int rc = check_frame_args(e, descs, d_blocks, d_pre_states, d_gate, d_lookup, pack, flags, period, &brk);
     if (rc != HSW_OK) return rc;
     DeviceScope ds(e->device);
     if (!ds.ok) return set_err(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
@@ -476,23 +514,22 @@ int hsw_witness_frames(hsw_engine *e, const hsw_frame_desc *descs, size_t n, con
     if (he != hipSuccess) return set_err(e, HSW_ERR_HIP, "hipEventRecord", he);
     slot->inflight = true;
     return HSW_OK;
-} HSW_NO_UNWIND
-
-}  // extern "C"
+}
 
 // dev_next_states: the DEVICE address of a->host_next_states when the caller already holds it (the gadget: its
 // own pinned staging, mapped once at creation), else NULL = ask the runtime.  The public entry point always asks:
 // round 2 cached one (host, device) pair per engine and translated every later pointer within 64 KiB above it by
 // offset -- a pointer from another (or from no) pinned allocation in that window skipped the check and the kernel
 // stored the next states through a stale or unmapped address.
-int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *a, uint32_t *dev_next_states) {
+int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *a, uint32_t *dev_next_states,
+                             const hsw::ContextPeriod *period) {
     if (!e || !a) return HSW_ERR_INVALID_ARG;
     const hsw_witness_args &b = a->blocks;
     if (a->n_digests == 0 || b.n_blocks == 0) return HSW_OK;
     if (!a->d_next_states0) return set_err(e, HSW_ERR_INVALID_ARG, "null pointer");
     hsw::FrameBreaks brk{};
     int rc = check_frame_args(e, a->descs, a->d_blocks0, a->d_pre_states0, a->d_gate0, a->d_lookup0, a->frame_pack,
-                              b.flags & HSW_REPR_MASK, &brk);
+                              b.flags & HSW_REPR_MASK, period, &brk);
     if (rc != HSW_OK) return rc;
     // the block streams of the call must be exactly the blocks of its digests, in order, with the frames
     // of equally sized digests in between (what frame_every describes)
@@ -508,10 +545,10 @@ int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *a, uint32_t 
     if (!ds.ok) return set_err(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
     if (!hsw_small_eligible(e, b.n_blocks) || a->descs[0].n_blocks > hsw::SMALL_FRAME_MAX_BLOCKS) {   // (the frame waves stage the candidate states in LDS)
         // two launches: the expansion, then the frames from the next states it left in HBM
-        rc = hsw_witness_blocks_ex(e, &b);
+        rc = hsw_witness_blocks_impl(e, &b, nullptr, nullptr, period);
         if (rc == HSW_OK)
-            rc = hsw_witness_frames(e, a->descs, a->n_digests, a->d_blocks0, a->d_pre_states0, a->d_next_states0,
-                                    a->d_gate0, a->d_lookup0, a->frame_pack, b.flags & HSW_REPR_MASK);
+            rc = hsw_witness_frames_impl(e, a->descs, a->n_digests, a->d_blocks0, a->d_pre_states0, a->d_next_states0,
+                                         a->d_gate0, a->d_lookup0, a->frame_pack, b.flags & HSW_REPR_MASK, period);
         if (rc == HSW_OK && a->host_next_states && b.d_next_states) {
             hipError_t he = hipMemcpyAsync(a->host_next_states, b.d_next_states, b.n_blocks * 32, hipMemcpyDeviceToHost, e->stream);
             if (he != hipSuccess) return set_err(e, HSW_ERR_HIP, "D2H next states", he);
@@ -556,7 +593,7 @@ int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *a, uint32_t 
             return set_err(e, HSW_ERR_INVALID_ARG, "host_next_states is not pinned, device-mapped host memory (hsw_host_alloc)", he);
         }
     }
-    rc = hsw_witness_blocks_impl(e, &b, &fr, host_next);
+    rc = hsw_witness_blocks_impl(e, &b, &fr, host_next, period);
     if (rc != HSW_OK) return rc;
     if (slot) {
         hipError_t he = hipEventRecord(slot->done, e->stream);
@@ -567,5 +604,5 @@ int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *a, uint32_t 
 }
 
 extern "C" int hsw_witness_digests(hsw_engine *e, const hsw_digests_args *a) try {
-    return hsw_witness_digests_impl(e, a, nullptr);
+    return hsw_witness_digests_impl(e, a, nullptr, nullptr);
 } HSW_NO_UNWIND

@@ -76,11 +76,22 @@ inline int set_err(hsw_engine *e, int status, const char *what, hipError_t he = 
     return status;
 }
 
-namespace hsw { struct SmallFrames; }
+namespace hsw { struct SmallFrames; struct ContextPeriod; }
 bool hsw_small_eligible(const hsw_engine *e, size_t n_blocks);
+// period: context images (hsw_kernels.h ContextPeriod; NULL = off) -- the gadget's HSW_GADGET_CONTEXT_IMAGES launches
 int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const hsw::SmallFrames *frames,
-                            uint32_t *host_next_states);
-int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *args, uint32_t *dev_next_states);
+                            uint32_t *host_next_states, const hsw::ContextPeriod *period);
+int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *args, uint32_t *dev_next_states,
+                             const hsw::ContextPeriod *period);
+int hsw_witness_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n, const uint8_t *d_blocks,
+                            const uint32_t *d_pre_states, const uint32_t *d_next_states, void *d_gate, void *d_lookup,
+                            const hsw_pack_plan *pack, uint32_t flags, const hsw::ContextPeriod *period);
+int hsw_verify_blocks_impl(hsw_engine *e, const hsw_witness_args *args, hsw_verify_report *report,
+                           const hsw::ContextPeriod *period);
+int hsw_verify_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n, const uint8_t *d_blocks,
+                           const uint32_t *d_pre_states, const uint32_t *d_next_states, const void *d_gate,
+                           const void *d_lookup, const hsw_pack_plan *pack, uint32_t flags, hsw_verify_report *report,
+                           const hsw::ContextPeriod *period);
 
 // Makes the engine's device current for the scope of one call (a no-op when it already is: the usual case,
 // and these scopes nest three deep on the latency-critical path of a small digest).

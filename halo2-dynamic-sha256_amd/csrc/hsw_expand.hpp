@@ -1420,9 +1420,17 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
     em.d16 = s_d16;
     em.tab = static_cast<const uint4 *>(p.mont_tab);
     {   // FlexGate column packing: gaps of the breaks at or before this block, and the (<= 2) inside it
-        u64 first = (u64)blk * (u64)LY::GATE_CELLS;
+        u64 first = (u64)blk * (u64)LY::GATE_CELLS, ctx_base = 0;
         if constexpr (RC)          // whole-digest streams: every frame_every blocks a digest frame sits in between
-            if (p.frame_every) first += (u64)(blk / p.frame_every) * p.frame_cells;
+            if (p.frame_every) {
+                const u32 ctx = (u32)blk / (u32)p.frame_every;       // wave-uniform (blk is the workgroup's block)
+                if (p.ctx_cells) {     // context images: the breaks are one context's, the image of context ctx follows ctx_cells further
+                    first -= (u64)ctx * (u64)p.frame_every * (u64)LY::GATE_CELLS;
+                    ctx_base = (u64)ctx * p.ctx_cells;
+                } else {
+                    first += (u64)ctx * p.frame_cells;
+                }
+            }
         u64 gap0 = 0;
         em.brk1 = em.brk2 = 0xffffffffu;
         em.gap1 = em.gap2 = 0;
@@ -1435,9 +1443,9 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
             }
         }
         if constexpr (REPR == 2)   // compact: 8-byte cells
-            em.out = reinterpret_cast<uint4 *>(reinterpret_cast<u64 *>(p.gate) + (size_t)(first + gap0));
+            em.out = reinterpret_cast<uint4 *>(reinterpret_cast<u64 *>(p.gate) + (size_t)(ctx_base + first + gap0));
         else
-            em.out = reinterpret_cast<uint4 *>(p.gate) + (size_t)(first + gap0) * 2u;
+            em.out = reinterpret_cast<uint4 *>(p.gate) + (size_t)(ctx_base + first + gap0) * 2u;
     }
     size_t lk_blk = (size_t)blk * (size_t)LY::LOOKUP_CELLS;
     if constexpr (RC)

@@ -82,6 +82,9 @@ struct FrameBreaks {      // entries past n: cell = UINT64_MAX, gap = 0 (the dev
     uint32_t n;
     uint64_t cell[16];
     uint64_t gap[16];
+    // context images (0 = off): the stream is K Contexts of ctx_stream cells each, and the breaks are those of one
+    // of them -- stream cell i of Context h = i / ctx_stream sits at h * ctx_image + place(i - h * ctx_stream)
+    uint64_t ctx_stream, ctx_image;
 };
 
 // Whole-digest launches of the small-batch kernel (hsw_small.hpp): the frames are written by waves of the

@@ -61,7 +61,9 @@ struct Out {
     // The walk over the break table (scalar loads, one round trip each) is remembered as the column segment
     // [seg_lo, seg_hi) it found: a thread's cells nearly always share one.
     mutable u64 seg_lo = 1, seg_hi = 0, seg_gap = 0;
+    u64 at0 = 0;        // context images: first stream cell of this digest's Context (gate then points at its image)
     DEV u64 place(u64 at) const {
+        at -= at0;
         if (at >= seg_lo && at < seg_hi) return at + seg_gap;
         u64 gap = 0, lo = 0, hi = ~0ull;
         for (u32 k = 0; k < brk->n; k++) {
@@ -101,7 +103,12 @@ template <bool MONT, class StateWord>
 DEV void frame_cells(const FrameDesc &d, const uint8_t *blocks, const u64 *inv_tbl, uint4 *gate, uint4 *lookup,
                      const FrameBreaks &brk, u32 parts, u32 gtid, u32 nthreads, StateWord state_word) {
     using namespace frame;
-    const Out<MONT> o{gate, lookup, &brk};      // (its segment cache is per thread)
+    Out<MONT> o{gate, lookup, &brk};            // (its segment cache is per thread)
+    if (brk.ctx_stream) {                       // context images: this digest's Context and its own image (wave-uniform)
+        const u64 ctx = d.prologue_cell / brk.ctx_stream;
+        o.gate = gate + 2u * (size_t)(ctx * brk.ctx_image);
+        o.at0 = ctx * brk.ctx_stream;
+    }
     const u64 P0 = d.prologue_cell, E0 = d.epilogue_cell;
     const u32 N = d.n_blocks;
     const u64 max_bytes = (u64)N * 64u;

@@ -20,8 +20,18 @@
 // library-internal entry points of hsw_api.cpp (hsw_engine.hpp)
 bool hsw_small_eligible(const hsw_engine *e, size_t n_blocks);
 int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const hsw::SmallFrames *frames,
-                            uint32_t *host_next_states);
-int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *args, uint32_t *dev_next_states);
+                            uint32_t *host_next_states, const hsw::ContextPeriod *period);
+int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *args, uint32_t *dev_next_states,
+                             const hsw::ContextPeriod *period);
+int hsw_witness_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n, const uint8_t *d_blocks,
+                            const uint32_t *d_pre_states, const uint32_t *d_next_states, void *d_gate, void *d_lookup,
+                            const hsw_pack_plan *pack, uint32_t flags, const hsw::ContextPeriod *period);
+int hsw_verify_blocks_impl(hsw_engine *e, const hsw_witness_args *args, hsw_verify_report *report,
+                           const hsw::ContextPeriod *period);
+int hsw_verify_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n, const uint8_t *d_blocks,
+                           const uint32_t *d_pre_states, const uint32_t *d_next_states, const void *d_gate,
+                           const void *d_lookup, const hsw_pack_plan *pack, uint32_t flags, hsw_verify_report *report,
+                           const hsw::ContextPeriod *period);
 
 namespace hsw {
 
@@ -228,7 +238,8 @@ void Context::free_compact_staging() {
     wide_cap = 0;
 }
 
-int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool whole_digest, bool independent) const {
+int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool whole_digest, bool independent,
+                                     bool context_images) const {
     if (!engine || !out) return HSW_ERR_INVALID_ARG;
     *out = nullptr;
     hsw_shape s;
@@ -255,6 +266,7 @@ int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool who
         if (s.mode != HSW_MODE_HALO2_INTERNALS) { delete c; return HSW_ERR_INVALID_ARG; }
         c->whole = true;
         c->independent = independent;
+        c->context_images = context_images;
         // the Context's zero cell: one, or one per digest when every digest is a Context of its own
         uint64_t cells = independent ? max_variable_byte_sizes.size() : 1, lookups = 0;
         for (size_t b : max_variable_byte_sizes) {
@@ -268,6 +280,8 @@ int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool who
             if (rc != HSW_OK) { delete c; return rc; }
             cells += fs.digest_cells;
             lookups += fs.digest_lookups;
+            c->ctx_digest_cells = fs.digest_cells;            // (context images: every digest has this shape)
+            c->ctx_own_lookups = fs.digest_lookups;
         }
         c->gate_capacity = cells;
         c->lookup_capacity = c->own_lookup_capacity = lookups;
@@ -315,18 +329,17 @@ int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool who
     return HSW_OK;
 }
 
-int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows) {
-    if (!whole || blocks_done != 0 || gate_cursor != 0) return HSW_ERR_INVALID_ARG;
-    if (independent) return HSW_ERR_UNSUPPORTED;         // K regions in one stream: linear only
+// The FlexGate column breaks of `sizes` digests laid out from row `row0` with a Context that has (or has not)
+// already loaded its zero cell: break k before stream cell bc[k], leaving bg[k] tail rows of its column unused.
+static int column_breaks(const hsw_shape &shape, const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows,
+                         uint64_t row0, bool zero_loaded, std::vector<uint64_t> &bc, std::vector<uint64_t> &bg) {
     const uint64_t G = shape.gate_cells_per_block;
-    if (rows < G + 16) return HSW_ERR_INVALID_ARG;        // keeps a block inside <= 2 columns (kernel: <= 2 breaks per block)
-    if (origin_row >= rows) return HSW_ERR_INVALID_ARG;   // the Context's next free row lies inside its column
     size_t n = 0;
     if (hsw_gate_tape(&shape, nullptr, 0, &n) != HSW_OK) return HSW_ERR_INVALID_ARG;
     std::vector<uint8_t> block_tape(n);
     hsw_gate_tape(&shape, block_tape.data(), n, nullptr);
-    std::vector<uint64_t> bc, bg;
-    uint64_t row = origin_row, cell = 0;                  // the Context's next free row (hsw_gadget_set_origin)
+    bc.clear(); bg.clear();
+    uint64_t row = row0, cell = 0;                        // the Context's next free row (hsw_gadget_set_origin)
     auto walk = [&](const std::vector<uint8_t> &lens) {
         for (uint8_t len : lens) {
             if (row + len >= rows) {                      // halo2-lib v0.2.x assign_region: next column (A3-iii)
@@ -336,7 +349,7 @@ int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint6
             row += len; cell += len;
         }
     };
-    bool zero = origin_zero_loaded;                       // a Context that already caches its zero cell assigns none
+    bool zero = zero_loaded;                              // a Context that already caches its zero cell assigns none
     for (size_t b : sizes) {
         for (int section = 0; section < 2; section++) {
             if (section == 1) {
@@ -354,16 +367,30 @@ int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint6
             walk(t);
         }
     }
-    if (bc.size() > HSW_MAX_BREAKS) return HSW_ERR_TOO_LARGE;
+    return bc.size() > HSW_MAX_BREAKS ? HSW_ERR_TOO_LARGE : HSW_OK;
+}
+
+int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows) {
+    if (!whole || blocks_done != 0 || gate_cursor != 0) return HSW_ERR_INVALID_ARG;
+    if (independent && !context_images) return HSW_ERR_UNSUPPORTED;   // K regions in one stream: linear only
+    const uint64_t G = shape.gate_cells_per_block;
+    if (rows < G + 16) return HSW_ERR_INVALID_ARG;        // keeps a block inside <= 2 columns (kernel: <= 2 breaks per block)
+    if (origin_row >= rows) return HSW_ERR_INVALID_ARG;   // the Context's next free row lies inside its column
+    std::vector<uint64_t> bc, bg;
+    // context images: ONE Context's walk (every Context is laid out alike), K images of it
+    const std::vector<size_t> one(sizes.begin(), sizes.begin() + (sizes.empty() ? 0 : 1));
+    int rc = column_breaks(shape, context_images ? one : sizes, rc_inputs, rows, origin_row, origin_zero_loaded, bc, bg);
+    if (rc != HSW_OK) return rc;
     const uint64_t cols = bc.size() + 1;
+    const size_t image_cells = (size_t)(cols * rows) * (context_images ? init_capacity : 1);
     int device = 0;
     hsw_engine_stream(engine, nullptr, &device);
     DeviceScope ds2(device);
     if (!ds2.ok) return HSW_ERR_NO_DEVICE;
     // (outstanding work on the old image: the callers -- hsw_gadget_set_columns / _set_origin -- run on a drained engine)
     void *img = nullptr;
-    hipError_t he = hipMalloc(&img, (size_t)(cols * rows) * HSW_CELL_BYTES);
-    if (he == hipSuccess) he = hipMemset(img, 0, (size_t)(cols * rows) * HSW_CELL_BYTES);   // unassigned advice cells are 0
+    hipError_t he = hipMalloc(&img, image_cells * HSW_CELL_BYTES);
+    if (he == hipSuccess) he = hipMemset(img, 0, image_cells * HSW_CELL_BYTES);   // unassigned advice cells are 0
     if (he != hipSuccess) { if (img) (void)hipFree(img); return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP; }
     (void)hipFree(d_gate);
     d_gate = img;
@@ -376,6 +403,7 @@ int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint6
 }
 
 void Context::position(uint64_t cell, uint64_t *column, uint64_t *row) const {
+    if (context_images && max_rows) cell %= ctx_stream();  // the owning Context's own stream cell
     uint64_t at = cell + origin_row;
     for (size_t k = 0; k < break_cell.size(); k++)
         if (break_cell[k] <= cell) at += break_gap[k];
@@ -383,9 +411,22 @@ void Context::position(uint64_t cell, uint64_t *column, uint64_t *row) const {
     else { if (column) *column = origin_column; if (row) *row = at; }
 }
 
+uint64_t Context::image_cell(uint64_t cell) const {
+    uint64_t base = 0;
+    if (context_images && max_rows) {
+        const uint64_t C = ctx_stream(), h = cell / C;
+        base = h * ctx_image();
+        cell -= h * C;
+    }
+    uint64_t at = base + cell + (max_rows ? origin_row : 0);
+    for (size_t k = 0; k < break_cell.size(); k++)
+        if (break_cell[k] <= cell) at += break_gap[k];
+    return at;
+}
+
 int Context::set_origin(uint64_t column, uint64_t row, bool zero_cell_loaded, uint64_t lookups_queued) {
     if (!whole || blocks_done != 0 || gate_cursor != 0 || lookup_cursor != origin_lookups) return HSW_ERR_INVALID_ARG;
-    if (independent) return HSW_ERR_UNSUPPORTED;
+    if (independent) return HSW_ERR_UNSUPPORTED;          // (context images: set_origin_images)
     if (max_rows && row >= max_rows) return HSW_ERR_INVALID_ARG;
     if (lookups_queued != origin_lookups) {
         // the lookup-advice stream is indexed from the Context's first queued cell: [0, lookups_queued) are the caller's
@@ -407,6 +448,59 @@ int Context::set_origin(uint64_t column, uint64_t row, bool zero_cell_loaded, ui
     lookup_cursor = lookups_queued;
     zero_loaded = zero_cell_loaded;
     // without the zero cell the stream is one cell shorter
+    return HSW_OK;
+}
+
+int Context::set_origin_images(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t column, uint64_t row,
+                               bool zero_cell_loaded, uint64_t lookups_queued) {
+    if (!whole || !context_images || blocks_done != 0 || gate_cursor != 0 || lookup_cursor != origin_lookups)
+        return HSW_ERR_INVALID_ARG;
+    if (max_rows && row >= max_rows) return HSW_ERR_INVALID_ARG;
+    // 1. the new layout, checked in full: nothing is touched if it cannot be had
+    std::vector<uint64_t> bc, bg;
+    const bool relayout = max_rows && (row != origin_row || zero_cell_loaded != origin_zero_loaded);
+    if (relayout) {
+        const std::vector<size_t> one(sizes.begin(), sizes.begin() + (sizes.empty() ? 0 : 1));
+        const int rc = column_breaks(shape, one, rc_inputs, max_rows, row, zero_cell_loaded, bc, bg);
+        if (rc != HSW_OK) return rc;
+    }
+    // 2. the new buffers: every Context's lookup column, every Context's image (zeroed: unassigned advice cells are 0)
+    int device = 0;
+    hsw_engine_stream(engine, nullptr, &device);
+    DeviceScope ds(device);
+    if (!ds.ok) return HSW_ERR_NO_DEVICE;
+    const size_t K = init_capacity;
+    void *lk = nullptr, *img = nullptr;
+    hipError_t he = hipSuccess;
+    const size_t lcells = K * (size_t)(lookups_queued + ctx_own_lookups);
+    if (lookups_queued != origin_lookups) {
+        he = hipMalloc(&lk, (lcells ? lcells : 1) * HSW_CELL_BYTES);
+        if (he == hipSuccess) he = hipMemset(lk, 0, (lcells ? lcells : 1) * HSW_CELL_BYTES);
+    }
+    const uint64_t cols = bc.size() + 1;
+    if (he == hipSuccess && relayout) {
+        he = hipMalloc(&img, K * (size_t)(cols * max_rows) * HSW_CELL_BYTES);
+        if (he == hipSuccess) he = hipMemset(img, 0, K * (size_t)(cols * max_rows) * HSW_CELL_BYTES);
+    }
+    if (he != hipSuccess) {
+        if (lk) (void)hipFree(lk);
+        if (img) (void)hipFree(img);
+        return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP;
+    }
+    // 3. commit
+    if (lk) { (void)hipFree(d_lookup); d_lookup = lk; }
+    if (img) {
+        (void)hipFree(d_gate);
+        d_gate = img;
+        columns = cols;
+        break_cell.swap(bc);
+        break_gap.swap(bg);
+    }
+    if (lk || img) free_compact_staging();
+    origin_column = column; origin_row = row; origin_zero_loaded = zero_cell_loaded; origin_lookups = lookups_queued;
+    lookup_capacity = K * (lookups_queued + ctx_own_lookups);
+    lookup_cursor = lookups_queued;
+    zero_loaded = zero_cell_loaded;
     return HSW_OK;
 }
 
@@ -527,7 +621,7 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
             a.chip_col_stride = ctx.chip_col_stride;
             a.d_next_states = d_next;
             a.flags = ctx.repr_flags;
-            rc = hsw_witness_blocks_impl(ctx.engine, &a, nullptr, small ? ctx.dp_next + 8 * b0 : nullptr);
+            rc = hsw_witness_blocks_impl(ctx.engine, &a, nullptr, small ? ctx.dp_next + 8 * b0 : nullptr, nullptr);
             next_in_pinned = small && rc == HSW_OK;
         } else {
             // whole-digest stream: prologue | [zero cell] | blocks | epilogue per digest (hsw_frame.hpp).
@@ -536,6 +630,11 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
             const size_t LK = ctx.shape.lookup_cells_per_block;
             uint64_t gc = ctx.gate_cursor, lc = ctx.lookup_cursor;
             bool zero_loaded = ctx.zero_loaded;
+            // every digest a Context of its own: its own zero cell unless the Contexts come with one (context images)
+            const bool own_zero = ctx.independent && !ctx.origin_zero_loaded;
+            // context images: one Context's period in the gate image and the lookup column (NULL: linear streams)
+            const ContextPeriod period{ctx.ctx_stream(), ctx.ctx_image()};
+            const ContextPeriod *per = ctx.context_images && ctx.max_rows ? &period : nullptr;
             frames.resize(n);
             std::vector<hsw_frame_shape> fss(n);
             size_t ob = 0;
@@ -550,10 +649,12 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 d.num_round = (uint32_t)plans[i].num_round;
                 d.precomputed_round = (uint32_t)plans[i].precomputed_round;
                 d.is_input_range_check = is_input_range_check ? 1u : 0u;
+                // context images: Context h's lookup column is cells [h*Lp, (h+1)*Lp), the caller's queued cells first
+                if (ctx.context_images) lc = (uint64_t)(cur_hash_idx + i) * ctx.ctx_lookups() + ctx.origin_lookups;
                 r.prologue_cell = d.prologue_cell = gc;      gc += fss[i].prologue_cells;
                 r.prologue_lookup = d.prologue_lookup = lc;  lc += fss[i].prologue_lookups;
                 d.zero_cell = ~0ull;
-                if (!zero_loaded || ctx.independent) { d.zero_cell = gc++; zero_loaded = true; }   // compression.rs:34 of the first block of a Context
+                if (!zero_loaded || own_zero) { d.zero_cell = gc++; zero_loaded = true; }   // compression.rs:34 of the first block of a Context
                 r.block_cell = gc;                           gc += (uint64_t)d.n_blocks * G;
                 r.block_lookup = lc;                         lc += (uint64_t)d.n_blocks * LK;
                 r.epilogue_cell = d.epilogue_cell = gc;      gc += fss[i].epilogue_cells;
@@ -574,7 +675,11 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 a.d_pre_states = d_pre + 8 * ob;
                 a.n_blocks = run_blocks;
                 a.spread_cursor0 = cursor;
-                a.d_gate = static_cast<uint8_t *>(ctx.gate_stream()) + (size_t)results[i].block_cell * cb;
+                // (context images: the run's first block in ITS Context's image; the breaks below are that Context's)
+                const uint64_t per_C = per ? per->stream_cells : 0, per_S = per ? per->image_cells : 0;
+                const uint64_t ctx0 = per ? results[i].block_cell / per_C : 0;
+                const uint64_t local_block_cell = results[i].block_cell - ctx0 * per_C;
+                a.d_gate = static_cast<uint8_t *>(ctx.gate_stream()) + (size_t)(ctx0 * per_S + local_block_cell) * cb;
                 a.d_chip_dense = static_cast<uint8_t *>(ctx.d_chip_dense) + (size_t)row_shift * cb;
                 a.d_chip_spread = static_cast<uint8_t *>(ctx.d_chip_spread) + (size_t)row_shift * cb;
                 a.chip_col_stride = ctx.chip_col_stride;
@@ -584,12 +689,13 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 a.frame_every = nb;
                 // (between the block streams of two digests: one epilogue, the next prologue -- and the next Context's
                 //  zero cell when every digest is a Context of its own)
-                a.frame_cells = fss[i].epilogue_cells + fss[i].prologue_cells + (ctx.independent ? 1u : 0u);
-                a.frame_lookups = fss[i].epilogue_lookups + fss[i].prologue_lookups;
+                a.frame_cells = fss[i].epilogue_cells + fss[i].prologue_cells + (own_zero ? 1u : 0u);
+                // (context images: and the next Context's caller-owned lookup cells)
+                a.frame_lookups = fss[i].epilogue_lookups + fss[i].prologue_lookups + (ctx.context_images ? ctx.origin_lookups : 0u);
                 hsw_pack_plan plan{};
                 if (ctx.max_rows) {
                     // column breaks relative to this launch's first cell; breaks before it are pure offsets
-                    const uint64_t base = results[i].block_cell;
+                    const uint64_t base = local_block_cell;
                     plan.n_breaks = (uint32_t)ctx.break_cell.size();
                     for (size_t k = 0; k < ctx.break_cell.size(); k++) {
                         plan.break_cell[k] = ctx.break_cell[k] > base ? ctx.break_cell[k] - base : 0;
@@ -612,10 +718,10 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                     da.frame_pack = ctx.max_rows ? &abs_plan : nullptr;
                     da.host_next_states = h_next + 8 * ob;
                     // (the device alias of the context's own pinned staging: no runtime lookup per call)
-                    rc = hsw_witness_digests_impl(ctx.engine, &da, ctx.dp_next + 8 * (b0 + ob));
+                    rc = hsw_witness_digests_impl(ctx.engine, &da, ctx.dp_next + 8 * (b0 + ob), per);
                     next_in_pinned = rc == HSW_OK;
                 } else {
-                    rc = hsw_witness_blocks_ex(ctx.engine, &a);
+                    rc = hsw_witness_blocks_impl(ctx.engine, &a, nullptr, nullptr, per);
                 }
                 ob += run_blocks;
                 i = j;
@@ -627,8 +733,8 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                     plan.break_cell[k] = ctx.break_cell[k];
                     plan.break_gap[k] = ctx.break_gap[k];
                 }
-                rc = hsw_witness_frames(ctx.engine, frames.data(), n, in_blocks, in_pre, ctx.d_next_states,
-                                        ctx.gate_stream(), ctx.d_lookup, ctx.max_rows ? &plan : nullptr, ctx.repr_flags);
+                rc = hsw_witness_frames_impl(ctx.engine, frames.data(), n, in_blocks, in_pre, ctx.d_next_states,
+                                             ctx.gate_stream(), ctx.d_lookup, ctx.max_rows ? &plan : nullptr, ctx.repr_flags, per);
             }
             if (rc == HSW_OK) { new_gate_cursor = gc; new_lookup_cursor = lc; }
         }
@@ -707,9 +813,13 @@ int hsw_gadget_create(hsw_engine *e, const size_t *max_variable_byte_sizes, size
 int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, size_t n_hashes,
                          int is_input_range_check, uint32_t flags, hsw_gadget **out) try {
     if (!e || !out || (!max_variable_byte_sizes && n_hashes)) return HSW_ERR_INVALID_ARG;
-    if (flags & ~(HSW_GADGET_WHOLE_DIGEST | HSW_GADGET_INDEPENDENT)) return HSW_ERR_INVALID_ARG;
+    if (flags & ~(HSW_GADGET_WHOLE_DIGEST | HSW_GADGET_INDEPENDENT | HSW_GADGET_CONTEXT_IMAGES)) return HSW_ERR_INVALID_ARG;
     if ((flags & HSW_GADGET_INDEPENDENT) && !(flags & HSW_GADGET_WHOLE_DIGEST)) return HSW_ERR_INVALID_ARG;
+    const bool images = (flags & HSW_GADGET_CONTEXT_IMAGES) != 0;
+    if (images && !(flags & HSW_GADGET_INDEPENDENT)) return HSW_ERR_INVALID_ARG;
     *out = nullptr;
+    for (size_t i = 1; images && i < n_hashes; i++)        // K proofs of ONE circuit: every Context laid out alike
+        if (max_variable_byte_sizes[i] != max_variable_byte_sizes[0]) return HSW_ERR_UNSUPPORTED;
     hsw_shape s;
     int rc = hsw_engine_shape(e, &s);
     if (rc != HSW_OK) return rc;
@@ -718,7 +828,8 @@ int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, s
     std::vector<size_t> sizes(max_variable_byte_sizes, max_variable_byte_sizes + n_hashes);
     rc = hsw::Sha256DynamicConfig::configure(sizes, s.num_bits_lookup, s.num_advice_columns,
                                              is_input_range_check != 0, &g->cfg);
-    if (rc == HSW_OK) rc = g->cfg.new_context(e, &g->ctx, (flags & HSW_GADGET_WHOLE_DIGEST) != 0, (flags & HSW_GADGET_INDEPENDENT) != 0);
+    if (rc == HSW_OK) rc = g->cfg.new_context(e, &g->ctx, (flags & HSW_GADGET_WHOLE_DIGEST) != 0, (flags & HSW_GADGET_INDEPENDENT) != 0,
+                                              images);
     if (rc != HSW_OK) { delete g; return rc; }
     *out = g;
     return HSW_OK;
@@ -836,6 +947,15 @@ int hsw_gadget_set_origin(hsw_gadget *g, uint64_t column, uint64_t row, int zero
     int rc = hsw_engine_synchronize(c.engine);
     if (rc != HSW_OK) return rc;
     const uint64_t old[4] = {c.origin_column, c.origin_row, c.origin_zero_loaded ? 1u : 0u, c.origin_lookups};
+    if (c.context_images) {
+        // every Context alike; the whole new layout is checked before anything is freed or reallocated
+        rc = c.set_origin_images(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, column, row,
+                                 zero_cell_loaded != 0, lookups_already_queued);
+        if (rc != HSW_OK) return rc;
+        if (old[2] != (zero_cell_loaded ? 1u : 0u)) { hsw::free_region_tape(g->tape); g->tape = nullptr; }
+        else if (old[1] != row) hsw::drop_region_tape_positions(g->tape);
+        return HSW_OK;
+    }
     rc = c.set_origin(column, row, zero_cell_loaded != 0, lookups_already_queued);
     if (rc != HSW_OK) return rc;
     // the region tape (hsw_replay.cpp) numbers stream cells: only a zero cell that comes or goes changes it; a new
@@ -957,7 +1077,20 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
             he = hipMemcpyAsync(static_cast<uint8_t *>(h) + cell0 * cb, static_cast<const uint8_t *>(d) + cell0 * cb,
                                 cells * cb, hipMemcpyDeviceToHost, stream);
     };
-    if (dst->gate) {
+    if (dst->gate && c.context_images && c.max_rows) {
+        // K images back to back, host layout = device layout: used rows of every assigned Context's columns
+        const uint64_t C = c.ctx_stream(), S = c.ctx_image();
+        uint64_t last_col = 0, last_row = 0;
+        c.position(C - 1, &last_col, &last_row);
+        last_row += 1;
+        last_col -= c.origin_column;
+        for (uint64_t h = 0; h < g->cfg.cur_hash_idx; h++)
+            for (uint64_t k = 0; k <= last_col; k++) {
+                const uint64_t used = k < last_col ? c.max_rows - c.break_gap[k] : last_row;
+                const uint64_t first = k == 0 ? c.origin_row : 0;    // rows above the origin are the caller's
+                if (used > first) copy(dst->gate, c.d_gate, (size_t)(h * S + k * c.max_rows + first), (size_t)(used - first));
+            }
+    } else if (dst->gate) {
         if (c.whole && c.max_rows) {
             // used rows of column k: up to its break (max_rows - gap), the last column up to the cursor
             uint64_t last_col = 0, last_row = 0;
@@ -973,8 +1106,13 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
             copy(dst->gate, c.d_gate, 0, cells);
         }
     }
-    if (dst->lookup && c.d_lookup)
+    if (dst->lookup && c.d_lookup && c.context_images) {
+        const uint64_t Lp = c.ctx_lookups();               // Context h: its own entries after the caller's queued cells
+        for (uint64_t h = 0; h < g->cfg.cur_hash_idx; h++)
+            copy(dst->lookup, c.d_lookup, (size_t)(h * Lp + c.origin_lookups), (size_t)c.ctx_own_lookups);
+    } else if (dst->lookup && c.d_lookup) {
         copy(dst->lookup, c.d_lookup, (size_t)c.origin_lookups, (size_t)(c.lookup_cursor - c.origin_lookups));
+    }
     const uint32_t ncols = c.shape.num_advice_columns;
     const size_t rows = (size_t)((c.num_limb_sum + ncols - 1) / ncols);
     for (uint32_t k = 0; k < ncols; k++) {
@@ -989,6 +1127,7 @@ int hsw_gadget_download_region_compact(hsw_gadget *g, hsw_region_compact *dst) t
     if (!g || !dst) return HSW_ERR_INVALID_ARG;
     hsw::Context &c = *g->ctx;
     if (c.repr_flags != HSW_REPR_CANONICAL) return HSW_ERR_UNSUPPORTED;      // packs canonical 32-byte cells
+    if (c.context_images) return HSW_ERR_UNSUPPORTED;                         // one image per Context: not packed here
     if (!dst->wide && dst->wide_cap) return HSW_ERR_INVALID_ARG;
     hipStream_t stream = nullptr;
     int device = 0;
@@ -1073,6 +1212,7 @@ int hsw_region_widen(const uint64_t *compact, size_t n_cells, uint64_t stream_id
 
 int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx) try {
     if (!g || hash_idx > g->cfg.max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
+    if (g->ctx->context_images) return HSW_ERR_UNSUPPORTED;       // K proofs of one circuit: nothing to deal out
     int rc = hsw_engine_synchronize(g->ctx->engine);
     if (rc != HSW_OK) return rc;
     hsw::Context &c = *g->ctx;
@@ -1117,6 +1257,10 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
     hsw_pack_plan abs_plan{};
     abs_plan.n_breaks = (uint32_t)c.break_cell.size();
     for (size_t k = 0; k < c.break_cell.size(); k++) { abs_plan.break_cell[k] = c.break_cell[k]; abs_plan.break_gap[k] = c.break_gap[k]; }
+    const bool own_zero = c.independent && !c.origin_zero_loaded;
+    const hsw::ContextPeriod period{c.ctx_stream(), c.ctx_image()};
+    const hsw::ContextPeriod *per = c.context_images && c.max_rows ? &period : nullptr;
+    const uint64_t per_C = per ? period.stream_cells : 0, per_S = per ? period.image_cells : 0;
     for (const hsw::Context::BatchRecord &b : c.batches) {
         const uint8_t *in_blocks = b.inputs_in_pinned ? c.dp_blocks : c.d_blocks;
         const uint32_t *in_pre = b.inputs_in_pinned ? c.dp_pre : c.d_pre_states;
@@ -1150,26 +1294,27 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
             a.d_blocks = in_blocks + 64 * fb; a.d_pre_states = in_pre + 8 * fb; a.n_blocks = run_blocks;
             a.spread_cursor0 = (uint64_t)fb * c.shape.limb_calls_per_block;
             const uint64_t row_shift = a.spread_cursor0 / ncols;
-            a.d_gate = static_cast<uint8_t *>(c.gate_stream()) + (size_t)r0.block_cell * cb;
+            const uint64_t ctx0 = per ? r0.block_cell / per_C : 0, local_block_cell = r0.block_cell - ctx0 * per_C;
+            a.d_gate = static_cast<uint8_t *>(c.gate_stream()) + (size_t)(ctx0 * per_S + local_block_cell) * cb;
             a.d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + (size_t)row_shift * cb;
             a.d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + (size_t)row_shift * cb;
             a.chip_col_stride = c.chip_col_stride;
             a.d_next_states = c.d_next_states + 8 * fb;
             a.d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)r0.block_lookup * cb;
-            a.frame_every = nb; a.frame_cells = fs.epilogue_cells + fs.prologue_cells + (c.independent ? 1u : 0u);
-            a.frame_lookups = fs.epilogue_lookups + fs.prologue_lookups;
+            a.frame_every = nb; a.frame_cells = fs.epilogue_cells + fs.prologue_cells + (own_zero ? 1u : 0u);
+            a.frame_lookups = fs.epilogue_lookups + fs.prologue_lookups + (c.context_images ? c.origin_lookups : 0u);
             a.flags = b.repr_flags;
             hsw_pack_plan rel{};
             if (c.max_rows) {
                 rel.n_breaks = abs_plan.n_breaks;
                 for (uint32_t k = 0; k < rel.n_breaks; k++) {
-                    rel.break_cell[k] = abs_plan.break_cell[k] > r0.block_cell ? abs_plan.break_cell[k] - r0.block_cell : 0;
+                    rel.break_cell[k] = abs_plan.break_cell[k] > local_block_cell ? abs_plan.break_cell[k] - local_block_cell : 0;
                     rel.break_gap[k] = abs_plan.break_gap[k];
                 }
                 a.pack = &rel;
             }
             hsw_verify_report r;
-            rc = hsw_verify_blocks(c.engine, &a, &r);
+            rc = hsw_verify_blocks_impl(c.engine, &a, &r, per);
             if (rc != HSW_OK) return rc;
             merge(r);
             std::vector<hsw_frame_desc> descs(j - i);
@@ -1185,14 +1330,48 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
                 d.zero_cell = rk.block_cell == rk.prologue_cell + fs.prologue_cells + 1 ? rk.block_cell - 1 : ~0ull;
                 blk += rk.n_blocks;
             }
-            rc = hsw_verify_frames(c.engine, descs.data(), descs.size(), in_blocks, in_pre, c.d_next_states, c.gate_stream(),
-                                   c.d_lookup, c.max_rows ? &abs_plan : nullptr, b.repr_flags, &r);
+            rc = hsw_verify_frames_impl(c.engine, descs.data(), descs.size(), in_blocks, in_pre, c.d_next_states, c.gate_stream(),
+                                        c.d_lookup, c.max_rows ? &abs_plan : nullptr, b.repr_flags, &r, per);
             if (rc != HSW_OK) return rc;
             merge(r);
             ob += run_blocks;
             i = j;
         }
     }
+    return HSW_OK;
+} HSW_NO_UNWIND
+
+int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region *out) try {
+    if (!g || !out) return HSW_ERR_INVALID_ARG;
+    const hsw::Context &c = *g->ctx;
+    if (!c.context_images || h >= g->cfg.max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
+    std::memset(out, 0, sizeof *out);
+    const size_t cb = HSW_CELL_BYTES;                       // whole-digest contexts: 32-byte cells
+    const uint32_t ncols = c.shape.num_advice_columns;
+    const uint64_t nb = g->cfg.max_variable_byte_sizes[h] / 64, C = c.ctx_stream();
+    out->stream_cells = C;
+    out->first_stream_cell = h * C;
+    out->columns = c.columns;
+    out->max_rows = c.max_rows;
+    if (c.max_rows) {
+        uint64_t col = 0, row = 0;
+        c.position(C - 1, &col, &row);
+        out->last_column_rows = row + 1;
+        out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * c.ctx_image()) * cb;
+    } else {
+        out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * C) * cb;   // linear: the Context's stream
+    }
+    out->lookup_cells = c.ctx_lookups();
+    out->d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)(h * c.ctx_lookups()) * cb;
+    out->chip_rows = nb * c.shape.limb_calls_per_block / ncols;
+    out->chip_col_stride = c.chip_col_stride;
+    const size_t chip_row0 = (size_t)(h * nb * c.shape.limb_calls_per_block / ncols);
+    out->d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + chip_row0 * cb;
+    out->d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + chip_row0 * cb;
+    out->origin_column = c.origin_column;
+    out->origin_row = c.origin_row;
+    out->origin_lookups = c.origin_lookups;
+    out->assigned = h < g->cfg.cur_hash_idx ? 1u : 0u;
     return HSW_OK;
 } HSW_NO_UNWIND
 

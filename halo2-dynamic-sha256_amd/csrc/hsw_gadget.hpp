@@ -74,7 +74,8 @@ class Sha256DynamicConfig {
 
     // lib.rs:351-360: a context sized for every hash this config will assign.
     // whole_digest: also lay out digest()'s own cells (HSW_GADGET_WHOLE_DIGEST)
-    int new_context(hsw_engine *engine, Context **out, bool whole_digest = false, bool independent = false) const;
+    int new_context(hsw_engine *engine, Context **out, bool whole_digest = false, bool independent = false,
+                    bool context_images = false) const;
 
     // lib.rs:71-349.  precomputed_input_len = 0 is the reference's None.
     int digest(Context &ctx, const uint8_t *input, size_t input_len, size_t precomputed_input_len,
@@ -122,6 +123,14 @@ class Context {
     // digest, back to back) and d_lookup the lookup-advice stream next to it
     bool whole = false;
     bool independent = false;        // HSW_GADGET_INDEPENDENT: every digest is a Context of its own (K proofs in flight)
+    // HSW_GADGET_CONTEXT_IMAGES (with independent, all digests of one size): every Context has an origin, a column
+    // image and a lookup column of its own, laid out alike -- Context h's image is cells [h*S, (h+1)*S) of d_gate,
+    // its lookup column cells [h*Lp, (h+1)*Lp) of d_lookup; break_cell / break_gap are ONE Context's
+    bool context_images = false;
+    uint64_t ctx_digest_cells = 0, ctx_own_lookups = 0;   // one Context's digest cells (zero cell not counted) and lookups
+    uint64_t ctx_stream() const { return ctx_digest_cells + (origin_zero_loaded ? 0u : 1u); }   // C: stream cells per Context
+    uint64_t ctx_image() const { return columns * max_rows; }                                    // S (0 without an image)
+    uint64_t ctx_lookups() const { return origin_lookups + ctx_own_lookups; }                   // Lp
     bool zero_loaded = false;        // Context.zero_cell (first load_zero: compression.rs:34 of the first block)
     uint64_t gate_cursor = 0, gate_capacity = 0;       // cells
     void *d_lookup = nullptr;
@@ -144,6 +153,9 @@ class Context {
     bool origin_zero_loaded = false;
     uint64_t own_lookup_capacity = 0;                  // lookup_capacity - origin_lookups
     int set_origin(uint64_t column, uint64_t row, bool zero_cell_loaded, uint64_t lookups_queued);
+    // context images: the same, validated in full (layout included) before anything is freed or reallocated
+    int set_origin_images(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t column, uint64_t row,
+                          bool zero_cell_loaded, uint64_t lookups_queued);
     // device address of stream cell 0 (32-byte cells: whole-digest contexts have no compact form)
     void *gate_stream() const {
         return static_cast<uint8_t *>(d_gate) + (size_t)(max_rows ? origin_row : 0) * HSW_CELL_BYTES;
@@ -151,8 +163,10 @@ class Context {
     // Lay the whole-digest stream out as FlexGate (Vertical) advice columns of max_rows usable rows.
     // Only before the first digest.  HSW_ERR_TOO_LARGE: more than HSW_MAX_BREAKS + 1 columns.
     int set_columns(const std::vector<size_t> &max_variable_byte_sizes, bool is_input_range_check, uint64_t max_rows);
-    // (column, row) of stream cell i
+    // (column, row) of stream cell i (context images: inside its own Context's image)
     void position(uint64_t cell, uint64_t *column, uint64_t *row) const;
+    // offset of stream cell i from d_gate, in cells (origin row, column breaks and, with context images, h*S included)
+    uint64_t image_cell(uint64_t cell) const;
     void free_compact_staging();                       // the 8-byte staging follows the geometry: dropped when it changes
 };
 

@@ -55,6 +55,11 @@ struct ExpandParams {
     // frame_cells cells and the lookup stream frame_lookups cells (a digest's epilogue and the
     // next digest's prologue, written by hsw_frame_kernel); frame_every = 0: off
     uint64_t frame_every, frame_cells, frame_lookups;
+    // context images (HSW_GADGET_CONTEXT_IMAGES): every frame_every blocks are one Context of their own whose gate
+    // cells lie ctx_cells (= columns x max_rows) cells after the previous one's; block b of context b / frame_every
+    // sits at (b / frame_every) * ctx_cells + (b % frame_every) * G + the gaps of ONE context's break table
+    // (frame_cells unused; frame_lookups then includes the next context's caller-owned lookup cells).  0 = off
+    uint64_t ctx_cells;
     uint32_t *next_states_host;   // small-batch kernel only: a second copy of next_states, in pinned host memory (may be null)
     const void *mont_tab;         // HSW_K_M32 only: 3 x 256 Montgomery-form cells -- i, spread(i), i << 8 for i < 256 (hsw_api.cpp)
 };
@@ -76,6 +81,12 @@ hipError_t launch_pack64(const void *src32, void *dst8, size_t n_cells, uint64_t
 
 // dst[w] = the 32-byte cell at image position pos[w] (distinct-value delivery, hsw_replay.cpp)
 hipError_t launch_gather32(const void *image, const uint32_t *pos, void *dst, size_t n, hipStream_t stream);
+
+// The period of a context-image launch (library-internal: the gadget passes it next to the public argument
+// structs, whose layouts are fixed): a Context's gate stream is stream_cells cells long, its image image_cells.
+struct ContextPeriod {
+    uint64_t stream_cells, image_cells;
+};
 
 struct FrameDesc;   // hsw_frame.hpp
 struct FrameBreaks;

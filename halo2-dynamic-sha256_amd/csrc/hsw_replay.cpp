@@ -141,7 +141,7 @@ static int build_region_tape(const hsw_gadget *g, RegionTape **out) {
         if (!b.section(pro, g0, pro_ext)) return HSW_ERR_INVALID_ARG;
         for (int64_t src : pro.lookup_src) t->lookup_code.push_back(b.code_of(pro_ext(src)));
         gc += P;
-        if (!zero_seen || c.independent) {                // this digest's Context loads its zero cell (A4-iii)
+        if (!zero_seen || (c.independent && !c.origin_zero_loaded)) {   // this digest's Context loads its zero cell (A4-iii)
             zero_abs = (int64_t)gc;
             t->gate_code[(size_t)gc] = b.constant(0);
             gc += 1;
@@ -186,20 +186,13 @@ static int build_region_tape(const hsw_gadget *g, RegionTape **out) {
         t->end_lookup.push_back(t->lookup_code.size());
         t->end_limb.push_back(t->chip_dense_code.size());
     }
-    // (a Context that came with its zero cell leaves the one cell reserved for it unused)
-    const uint64_t unused = (c.origin_zero_loaded && !c.independent) ? 1 : 0;
+    // (a Context that came with its zero cell leaves the one cell reserved for it unused -- one per Context when
+    //  every digest is a Context of its own)
+    const uint64_t unused = c.origin_zero_loaded ? (c.independent ? (uint64_t)g->cfg.max_variable_byte_sizes.size() : 1) : 0;
     if (gc + unused != c.gate_capacity || t->lookup_code.size() != c.own_lookup_capacity) return HSW_ERR_INVALID_ARG;
     guard.p = nullptr;
     *out = t;
     return HSW_OK;
-}
-
-// stream cell -> image cell (Context::position as one index; the image's column 0 is FlexGate column origin_column)
-static inline uint64_t image_cell(const Context &c, uint64_t cell) {
-    uint64_t at = cell + (c.max_rows ? c.origin_row : 0);
-    for (size_t k = 0; k < c.break_cell.size(); k++)
-        if (c.break_cell[k] <= cell) at += c.break_gap[k];
-    return at;
 }
 
 static int ensure_tape(hsw_gadget *g) {
@@ -262,8 +255,13 @@ int hsw_gadget_download_region_distinct(hsw_gadget *g, void *distinct, size_t ca
     if (prev != device && hipSetDevice(device) != hipSuccess) return HSW_ERR_NO_DEVICE;
     hipError_t he = hipSuccess;
     if (!t.d_wit_pos) {                                   // first delivery with this layout: where every witness sits in the image
+        // (image positions are 32-bit: every Context's image together must stay below 2^32 cells)
+        if (c.max_rows && c.columns * c.max_rows * (c.context_images ? c.init_capacity : 1) >= (1ull << 32)) {
+            if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+            return HSW_ERR_TOO_LARGE;
+        }
         std::vector<uint32_t> pos(t.wit_cell.size());
-        for (size_t w = 0; w < pos.size(); w++) pos[w] = (uint32_t)image_cell(c, t.wit_cell[w]);
+        for (size_t w = 0; w < pos.size(); w++) pos[w] = (uint32_t)c.image_cell(t.wit_cell[w]);
         t.device = device;
         he = hipMalloc((void **)&t.d_wit_pos, pos.size() * sizeof(uint32_t));
         if (he == hipSuccess) he = hipMalloc(&t.d_distinct, pos.size() * (size_t)HSW_CELL_BYTES);
@@ -299,6 +297,10 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
     auto gate_part = [&](uint64_t lo, uint64_t hi) {
         if (!dst->gate) return;
         Cell *img = static_cast<Cell *>(dst->gate);
+        if (c.context_images && c.max_rows) {                     // K images: every Context walks its own breaks
+            for (uint64_t i = lo; i < hi; i++) img[c.image_cell(i)] = value(t.gate_code[i]);
+            return;
+        }
         size_t nb = 0;
         uint64_t shift = c.max_rows ? c.origin_row : 0;
         while (nb < c.break_cell.size() && c.break_cell[nb] <= lo) shift += c.break_gap[nb++];
@@ -310,6 +312,11 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
     auto lookup_part = [&](uint64_t lo, uint64_t hi) {
         if (!dst->lookup) return;
         Cell *lk = static_cast<Cell *>(dst->lookup) + c.origin_lookups;
+        if (c.context_images) {                                   // entry j of Context h = j / own: its own lookup column
+            const uint64_t own = c.ctx_own_lookups, Lp = c.ctx_lookups();
+            for (uint64_t j = lo; j < hi; j++) lk[(j / own) * Lp + j % own] = value(t.lookup_code[j]);
+            return;
+        }
         for (uint64_t j = lo; j < hi; j++) lk[j] = value(t.lookup_code[j]);
     };
     auto chip_part = [&](uint64_t lo, uint64_t hi) {              // limb call n: column n % ncols, row n / ncols

@@ -38,6 +38,7 @@ struct VerifyParams {
     // gate_cell0 + b*gate_cells + (b / frame_every)*frame_cells (lookups alike); a stream cell i sits at
     // i + the gaps of all breaks at or before it
     uint64_t gate_cell0, lookup_cell0, frame_every, frame_cells, frame_lookups;
+    uint64_t ctx_cells;            // context images: as ExpandParams::ctx_cells (0 = off)
     uint32_t n_breaks;
     uint64_t break_cell[16], break_gap[16];
     // the structure (device copies of hsw::BlockStructure)
@@ -61,6 +62,7 @@ struct FrameVerifyParams {
     const uint32_t *pre_states, *next_states;
     uint32_t n_breaks, montgomery;
     uint64_t break_cell[16], break_gap[16];
+    uint64_t ctx_stream, ctx_image;   // context images: as FrameBreaks (0 = off)
     struct Section {
         uint32_t cells, n_rows, n_assert_eq, n_assert_const, n_range, n_lookup;
         const uint8_t *kind;

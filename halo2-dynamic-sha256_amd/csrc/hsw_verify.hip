@@ -145,7 +145,11 @@ __global__ __launch_bounds__(256) void hsw_verify_kernel(VerifyParams p) {
     const u32 tid = (blockIdx.x % p.slices) * blockDim.x + threadIdx.x, nt = p.slices * blockDim.x;
     const uint4 *gate = reinterpret_cast<const uint4 *>(p.gate);
     const u64 dg = p.frame_every ? blk / p.frame_every : 0;
-    const u64 g0 = p.gate_cell0 + blk * (u64)p.gate_cells + dg * p.frame_cells;
+    u64 g0 = p.gate_cell0 + blk * (u64)p.gate_cells + dg * p.frame_cells;
+    if (p.ctx_cells) {        // context images: the block's place in its own Context, whose image starts dg * ctx_cells further
+        g0 = p.gate_cell0 + (blk - dg * p.frame_every) * (u64)p.gate_cells;
+        gate += 2u * (size_t)(dg * p.ctx_cells);
+    }
     const bool packed = p.n_breaks != 0;
     auto gcell = [&](u64 idx) -> Cell { return load_value<MONT>(gate, packed ? place(p, idx) : idx); };
     const uint8_t *bytes = p.blocks + 64 * blk;
@@ -316,7 +320,13 @@ __global__ __launch_bounds__(256) void hsw_verify_frame_kernel(FrameVerifyParams
     const uint4 *gate = reinterpret_cast<const uint4 *>(p.gate);
     const uint4 *lk = reinterpret_cast<const uint4 *>(p.lookup);
     const bool packed = p.n_breaks != 0;
-    auto gcell = [&](u64 idx) -> Cell { return load_value<MONT>(gate, packed ? place(p, idx) : idx); };
+    u64 at0 = 0;              // context images: the digest's Context starts at stream cell at0, its image ctx * ctx_image further
+    if (p.ctx_stream) {
+        const u64 ctx = d.prologue_cell / p.ctx_stream;
+        at0 = ctx * p.ctx_stream;
+        gate += 2u * (size_t)(ctx * p.ctx_image);
+    }
+    auto gcell = [&](u64 idx) -> Cell { idx -= at0; return load_value<MONT>(gate, packed ? place(p, idx) : idx); };
     u32 bad = 0, first = 0xffffffffu, first_class = 0;
     auto fail = [&](u32 cls, u32 at) { bad++; if (at < first) { first = at; first_class = cls; } };
     const u32 N = d.n_blocks;

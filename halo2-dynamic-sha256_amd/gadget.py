@@ -35,12 +35,16 @@ class AssignedHashResult:
 class Sha256DynamicConfig:
     """configure (lib.rs:49-69) + new_context (lib.rs:351-360) in one object."""
 
-    def __init__(self, engine, max_variable_byte_sizes, is_input_range_check=True, whole_digest=False, independent=False):
+    def __init__(self, engine, max_variable_byte_sizes, is_input_range_check=True, whole_digest=False, independent=False,
+                 context_images=False):
         """whole_digest: also emit the cells digest() itself allocates (lib.rs:122-178, 294-341;
         SURVEY 8 f4, assumption A4) -- needs an engine in HSW_MODE_HALO2_INTERNALS.
-        independent: every digest is a synthesis of its own (HSW_GADGET_INDEPENDENT: K proofs in one launch)."""
+        independent: every digest is a synthesis of its own (HSW_GADGET_INDEPENDENT: K proofs in one launch).
+        context_images: with independent, every proof gets a column image and lookup column of its own at the same
+        Context origin (HSW_GADGET_CONTEXT_IMAGES; all max_variable_byte_sizes equal)."""
         self.engine = engine
         self.whole_digest = bool(whole_digest)
+        self.context_images = bool(context_images)
         self.lib = engine.lib
         self.max_variable_byte_sizes = list(max_variable_byte_sizes)
         arr = (C.c_size_t * max(len(self.max_variable_byte_sizes), 1))(*self.max_variable_byte_sizes)
@@ -48,7 +52,8 @@ class Sha256DynamicConfig:
         rc = self.lib.hsw_gadget_create_ex(engine.h, arr, len(self.max_variable_byte_sizes),
                                            1 if is_input_range_check else 0,
                                            (N.HSW_GADGET_WHOLE_DIGEST if whole_digest else 0) |
-                                           (N.HSW_GADGET_INDEPENDENT if independent else 0), C.byref(h))
+                                           (N.HSW_GADGET_INDEPENDENT if independent else 0) |
+                                           (N.HSW_GADGET_CONTEXT_IMAGES if context_images else 0), C.byref(h))
         if rc != N.HSW_OK:
             raise N.HswError(rc, self.lib.hsw_last_error(engine.h).decode())
         self.h = h
@@ -122,6 +127,11 @@ class Sha256DynamicConfig:
         self._ok(self.lib.hsw_gadget_reset(self.h))
         self._n = 0
 
+    def _image_shape(self, v):
+        """Shape of the gate image: (columns, max_rows), or (K, columns, max_rows) with context images."""
+        cr = (int(v.columns), int(v.max_rows))
+        return (len(self.max_variable_byte_sizes),) + cr if self.context_images else cr
+
     def download_region(self, pinned=True):
         """hsw_gadget_download_region into (pinned) host arrays: dict of numpy uint64 arrays shaped like
         streams() -- gate (columns, max_rows, 4) or (cells, 4); lookup; dense / spread (ncols, stride, 4)."""
@@ -129,7 +139,7 @@ class Sha256DynamicConfig:
         v = self.view()
         ncols = self.engine.ncols
         img = self.whole_digest and int(v.max_rows)
-        n_gate = int(v.max_rows) * int(v.columns) if img else (
+        n_gate = int(np.prod(self._image_shape(v))) if img else (
             int(v.gate_cells) if self.whole_digest else int(v.blocks_done) * self.engine.G)
         stride = int(v.chip_col_stride)
 
@@ -145,7 +155,7 @@ class Sha256DynamicConfig:
                            dense.ctypes.data, spread.ctypes.data)
         self._ok(self.lib.hsw_gadget_download_region(self.h, C.byref(dst)))
         rows = (int(v.num_limb_sum) + ncols - 1) // ncols
-        out = dict(gate=gate[:n_gate].reshape(int(v.columns), int(v.max_rows), 4) if img else gate[:n_gate],
+        out = dict(gate=gate[:n_gate].reshape(self._image_shape(v) + (4,)) if img else gate[:n_gate],
                    dense=dense.reshape(ncols, stride, 4)[:, :rows], spread=spread.reshape(ncols, stride, 4)[:, :rows],
                    rows=rows)
         if lookup is not None:
@@ -170,7 +180,7 @@ class Sha256DynamicConfig:
         v = self.view()
         ncols = self.engine.ncols
         img = int(v.max_rows)
-        n_gate = int(v.max_rows) * int(v.columns) if img else int(v.gate_cells)
+        n_gate = int(np.prod(self._image_shape(v))) if img else int(v.gate_cells)
         stride = int(v.chip_col_stride)
         if bufs is None:          # sized for the whole gadget, so that they can be reused as more digests are assigned
             bufs = dict(distinct=self.engine.host_empty((max(int(tape.distinct_capacity), 1), 4)),
@@ -181,7 +191,7 @@ class Sha256DynamicConfig:
         dst = N.RegionHost(bufs["gate"].ctypes.data, bufs["lookup"].ctypes.data, bufs["dense"].ctypes.data, bufs["spread"].ctypes.data)
         self._ok(self.lib.hsw_gadget_replay_region(self.h, bufs["distinct"].ctypes.data, C.byref(dst), threads))
         rows = (int(v.num_limb_sum) + ncols - 1) // ncols
-        return dict(gate=bufs["gate"][:n_gate].reshape(int(v.columns), int(v.max_rows), 4) if img else bufs["gate"][:n_gate],
+        return dict(gate=bufs["gate"][:n_gate].reshape(self._image_shape(v) + (4,)) if img else bufs["gate"][:n_gate],
                     lookup=bufs["lookup"][: int(v.lookup_cells)], dense=bufs["dense"].reshape(ncols, stride, 4)[:, :rows],
                     spread=bufs["spread"].reshape(ncols, stride, 4)[:, :rows], rows=rows, distinct=bufs["distinct"][: n.value],
                     n_distinct=int(n.value), bufs=bufs)
@@ -233,6 +243,12 @@ class Sha256DynamicConfig:
         self._ok(self.lib.hsw_gadget_seek(self.h, hash_idx))
         self._n = hash_idx
 
+    def context_region(self, h):
+        """hsw_gadget_context_region: where proof h lives on the device (context-image gadgets)."""
+        r = N.ContextRegion()
+        self._ok(self.lib.hsw_gadget_context_region(self.h, h, C.byref(r)))
+        return r
+
     def cell_position(self, cell):
         c, r = C.c_uint64(), C.c_uint64()
         self._ok(self.lib.hsw_gadget_cell_position(self.h, cell, C.byref(c), C.byref(r)))
@@ -259,7 +275,10 @@ class Sha256DynamicConfig:
             return a
 
         rows = (int(v.num_limb_sum) + ncols - 1) // ncols
-        if self.whole_digest and int(v.max_rows):
+        if self.context_images and int(v.max_rows):       # (K, columns, max_rows, 4): one image per proof
+            k = len(self.max_variable_byte_sizes)
+            gate = grab(v.d_gate, k * int(v.max_rows) * int(v.columns)).reshape(k, int(v.columns), int(v.max_rows), 4)
+        elif self.whole_digest and int(v.max_rows):
             gate = grab(v.d_gate, int(v.max_rows) * int(v.columns)).reshape(int(v.columns), int(v.max_rows), 4)
         else:
             gate = grab(v.d_gate, int(v.gate_cells) if self.whole_digest else int(v.blocks_done) * G)

@@ -542,8 +542,27 @@ int hsw_gadget_create(hsw_engine *e, const size_t *max_variable_byte_sizes, size
  * [prologue_lookup, epilogue_lookup + 64) of hsw_hash_result -- cell for cell what a single-digest gadget writes
  * from cell 0 -- and its chip rows are rows [first_block * limb_calls_per_block / ncols, ...) of the chip columns
  * (needs n_blocks * limb_calls_per_block to be a multiple of num_advice_columns: HSW_ERR_UNSUPPORTED otherwise).
- * Linear streams only: hsw_gadget_set_columns / hsw_gadget_set_origin return HSW_ERR_UNSUPPORTED. */
+ * Linear streams only unless HSW_GADGET_CONTEXT_IMAGES: without it hsw_gadget_set_columns / hsw_gadget_set_origin
+ * return HSW_ERR_UNSUPPORTED. */
 #define HSW_GADGET_INDEPENDENT  2u
+/* With HSW_GADGET_WHOLE_DIGEST | HSW_GADGET_INDEPENDENT (else HSW_ERR_INVALID_ARG), and every max_variable_byte_size
+ * equal (K proofs of one circuit; else HSW_ERR_UNSUPPORTED): every Context is a column image of its own, all starting
+ * at the same Context origin, still written by one launch.  hsw_gadget_set_columns / hsw_gadget_set_origin are
+ * accepted and apply to every Context alike (a failing call leaves the previous layout and buffers as they were).
+ * Layout of Context (proof) h, S = columns x max_rows, Lp = lookups_already_queued + the digest's own lookup entries:
+ *   gate cells     cells [h*S, (h+1)*S) of d_gate; image column k = FlexGate column origin_column + k of proof h; rows
+ *                  [0, origin_row) of its column 0 are the caller's: never written, never touched by a delivery
+ *   lookup column  cells [h*Lp, (h+1)*Lp) of d_lookup; its first lookups_already_queued cells are the caller's
+ *   chip rows      as without the flag: rows [first_block * limb_calls_per_block / ncols, ...) of the chip columns
+ *   zero cell      zero_cell_loaded holds for every Context: each stream is then one cell shorter
+ * hsw_hash_result gate cells stay gadget-stream indices (the K streams back to back, stream_cells of
+ * hsw_context_region each); its lookup indices are d_lookup cells.  hsw_gadget_cell_position /
+ * hsw_gadget_result_cells map a stream cell to (FlexGate column, row) inside the owning Context's image.
+ * Without hsw_gadget_set_columns the gate cells stay the linear stream (lookups and origin as above).
+ * Deliveries: hsw_gadget_download_region writes the K images back to back (host layout = device layout; used rows
+ * only); the region tape, distinct delivery and hsw_gadget_replay_region keep their meaning; hsw_gadget_verify and
+ * hsw_gadget_place work.  hsw_gadget_download_region_compact and hsw_gadget_seek return HSW_ERR_UNSUPPORTED. */
+#define HSW_GADGET_CONTEXT_IMAGES 4u
 int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, size_t n_hashes,
                          int is_input_range_check, uint32_t flags, hsw_gadget **out);
 void hsw_gadget_destroy(hsw_gadget *g);
@@ -680,6 +699,25 @@ int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx);
 int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report);
 /* (column, row) of gate-stream cell `cell` (identity on row without set_columns). */
 int hsw_gadget_cell_position(const hsw_gadget *g, uint64_t cell, uint64_t *column, uint64_t *row);
+/* HSW_GADGET_CONTEXT_IMAGES: where proof h lives on the device -- what a prover batching K proofs hands to its h-th
+ * proof.  32-byte cells in the gadget's representation.  HSW_ERR_INVALID_ARG without the flag or for h >= K. */
+typedef struct hsw_context_region {
+    void *d_image;                      /* columns x max_rows cells, column k = FlexGate column origin_column + k
+                                           (without hsw_gadget_set_columns: the proof's linear stream) */
+    void *d_lookup;                     /* lookup_cells cells; [0, origin_lookups) are the caller's */
+    void *d_chip_dense, *d_chip_spread; /* the proof's chip row 0 of chip column 0; column c is c * chip_col_stride further */
+    uint64_t columns, max_rows;
+    uint64_t last_column_rows;          /* rows of image column columns - 1 the proof uses */
+    uint64_t stream_cells;              /* gate-stream cells of one proof */
+    uint64_t first_stream_cell;         /* h * stream_cells: the proof's first gadget-stream cell (hsw_hash_result) */
+    uint64_t lookup_cells;              /* Lp */
+    uint64_t chip_rows;                 /* chip rows of one proof */
+    uint64_t chip_col_stride;
+    uint64_t origin_column, origin_row, origin_lookups;
+    uint32_t assigned;                  /* 1 once proof h has been digested in this synthesis pass */
+    uint32_t reserved_;
+} hsw_context_region;
+int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region *out);
 /* Sha256DynamicConfig::digest (lib.rs:71-349); precomputed_input_len 0 = None.
  * Synchronous: returns once the streams of this hash are in HBM. */
 int hsw_gadget_digest(hsw_gadget *g, const uint8_t *input, size_t input_len,

@@ -29,6 +29,7 @@ pub const HSW_MAX_BREAKS: usize = 16;
 pub const HSW_CELL_BYTES: usize = 32;
 pub const HSW_GADGET_WHOLE_DIGEST: u32 = 1;
 pub const HSW_GADGET_INDEPENDENT: u32 = 2;
+pub const HSW_GADGET_CONTEXT_IMAGES: u32 = 4;
 
 #[repr(C)]
 #[derive(Default, Clone, Copy, Debug)]
@@ -319,6 +320,28 @@ pub struct hsw_gadget_view {
     pub reserved_: u32,
 }
 
+/// hsw_context_region: proof h of an HSW_GADGET_CONTEXT_IMAGES gadget on the device (include/hsw.h).
+#[repr(C)]
+pub struct hsw_context_region {
+    pub d_image: *mut c_void,
+    pub d_lookup: *mut c_void,
+    pub d_chip_dense: *mut c_void,
+    pub d_chip_spread: *mut c_void,
+    pub columns: u64,
+    pub max_rows: u64,
+    pub last_column_rows: u64,
+    pub stream_cells: u64,
+    pub first_stream_cell: u64,
+    pub lookup_cells: u64,
+    pub chip_rows: u64,
+    pub chip_col_stride: u64,
+    pub origin_column: u64,
+    pub origin_row: u64,
+    pub origin_lookups: u64,
+    pub assigned: u32,
+    pub reserved_: u32,
+}
+
 extern "C" {
     pub fn hsw_abi_version() -> u32;
     pub fn hsw_strerror(status: c_int) -> *const c_char;
@@ -403,6 +426,7 @@ extern "C" {
                                lookup_src: *mut i64, chip: *mut i64, next_state: *mut i64) -> c_int;
     pub fn hsw_gadget_download_region(g: *mut hsw_gadget, dst: *const hsw_region_host) -> c_int;
     pub fn hsw_gadget_cell_position(g: *const hsw_gadget, cell: u64, column: *mut u64, row: *mut u64) -> c_int;
+    pub fn hsw_gadget_context_region(g: *const hsw_gadget, h: usize, out: *mut hsw_context_region) -> c_int;
     pub fn hsw_frame_query(shape: *const hsw_shape, max_variable_byte_size: usize, is_input_range_check: c_int,
                            out: *mut hsw_frame_shape) -> c_int;
     pub fn hsw_frame_tape(shape: *const hsw_shape, max_variable_byte_size: usize, is_input_range_check: c_int,

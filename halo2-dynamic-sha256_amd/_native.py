@@ -34,6 +34,8 @@ HSW_CELL_BYTES = 32
 HSW_GADGET_WHOLE_DIGEST = 1
 HSW_GADGET_INDEPENDENT = 2
 HSW_GADGET_CONTEXT_IMAGES = 4
+HSW_GADGET_SHARED_CONTEXT = 8
+HSW_GADGET_MAX_COLUMNS = 1024
 NO_CELL = (1 << 64) - 1
 
 
@@ -197,7 +199,7 @@ SYMBOLS = (
     "hsw_verify_frames", "hsw_gadget_verify", "hsw_last_launch", "hsw_witness_digests",
     "hsw_gadget_download_region_compact", "hsw_region_widen", "hsw_gadget_result_cells",
     "hsw_gadget_set_origin", "hsw_gadget_region_tape", "hsw_gadget_download_region_distinct", "hsw_gadget_replay_region",
-    "hsw_gadget_context_region",
+    "hsw_gadget_context_region", "hsw_gadget_set_digest_origin",
 )
 
 
@@ -345,6 +347,8 @@ def lib():
         L.hsw_gadget_reset.argtypes = [vp]
         L.hsw_gadget_cell_position.restype = C.c_int
         L.hsw_gadget_cell_position.argtypes = [vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.hsw_gadget_set_digest_origin.restype = C.c_int
+        L.hsw_gadget_set_digest_origin.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64]
         L.hsw_gadget_context_region.restype = C.c_int
         L.hsw_gadget_context_region.argtypes = [vp, C.c_size_t, C.POINTER(ContextRegion)]
         L.hsw_gadget_create_ex.restype = C.c_int

@@ -426,6 +426,9 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
     if (period && period->image_cells &&      // context images: one Context per frame_every blocks, each of image_cells cells
         (!args->frame_every || n_blocks % args->frame_every != 0))
         return set_err(e, HSW_ERR_INVALID_ARG, "context images: whole Contexts of frame_every blocks each");
+    const hsw::PlaceTable *table = period ? period->place : nullptr;   // shared context: the table-path kernels
+    if (table && (!args->frame_every || e->limbs != 2 || (flags & HSW_REPR_COMPACT64) || args->pack))
+        return set_err(e, HSW_ERR_UNSUPPORTED, "placement table: whole-digest launches, 8-bit table, 32-byte cells, no pack plan");
     if ((frames || host_next_states) && !hsw_small_eligible(e, n_blocks))
         return set_err(e, HSW_ERR_INVALID_ARG, "frames / host next states ride on small-batch launches only");
     DeviceScope ds(e->device);
@@ -481,7 +484,7 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
         //  drops to 4 waves per CU and loses to the write-out conversion, 2.35 vs 1.96 ms)
         // (and only for launches that fill the chip with one wave per block: below ~1,500 blocks the write-out
         //  conversion, which spreads a block over up to 16 waves, is faster -- 160 blocks 0.15 against 0.30 ms)
-        const bool m32 = !small && e->limbs == 2 && (flags & HSW_REPR_MONTGOMERY) && !(p.flags & hsw::HSW_K_SPLIT) &&
+        const bool m32 = !small && !table && e->limbs == 2 && (flags & HSW_REPR_MONTGOMERY) && !(p.flags & hsw::HSW_K_SPLIT) &&
                          (e->mont_emit == 2 || (e->mont_emit == 1 && e->mode != HSW_MODE_HALO2_INTERNALS && n >= 1536));
         if (m32) {
             const int rc = ensure_mont_tab(e);
@@ -521,7 +524,8 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
             if (n <= 16) p.flags |= hsw::HSW_K_ROLE_MAJOR;
             else p.flags &= ~(uint32_t)hsw::HSW_K_ROLE_MAJOR;
             p.next_states_host = host_next_states ? host_next_states + 8 * done : nullptr;
-            he = hsw::launch_small(p, done == 0 ? frames : nullptr, e->limbs, e->stream);
+            he = table ? hsw::launch_small_table(p, done == 0 ? frames : nullptr, *table, e->stream)
+                       : hsw::launch_small(p, done == 0 ? frames : nullptr, e->limbs, e->stream);
             if (he != hipSuccess) return set_err(e, HSW_ERR_HIP, "launch hsw_small_kernel", he);
             hsw_launch_info &li = e->last_launch;
             li.limbs = 2; li.tile_cells = 128; li.tile_rows = 16;
@@ -531,7 +535,7 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
             li.grid = (uint64_t)n * hsw::HSW_SMALL_WAVES_PER_BLOCK + ((done == 0 && frames) ? (uint64_t)frames->n_frames * (frames->state_waves + frames->byte_waves) : 0);
             continue;
         }
-        he = hsw::launch_expand(p, e->limbs, tile, e->stream);
+        he = table ? hsw::launch_expand_table(p, *table, tile, e->stream) : hsw::launch_expand(p, e->limbs, tile, e->stream);
         if (he != hipSuccess) return set_err(e, HSW_ERR_HIP, "launch hsw_expand_kernel", he);
         {
             hsw_launch_info &li = e->last_launch;

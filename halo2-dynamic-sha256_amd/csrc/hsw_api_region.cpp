@@ -194,7 +194,9 @@ int hsw_verify_blocks_impl(hsw_engine *e, const hsw_witness_args *args, hsw_veri
     const hsw::VerifyReport zero{0, ~0ull, 0};
     hipError_t he = hipMemcpyAsync(e->d_report, &zero, sizeof zero, hipMemcpyHostToDevice, e->stream);
     if (he == hipSuccess) he = hipEventRecord(e->ev0, e->stream);
-    if (he == hipSuccess) he = hsw::launch_verify(p, args->n_blocks, e->stream);
+    if (he == hipSuccess)
+        he = period && period->place ? hsw::launch_verify_table(p, *period->place, args->n_blocks, e->stream)
+                                     : hsw::launch_verify(p, args->n_blocks, e->stream);
     if (he == hipSuccess) he = hipEventRecord(e->ev1, e->stream);
     hsw::VerifyReport got{};
     if (he == hipSuccess) he = hipMemcpyAsync(&got, e->d_report, sizeof got, hipMemcpyDeviceToHost, e->stream);
@@ -315,7 +317,9 @@ int hsw_verify_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n,
     he = hipMemcpyAsync(dbuf, h.data(), h.size(), hipMemcpyHostToDevice, e->stream);
     if (he == hipSuccess) he = hipMemcpyAsync(e->d_report, &zero, sizeof zero, hipMemcpyHostToDevice, e->stream);
     if (he == hipSuccess) he = hipEventRecord(e->ev0, e->stream);
-    if (he == hipSuccess) he = hsw::launch_verify_frames(p, n, e->stream);
+    if (he == hipSuccess)
+        he = period && period->place ? hsw::launch_verify_frames_table(p, *period->place, n, e->stream)
+                                     : hsw::launch_verify_frames(p, n, e->stream);
     if (he == hipSuccess) he = hipEventRecord(e->ev1, e->stream);
     hsw::VerifyReport got{};
     if (he == hipSuccess) he = hipMemcpyAsync(&got, e->d_report, sizeof got, hipMemcpyDeviceToHost, e->stream);
@@ -505,10 +509,13 @@ int hsw_witness_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n
     rc = stage_frame_descs(e, descs, n, &d_descs, &max_blocks, &slot);
     if (rc != HSW_OK) return rc;
     const bool mont = (flags & HSW_REPR_MONTGOMERY) != 0;
-    hipError_t he = hsw::launch_frames(d_descs, n, d_blocks, d_pre_states, d_next_states, e->d_inv_tbl[mont ? 1 : 0],
-                            d_gate, d_lookup, brk,
-                            /* workgroups per digest: one per 4 blocks (256 input bytes each), at most 64 */
-                            (unsigned)(max_blocks / 4 < 1 ? 1 : (max_blocks / 4 > 64 ? 64 : max_blocks / 4)), mont, e->stream);
+    /* workgroups per digest: one per 4 blocks (256 input bytes each), at most 64 */
+    const unsigned slices = (unsigned)(max_blocks / 4 < 1 ? 1 : (max_blocks / 4 > 64 ? 64 : max_blocks / 4));
+    hipError_t he = period && period->place
+        ? hsw::launch_frames_table(d_descs, n, d_blocks, d_pre_states, d_next_states, e->d_inv_tbl[mont ? 1 : 0],
+                                   d_gate, d_lookup, *period->place, slices, mont, e->stream)
+        : hsw::launch_frames(d_descs, n, d_blocks, d_pre_states, d_next_states, e->d_inv_tbl[mont ? 1 : 0],
+                             d_gate, d_lookup, brk, slices, mont, e->stream);
     if (he != hipSuccess) return set_err(e, HSW_ERR_HIP, "launch hsw_frame_kernel", he);
     he = hipEventRecord(slot->done, e->stream);
     if (he != hipSuccess) return set_err(e, HSW_ERR_HIP, "hipEventRecord", he);

@@ -72,6 +72,32 @@ static __device__ __constant__ u32 IV256[8] = {0x6a09e667, 0xbb67ae85, 0x3c6ef37
 
 #define DEV __device__ __forceinline__
 
+// ---- placement table (shared contexts, hsw_kernels.h PlaceTable) ----
+// Wave-uniform reads through the constant address space: scalar loads, which only read.
+DEV u64 tbl_uniform(const uint64_t *t, u64 i) {
+    return ((const __attribute__((address_space(4))) uint64_t *)t)[i];
+}
+// The number of jumps at or before stream cell `at`, for a wave-uniform `at` (binary search, scalar loads).
+DEV u64 tbl_count_uniform(const PlaceTable &t, u64 at) {
+    // (at comes from the workgroup's block: uniform; readfirstlane keeps the search scalar where the compiler cannot see it)
+    at = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(at >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)at);
+    u64 lo = 0, hi = t.n;
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (tbl_uniform(t.cell, mid) <= at) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// The same for a per-lane `at` (frame cells, verify): vector loads.
+DEV u64 tbl_count(const PlaceTable &t, u64 at) {
+    u64 lo = 0, hi = t.n;
+    while (lo < hi) {
+        const u64 mid = (lo + hi) >> 1;
+        if (t.cell[mid] <= at) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // Tuning aid (tools/latency_probe): with -DHSW_STAMPS every wave records the 100 MHz wall clock at its
 // phase boundaries.  Never defined in the product build.
 #ifdef HSW_STAMPS
@@ -1327,12 +1353,30 @@ DEV bool phase_window(bool split, int phase, u32 part, u32 parts, u32 &wpart, u3
     return in;
 }
 
+// Shared context: gap0 = the gaps of the jumps at or before the block's first stream cell `at`, and the (<= 2)
+// column breaks inside its G cells (an interlude jump falls on a digest's prologue, never inside a block).
+template <class EM>
+DEV void table_block_jumps(EM &em, const PlaceTable &t, u64 at, u64 G, u64 &gap0) {
+    const u64 k = tbl_count_uniform(t, at);
+    u64 prev = k ? tbl_uniform(t.cum, k - 1) : 0;
+    gap0 = prev;
+    for (u64 j = k; j < k + 2 && j < t.n; j++) {
+        const u64 bc = tbl_uniform(t.cell, j);
+        if (bc >= at + G) break;
+        const u64 cum = tbl_uniform(t.cum, j);
+        if (em.brk1 == 0xffffffffu) { em.brk1 = (u32)(bc - at); em.gap1 = (u32)(cum - prev); }
+        else { em.brk2 = (u32)(bc - at); em.gap2 = (u32)(cum - prev); }
+        prev = cum;
+    }
+}
+
 // --------------------------------------------------------------- the kernel
 // T = tile width in cells (contiguous run per row = 32*T bytes), R = tile rows =
 // units one wave expands per phase; a block needs parts >= 64/R waves.
 // One wave's program for its block (or its share of one).
-template <int L, int T, int R, int REPR, bool RC, bool EMITS>
-DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d16, u16 *s_lk16) {
+template <int L, int T, int R, int REPR, bool RC, bool EMITS, bool TABLE = false>
+DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d16, u16 *s_lk16,
+                      const PlaceTable *tbl = nullptr) {
     using LY = Lay<L, RC>;
     using EM = Em<T, R, REPR, RC, false, EMITS>;
     static_assert(R * EM::STRIDE_W * 8 >= 800, "tile must be able to hold the chain seeds");
@@ -1434,6 +1478,9 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
         u64 gap0 = 0;
         em.brk1 = em.brk2 = 0xffffffffu;
         em.gap1 = em.gap2 = 0;
+        if constexpr (TABLE) {     // shared context: search the jump table, then the (<= 2) jumps inside the block
+            table_block_jumps(em, *tbl, tbl->base + first, (u64)LY::GATE_CELLS, gap0);
+        } else {
         for (u32 k = 0; k < p.n_breaks; k++) {
             const u64 bc = p.break_cell[k];
             if (bc <= first) gap0 += p.break_gap[k];
@@ -1441,6 +1488,7 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
                 if (em.brk1 == 0xffffffffu) { em.brk1 = (u32)(bc - first); em.gap1 = (u32)p.break_gap[k]; }
                 else { em.brk2 = (u32)(bc - first); em.gap2 = (u32)p.break_gap[k]; }
             }
+        }
         }
         if constexpr (REPR == 2)   // compact: 8-byte cells
             em.out = reinterpret_cast<uint4 *>(reinterpret_cast<u64 *>(p.gate) + (size_t)(ctx_base + first + gap0));
@@ -1450,6 +1498,8 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
     size_t lk_blk = (size_t)blk * (size_t)LY::LOOKUP_CELLS;
     if constexpr (RC)
         if (p.frame_every) lk_blk += (size_t)(blk / p.frame_every) * (size_t)p.frame_lookups;
+    if constexpr (TABLE)           // shared context: the caller's lookup entries queued before this block's digest
+        lk_blk += (size_t)(tbl_uniform(tbl->lk_shift, (u64)(blk / p.frame_every)) - tbl_uniform(tbl->lk_shift, 0));
     em.write_gate = (p.flags & HSW_K_SKIP_GATE) == 0u;
     const u64 blk_limb0 = p.cursor0 + (u64)blk * (u64)LY::LIMB_CALLS;   // first limb call of this block
 
@@ -1537,7 +1587,32 @@ __global__ __launch_bounds__(64) void hsw_expand_kernel(ExpandParams p) {
     expand_block<L, T, R, REPR, RC, true>(p, s_tile, s_head, s_d16, s_lk16);
 }
 
+// Shared contexts (HSW_GADGET_SHARED_CONTEXT): whole-digest streams placed by a jump table (hsw_kernels.h PlaceTable).
+template <int L, int T, int R, int REPR>
+__global__ __launch_bounds__(64) void hsw_expand_table_kernel(ExpandParams p, PlaceTable t) {
+    using LY = Lay<L, true>;
+    using EM = Em<T, R, REPR, true>;
+    __shared__ __attribute__((aligned(16))) u64 s_tile[(R + (R < 64 ? 1 : 0)) * EM::STRIDE_W];
+    __shared__ __attribute__((aligned(16))) u64 s_head[EM::REALIGN ? R * EM::HEAD_W : 2];
+    __shared__ u16 s_d16[R * LY::CALLS_ROUND];
+    __shared__ u16 s_lk16[R * LY::LK_ROUND];
+    expand_block<L, T, R, REPR, true, true, true>(p, s_tile, s_head, s_d16, s_lk16, &t);
+}
+
 // ------------------------------------------------------------------ launch
+template <int L, int T, int R>
+static hipError_t launch_expand_table_LTR(const ExpandParams &p, const PlaceTable &t, hipStream_t stream) {
+    if ((p.flags & HSW_K_SPLIT) ? (p.parts != 32u || R < 8) : (p.parts * (unsigned)R < 64u))
+        return hipErrorInvalidValue;
+    if ((p.flags & (HSW_K_COMPACT | HSW_K_M32)) || !(p.flags & HSW_K_INTERNALS) || !p.frame_every) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(p.n_blocks * p.parts)), block(64);
+    if (p.flags & HSW_K_MONTGOMERY)
+        hipLaunchKernelGGL((hsw_expand_table_kernel<L, T, R, 1>), grid, block, 0, stream, p, t);
+    else
+        hipLaunchKernelGGL((hsw_expand_table_kernel<L, T, R, 0>), grid, block, 0, stream, p, t);
+    return hipGetLastError();
+}
+
 template <int L, int T, int R, bool RC>
 static hipError_t launch_expand_LTR(const ExpandParams &p, hipStream_t stream) {
     if ((p.flags & HSW_K_SPLIT) ? (p.parts != 32u || R < 8) : (p.parts * (unsigned)R < 64u))

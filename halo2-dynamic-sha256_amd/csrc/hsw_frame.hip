@@ -27,6 +27,39 @@ __global__ __launch_bounds__(256) void hsw_frame_kernel(const FrameDesc *descs, 
                                 });
 }
 
+// Shared contexts (HSW_GADGET_SHARED_CONTEXT): the frame cells placed by a jump table (hsw_kernels.h PlaceTable).
+template <bool MONT>
+__global__ __launch_bounds__(256) void hsw_frame_table_kernel(const FrameDesc *descs, const uint8_t *blocks,
+                                                              const u32 *pre_states, const u32 *next_states,
+                                                              const u64 *inv_tbl, uint4 *gate, uint4 *lookup,
+                                                              u32 slices, PlaceTable t) {
+    const FrameBreaks brk{};   // (no break table, no context images: the placement is the table's)
+    const u32 slice = blockIdx.x % slices;
+    const FrameDesc d = descs[blockIdx.x / slices];
+    framedev::frame_cells<MONT, true>(d, blocks, inv_tbl, gate, lookup, brk, framedev::FRAME_ALL, slice * blockDim.x + threadIdx.x,
+                                      slices * blockDim.x, [&](u32 n, u32 i) -> u32 {
+                                          return n == 0 ? pre_states[8 * d.first_block + i]
+                                                        : next_states[8 * (d.first_block + n - 1) + i];
+                                      }, &t);
+}
+
+hipError_t launch_frames_table(const FrameDesc *d_descs, size_t n, const uint8_t *blocks, const uint32_t *pre_states,
+                               const uint32_t *next_states, const uint64_t *d_inv_tbl, void *gate, void *lookup,
+                               const PlaceTable &t, unsigned slices, bool montgomery, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    if (slices == 0) slices = 1;
+    const dim3 grid((unsigned)(n * slices)), block(256);
+    if (montgomery)
+        hipLaunchKernelGGL(hsw_frame_table_kernel<true>, grid, block, 0, stream, d_descs, blocks, pre_states, next_states,
+                           reinterpret_cast<const u64 *>(d_inv_tbl), reinterpret_cast<uint4 *>(gate),
+                           reinterpret_cast<uint4 *>(lookup), slices, t);
+    else
+        hipLaunchKernelGGL(hsw_frame_table_kernel<false>, grid, block, 0, stream, d_descs, blocks, pre_states, next_states,
+                           reinterpret_cast<const u64 *>(d_inv_tbl), reinterpret_cast<uint4 *>(gate),
+                           reinterpret_cast<uint4 *>(lookup), slices, t);
+    return hipGetLastError();
+}
+
 hipError_t launch_frames(const FrameDesc *d_descs, size_t n, const uint8_t *blocks, const uint32_t *pre_states,
                          const uint32_t *next_states, const uint64_t *d_inv_tbl, void *gate, void *lookup,
                          const FrameBreaks &brk, unsigned slices, bool montgomery, hipStream_t stream) {

@@ -52,11 +52,12 @@ DEV void put(uint4 *gate, u64 cell, const Fe8 &v) {
     gate[2 * cell + 1] = b;
 }
 
-template <bool MONT>
+template <bool MONT, bool TABLE = false>
 struct Out {
     uint4 *gate;
     uint4 *lookup;      // may be null
     const FrameBreaks *brk;
+    const PlaceTable *tbl = nullptr;   // TABLE (shared contexts): the jump table instead of brk's breaks
     // FlexGate column packing (A3-iii): stream cell `at` sits at `at` + the gaps of all breaks at or before it.
     // The walk over the break table (scalar loads, one round trip each) is remembered as the column segment
     // [seg_lo, seg_hi) it found: a thread's cells nearly always share one.
@@ -66,6 +67,13 @@ struct Out {
         at -= at0;
         if (at >= seg_lo && at < seg_hi) return at + seg_gap;
         u64 gap = 0, lo = 0, hi = ~0ull;
+        if constexpr (TABLE) {         // the segment between the last jump at or before `at` and the next one
+            const u64 k = tbl_count(*tbl, at);
+            if (k) { gap = tbl->cum[k - 1]; lo = tbl->cell[k - 1]; }
+            if (k < tbl->n) hi = tbl->cell[k];
+            seg_lo = lo; seg_hi = hi; seg_gap = gap;
+            return at + gap;
+        }
         for (u32 k = 0; k < brk->n; k++) {
             const u64 c = brk->cell[k];
             if (c <= at) { gap += brk->gap[k]; lo = c; }
@@ -99,11 +107,12 @@ struct Out {
 // nothing but the bytes), FRAME_STATES everything that looks at a state word (the fixed prologue cells, the
 // state selection, the digest bytes); gtid / nthreads count the threads of the SAME group.
 enum : u32 { FRAME_BYTES = 1u, FRAME_STATES = 2u, FRAME_ALL = 3u };
-template <bool MONT, class StateWord>
+template <bool MONT, bool TABLE = false, class StateWord>
 DEV void frame_cells(const FrameDesc &d, const uint8_t *blocks, const u64 *inv_tbl, uint4 *gate, uint4 *lookup,
-                     const FrameBreaks &brk, u32 parts, u32 gtid, u32 nthreads, StateWord state_word) {
+                     const FrameBreaks &brk, u32 parts, u32 gtid, u32 nthreads, StateWord state_word,
+                     const PlaceTable *tbl = nullptr) {
     using namespace frame;
-    Out<MONT> o{gate, lookup, &brk};            // (its segment cache is per thread)
+    Out<MONT, TABLE> o{gate, lookup, &brk, tbl};   // (its segment cache is per thread)
     if (brk.ctx_stream) {                       // context images: this digest's Context and its own image (wave-uniform)
         const u64 ctx = d.prologue_cell / brk.ctx_stream;
         o.gate = gate + 2u * (size_t)(ctx * brk.ctx_image);

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <vector>
@@ -224,7 +225,7 @@ std::vector<std::pair<uint64_t, uint64_t>> Sha256DynamicConfig::load() const {
 Context::~Context() {
     (void)hipFree(d_gate); (void)hipFree(d_chip_dense); (void)hipFree(d_chip_spread);
     (void)hipFree(d_next_states); (void)hipFree(d_blocks); (void)hipFree(d_pre_states);
-    (void)hipFree(d_init_states); (void)hipFree(d_offsets); (void)hipFree(d_lookup);
+    (void)hipFree(d_init_states); (void)hipFree(d_offsets); (void)hipFree(d_lookup); (void)hipFree(d_place);
     if (hp_blocks) (void)hipHostFree(hp_blocks);
     free_compact_staging();
 }
@@ -239,7 +240,7 @@ void Context::free_compact_staging() {
 }
 
 int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool whole_digest, bool independent,
-                                     bool context_images) const {
+                                     bool context_images, bool shared) const {
     if (!engine || !out) return HSW_ERR_INVALID_ARG;
     *out = nullptr;
     hsw_shape s;
@@ -267,6 +268,8 @@ int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool who
         c->whole = true;
         c->independent = independent;
         c->context_images = context_images;
+        c->shared = shared;
+        if (shared) c->declared.resize(max_variable_byte_sizes.size());
         // the Context's zero cell: one, or one per digest when every digest is a Context of its own
         uint64_t cells = independent ? max_variable_byte_sizes.size() : 1, lookups = 0;
         for (size_t b : max_variable_byte_sizes) {
@@ -376,6 +379,15 @@ int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint6
     const uint64_t G = shape.gate_cells_per_block;
     if (rows < G + 16) return HSW_ERR_INVALID_ARG;        // keeps a block inside <= 2 columns (kernel: <= 2 breaks per block)
     if (origin_row >= rows) return HSW_ERR_INVALID_ARG;   // the Context's next free row lies inside its column
+    if (shared) {                                         // a new layout: the declarations made for the old one are dropped
+        const uint64_t old_rows = max_rows, old_cols = image_columns;
+        if (rows != max_rows) image_columns = 0;          // (a different column height: a fresh image)
+        max_rows = rows;
+        const int rc = shared_relayout(sizes, rc_inputs, rows, std::vector<DigestOrigin>(declared.size()), 0);
+        if (rc != HSW_OK) { max_rows = old_rows; image_columns = old_cols; return rc; }
+        declared.assign(declared.size(), DigestOrigin{});
+        return HSW_OK;
+    }
     std::vector<uint64_t> bc, bg;
     // context images: ONE Context's walk (every Context is laid out alike), K images of it
     const std::vector<size_t> one(sizes.begin(), sizes.begin() + (sizes.empty() ? 0 : 1));
@@ -397,16 +409,26 @@ int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint6
     free_compact_staging();                               // sized for the old geometry
     max_rows = rows;
     columns = cols;
+    set_breaks(bc, bg);
+    return HSW_OK;
+}
+
+void Context::set_breaks(std::vector<uint64_t> &bc, std::vector<uint64_t> &bg) {
     break_cell.swap(bc);
     break_gap.swap(bg);
-    return HSW_OK;
+    break_cum.resize(break_gap.size());
+    uint64_t sum = 0;
+    for (size_t k = 0; k < break_gap.size(); k++) break_cum[k] = sum += break_gap[k];
+}
+
+uint64_t Context::gap_at(uint64_t cell) const {      // breaks are ascending: a binary search
+    const size_t k = (size_t)(std::upper_bound(break_cell.begin(), break_cell.end(), cell) - break_cell.begin());
+    return k ? break_cum[k - 1] : 0;
 }
 
 void Context::position(uint64_t cell, uint64_t *column, uint64_t *row) const {
     if (context_images && max_rows) cell %= ctx_stream();  // the owning Context's own stream cell
-    uint64_t at = cell + origin_row;
-    for (size_t k = 0; k < break_cell.size(); k++)
-        if (break_cell[k] <= cell) at += break_gap[k];
+    uint64_t at = cell + origin_row + gap_at(cell);
     if (max_rows) { if (column) *column = origin_column + at / max_rows; if (row) *row = at % max_rows; }
     else { if (column) *column = origin_column; if (row) *row = at; }
 }
@@ -418,13 +440,159 @@ uint64_t Context::image_cell(uint64_t cell) const {
         base = h * ctx_image();
         cell -= h * C;
     }
-    uint64_t at = base + cell + (max_rows ? origin_row : 0);
-    for (size_t k = 0; k < break_cell.size(); k++)
-        if (break_cell[k] <= cell) at += break_gap[k];
-    return at;
+    return base + cell + (max_rows ? origin_row : 0) + gap_at(cell);
+}
+
+// Shared context: the pass laid out digest by digest from the origin, with a jump wherever a digest's declared origin
+// lies further on than the next free cell (an interlude; its gap may span columns) and its lookup entries
+// starting at the declared queue length.  bc / bg: every jump; lk0 / e0 per digest; cols: image columns used.
+static int shared_breaks(const hsw_shape &shape, const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows,
+                         uint64_t origin_column, uint64_t row0, bool zero_loaded, uint64_t lookups0,
+                         const std::vector<Context::DigestOrigin> &decl, std::vector<uint64_t> &bc,
+                         std::vector<uint64_t> &bg, std::vector<uint64_t> &lk0, std::vector<uint64_t> &e0,
+                         std::vector<uint64_t> &c0, uint64_t *cols, uint64_t *lookups_end) {
+    const uint64_t G = shape.gate_cells_per_block;
+    size_t n = 0;
+    if (hsw_gate_tape(&shape, nullptr, 0, &n) != HSW_OK) return HSW_ERR_INVALID_ARG;
+    std::vector<uint8_t> block_tape(n);
+    hsw_gate_tape(&shape, block_tape.data(), n, nullptr);
+    bc.clear(); bg.clear(); lk0.clear(); e0.clear(); c0.clear();
+    uint64_t col = 0, row = row0, cell = 0, lk = lookups0, own = 0;
+    auto walk = [&](const std::vector<uint8_t> &lens) {
+        for (uint8_t len : lens) {
+            if (row + len >= rows) {                      // halo2-lib v0.2.x assign_region: next column (A3-iii)
+                bc.push_back(cell); bg.push_back(rows - row);
+                row = 0; col++;
+            }
+            row += len; cell += len;
+        }
+    };
+    bool zero = zero_loaded;
+    for (size_t h = 0; h < sizes.size(); h++) {
+        const size_t b = sizes[h];
+        if (h < decl.size() && decl[h].set) {             // the caller's interlude ends at (column, row)
+            const Context::DigestOrigin &d = decl[h];
+            if (d.column < origin_column || d.row >= rows) return HSW_ERR_INVALID_ARG;
+            const uint64_t want = (d.column - origin_column) * rows + d.row, here = col * rows + row;
+            if (want < here || d.lookups < lk) return HSW_ERR_INVALID_ARG;
+            if (want > here) { bc.push_back(cell); bg.push_back(want - here); }
+            col = d.column - origin_column; row = d.row; lk = d.lookups;
+        }
+        lk0.push_back(lk);
+        c0.push_back(cell);
+        e0.push_back(own);
+        hsw_frame_shape fs;
+        int rc = hsw_frame_query(&shape, b, rc_inputs ? 1 : 0, &fs);
+        if (rc != HSW_OK) return rc;
+        lk += fs.digest_lookups;
+        own += fs.digest_lookups;
+        for (int section = 0; section < 2; section++) {
+            if (section == 1) {
+                if (!zero) { walk({1}); zero = true; }    // Context.zero_cell, first load_zero
+                for (size_t k = 0; k < b / 64; k++) {
+                    if (row + G + 8 < rows) { row += G; cell += G; }
+                    else walk(block_tape);
+                }
+            }
+            size_t m = 0;
+            rc = hsw_frame_tape(&shape, b, rc_inputs ? 1 : 0, section, nullptr, 0, &m);
+            if (rc != HSW_OK) return rc;
+            std::vector<uint8_t> t(m);
+            hsw_frame_tape(&shape, b, rc_inputs ? 1 : 0, section, t.data(), m, nullptr);
+            walk(t);
+        }
+    }
+    *cols = col + 1;
+    *lookups_end = lk;
+    return *cols > HSW_GADGET_MAX_COLUMNS ? HSW_ERR_TOO_LARGE : HSW_OK;
+}
+
+int Context::shared_relayout(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows,
+                             const std::vector<DigestOrigin> &decl, uint64_t clear_from) {
+    std::vector<uint64_t> bc, bg, lk0, e0, c0;
+    uint64_t cols = 0, lk_end = 0;
+    int rc = shared_breaks(shape, sizes, rc_inputs, rows, origin_column, origin_row, origin_zero_loaded, origin_lookups,
+                           decl, bc, bg, lk0, e0, c0, &cols, &lk_end);
+    if (rc != HSW_OK) return rc;
+    const bool changed = !(bc == break_cell && bg == break_gap && lk0 == digest_lookup0 && cols == columns);
+    if (!changed && cols <= image_columns && lk_end <= lookup_capacity) return HSW_OK;   // nothing to do
+    int device = 0;
+    hsw_engine_stream(engine, nullptr, &device);
+    DeviceScope ds(device);
+    if (!ds.ok) return HSW_ERR_NO_DEVICE;
+    // (the callers run on a drained engine: nothing still writes the buffers replaced here)
+    void *img = nullptr, *lk = nullptr;
+    hipError_t he = hipSuccess;
+    if (cols > image_columns) {                           // the image grows: the columns so far are copied over
+        const size_t bytes = (size_t)(cols * rows) * HSW_CELL_BYTES;
+        he = hipMalloc(&img, bytes);
+        if (he == hipSuccess) he = hipMemset(img, 0, bytes);   // unassigned advice cells are 0
+        if (he == hipSuccess && image_columns && d_gate)
+            he = hipMemcpy(img, d_gate, (size_t)(image_columns * rows) * HSW_CELL_BYTES, hipMemcpyDeviceToDevice);
+    }
+    if (he == hipSuccess && lk_end > lookup_capacity) {  // room for the caller's entries of the interludes
+        const size_t bytes = (size_t)lk_end * HSW_CELL_BYTES;
+        he = hipMalloc(&lk, bytes);
+        if (he == hipSuccess) he = hipMemset(lk, 0, bytes);
+        if (he == hipSuccess && d_lookup && lookup_capacity)
+            he = hipMemcpy(lk, d_lookup, (size_t)lookup_capacity * HSW_CELL_BYTES, hipMemcpyDeviceToDevice);
+    }
+    if (he != hipSuccess) {
+        if (img) (void)hipFree(img);
+        if (lk) (void)hipFree(lk);
+        return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP;
+    }
+    if (img) { (void)hipFree(d_gate); d_gate = img; image_columns = cols; }
+    if (lk) { (void)hipFree(d_lookup); d_lookup = lk; lookup_capacity = lk_end; }
+    if (img || lk) free_compact_staging();
+    if (changed && clear_from < image_columns * rows)      // cells an earlier layout wrote past the unchanged part
+        (void)hipMemset(static_cast<uint8_t *>(d_gate) + (size_t)clear_from * HSW_CELL_BYTES, 0,
+                        (size_t)(image_columns * rows - clear_from) * HSW_CELL_BYTES);
+    columns = cols;
+    set_breaks(bc, bg);
+    digest_lookup0.swap(lk0);
+    digest_entry0.swap(e0);
+    digest_cell0.swap(c0);
+    place_dirty = true;
+    return HSW_OK;
+}
+
+int Context::upload_place() {
+    if (!place_dirty && d_place) return HSW_OK;
+    // [jump cells n][cumulative gaps n][per digest: the caller's lookup entries before it, cumulative]
+    const size_t n = break_cell.size(), H = digest_lookup0.size();
+    std::vector<uint64_t> h(2 * n + (H ? H : 1), 0);
+    for (size_t k = 0; k < n; k++) { h[k] = break_cell[k]; h[n + k] = break_cum[k]; }
+    for (size_t d = 0; d < H; d++) h[2 * n + d] = digest_lookup0[d] - origin_lookups - digest_entry0[d];
+    if (d_place && h == place_host) { place_dirty = false; return HSW_OK; }   // the device already holds this table
+    int device = 0;
+    hsw_engine_stream(engine, nullptr, &device);
+    DeviceScope ds(device);
+    if (!ds.ok) return HSW_ERR_NO_DEVICE;
+    hipError_t he = hipSuccess;
+    if (h.size() > place_cap) {
+        void *p = nullptr;
+        he = hipMalloc(&p, h.size() * sizeof(uint64_t));
+        if (he != hipSuccess) return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP;
+        (void)hipFree(d_place);
+        d_place = p;
+        place_cap = h.size();
+    }
+    he = hipMemcpy(d_place, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (he != hipSuccess) return HSW_ERR_HIP;
+    place_host.swap(h);
+    place_dirty = false;
+    return HSW_OK;
+}
+
+uint64_t Context::lookup_cell(uint64_t entry) const {
+    if (!shared || digest_entry0.empty()) return origin_lookups + entry;
+    const size_t h = (size_t)(std::upper_bound(digest_entry0.begin(), digest_entry0.end(), entry) - digest_entry0.begin()) - 1;
+    return digest_lookup0[h] + (entry - digest_entry0[h]);
 }
 
 int Context::set_origin(uint64_t column, uint64_t row, bool zero_cell_loaded, uint64_t lookups_queued) {
+    const bool same_lookups = lookups_queued == origin_lookups;   // (d_lookup is kept)
     if (!whole || blocks_done != 0 || gate_cursor != 0 || lookup_cursor != origin_lookups) return HSW_ERR_INVALID_ARG;
     if (independent) return HSW_ERR_UNSUPPORTED;          // (context images: set_origin_images)
     if (max_rows && row >= max_rows) return HSW_ERR_INVALID_ARG;
@@ -444,7 +612,9 @@ int Context::set_origin(uint64_t column, uint64_t row, bool zero_cell_loaded, ui
         free_compact_staging();
     }
     origin_column = column; origin_row = row; origin_zero_loaded = zero_cell_loaded; origin_lookups = lookups_queued;
-    lookup_capacity = own_lookup_capacity + lookups_queued;
+    // (shared context: a buffer grown for interlude entries keeps its size while it is kept)
+    if (!(shared && same_lookups && lookup_capacity > own_lookup_capacity + lookups_queued))
+        lookup_capacity = own_lookup_capacity + lookups_queued;
     lookup_cursor = lookups_queued;
     zero_loaded = zero_cell_loaded;
     // without the zero cell the stream is one cell shorter
@@ -493,8 +663,7 @@ int Context::set_origin_images(const std::vector<size_t> &sizes, bool rc_inputs,
         (void)hipFree(d_gate);
         d_gate = img;
         columns = cols;
-        break_cell.swap(bc);
-        break_gap.swap(bg);
+        set_breaks(bc, bg);
     }
     if (lk || img) free_compact_staging();
     origin_column = column; origin_row = row; origin_zero_loaded = zero_cell_loaded; origin_lookups = lookups_queued;
@@ -635,6 +804,15 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
             // context images: one Context's period in the gate image and the lookup column (NULL: linear streams)
             const ContextPeriod period{ctx.ctx_stream(), ctx.ctx_image()};
             const ContextPeriod *per = ctx.context_images && ctx.max_rows ? &period : nullptr;
+            // shared context: every launch placed by the jump table (uploaded when the layout changed)
+            const bool table = ctx.shared && ctx.max_rows;
+            if (table && (rc = ctx.upload_place()) != HSW_OK) break;
+            const uint64_t *d_place = static_cast<const uint64_t *>(ctx.d_place);
+            const size_t n_jumps = ctx.break_cell.size();
+            PlaceTable tbl{};
+            if (table) tbl = PlaceTable{d_place, d_place + n_jumps, d_place + 2 * n_jumps, n_jumps, 0};
+            const ContextPeriod tper{0, 0, &tbl};
+            if (table) per = &tper;
             frames.resize(n);
             std::vector<hsw_frame_shape> fss(n);
             size_t ob = 0;
@@ -651,6 +829,7 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 d.is_input_range_check = is_input_range_check ? 1u : 0u;
                 // context images: Context h's lookup column is cells [h*Lp, (h+1)*Lp), the caller's queued cells first
                 if (ctx.context_images) lc = (uint64_t)(cur_hash_idx + i) * ctx.ctx_lookups() + ctx.origin_lookups;
+                if (table) lc = ctx.digest_lookup0[cur_hash_idx + i];   // after the caller's entries of the interlude
                 r.prologue_cell = d.prologue_cell = gc;      gc += fss[i].prologue_cells;
                 r.prologue_lookup = d.prologue_lookup = lc;  lc += fss[i].prologue_lookups;
                 d.zero_cell = ~0ull;
@@ -676,8 +855,8 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 a.n_blocks = run_blocks;
                 a.spread_cursor0 = cursor;
                 // (context images: the run's first block in ITS Context's image; the breaks below are that Context's)
-                const uint64_t per_C = per ? per->stream_cells : 0, per_S = per ? per->image_cells : 0;
-                const uint64_t ctx0 = per ? results[i].block_cell / per_C : 0;
+                const uint64_t per_C = per && !table ? per->stream_cells : 0, per_S = per && !table ? per->image_cells : 0;
+                const uint64_t ctx0 = per && !table ? results[i].block_cell / per_C : 0;
                 const uint64_t local_block_cell = results[i].block_cell - ctx0 * per_C;
                 a.d_gate = static_cast<uint8_t *>(ctx.gate_stream()) + (size_t)(ctx0 * per_S + local_block_cell) * cb;
                 a.d_chip_dense = static_cast<uint8_t *>(ctx.d_chip_dense) + (size_t)row_shift * cb;
@@ -693,7 +872,9 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 // (context images: and the next Context's caller-owned lookup cells)
                 a.frame_lookups = fss[i].epilogue_lookups + fss[i].prologue_lookups + (ctx.context_images ? ctx.origin_lookups : 0u);
                 hsw_pack_plan plan{};
-                if (ctx.max_rows) {
+                tbl.base = local_block_cell;                 // (table: the run's first block cell, its lookup shifts)
+                if (table) tbl.lk_shift = d_place + 2 * n_jumps + (cur_hash_idx + i);
+                if (ctx.max_rows && !table) {
                     // column breaks relative to this launch's first cell; breaks before it are pure offsets
                     const uint64_t base = local_block_cell;
                     plan.n_breaks = (uint32_t)ctx.break_cell.size();
@@ -710,12 +891,12 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                     da.d_blocks0 = in_blocks; da.d_pre_states0 = in_pre; da.d_next_states0 = ctx.d_next_states;
                     da.d_gate0 = ctx.gate_stream(); da.d_lookup0 = ctx.d_lookup;
                     hsw_pack_plan abs_plan{};
-                    abs_plan.n_breaks = (uint32_t)ctx.break_cell.size();
-                    for (size_t k = 0; k < ctx.break_cell.size(); k++) {
+                    abs_plan.n_breaks = table ? 0u : (uint32_t)ctx.break_cell.size();
+                    for (size_t k = 0; k < abs_plan.n_breaks; k++) {
                         abs_plan.break_cell[k] = ctx.break_cell[k];
                         abs_plan.break_gap[k] = ctx.break_gap[k];
                     }
-                    da.frame_pack = ctx.max_rows ? &abs_plan : nullptr;
+                    da.frame_pack = ctx.max_rows && !table ? &abs_plan : nullptr;
                     da.host_next_states = h_next + 8 * ob;
                     // (the device alias of the context's own pinned staging: no runtime lookup per call)
                     rc = hsw_witness_digests_impl(ctx.engine, &da, ctx.dp_next + 8 * (b0 + ob), per);
@@ -728,13 +909,13 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
             }
             if (rc == HSW_OK && !small) {
                 hsw_pack_plan plan{};
-                plan.n_breaks = (uint32_t)ctx.break_cell.size();
-                for (size_t k = 0; k < ctx.break_cell.size(); k++) {
+                plan.n_breaks = table ? 0u : (uint32_t)ctx.break_cell.size();
+                for (size_t k = 0; k < plan.n_breaks; k++) {
                     plan.break_cell[k] = ctx.break_cell[k];
                     plan.break_gap[k] = ctx.break_gap[k];
                 }
                 rc = hsw_witness_frames_impl(ctx.engine, frames.data(), n, in_blocks, in_pre, ctx.d_next_states,
-                                             ctx.gate_stream(), ctx.d_lookup, ctx.max_rows ? &plan : nullptr, ctx.repr_flags, per);
+                                             ctx.gate_stream(), ctx.d_lookup, ctx.max_rows && !table ? &plan : nullptr, ctx.repr_flags, per);
             }
             if (rc == HSW_OK) { new_gate_cursor = gc; new_lookup_cursor = lc; }
         }
@@ -813,7 +994,11 @@ int hsw_gadget_create(hsw_engine *e, const size_t *max_variable_byte_sizes, size
 int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, size_t n_hashes,
                          int is_input_range_check, uint32_t flags, hsw_gadget **out) try {
     if (!e || !out || (!max_variable_byte_sizes && n_hashes)) return HSW_ERR_INVALID_ARG;
-    if (flags & ~(HSW_GADGET_WHOLE_DIGEST | HSW_GADGET_INDEPENDENT | HSW_GADGET_CONTEXT_IMAGES)) return HSW_ERR_INVALID_ARG;
+    if (flags & ~(HSW_GADGET_WHOLE_DIGEST | HSW_GADGET_INDEPENDENT | HSW_GADGET_CONTEXT_IMAGES | HSW_GADGET_SHARED_CONTEXT))
+        return HSW_ERR_INVALID_ARG;
+    const bool shared = (flags & HSW_GADGET_SHARED_CONTEXT) != 0;
+    if (shared && (!(flags & HSW_GADGET_WHOLE_DIGEST) || (flags & (HSW_GADGET_INDEPENDENT | HSW_GADGET_CONTEXT_IMAGES))))
+        return HSW_ERR_INVALID_ARG;
     if ((flags & HSW_GADGET_INDEPENDENT) && !(flags & HSW_GADGET_WHOLE_DIGEST)) return HSW_ERR_INVALID_ARG;
     const bool images = (flags & HSW_GADGET_CONTEXT_IMAGES) != 0;
     if (images && !(flags & HSW_GADGET_INDEPENDENT)) return HSW_ERR_INVALID_ARG;
@@ -823,13 +1008,14 @@ int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, s
     hsw_shape s;
     int rc = hsw_engine_shape(e, &s);
     if (rc != HSW_OK) return rc;
+    if (shared && s.num_bits_lookup != 8) return HSW_ERR_UNSUPPORTED;   // the table-path kernels: the 8-bit spread table
     hsw_gadget *g = new (std::nothrow) hsw_gadget();
     if (!g) return HSW_ERR_NOMEM;
     std::vector<size_t> sizes(max_variable_byte_sizes, max_variable_byte_sizes + n_hashes);
     rc = hsw::Sha256DynamicConfig::configure(sizes, s.num_bits_lookup, s.num_advice_columns,
                                              is_input_range_check != 0, &g->cfg);
     if (rc == HSW_OK) rc = g->cfg.new_context(e, &g->ctx, (flags & HSW_GADGET_WHOLE_DIGEST) != 0, (flags & HSW_GADGET_INDEPENDENT) != 0,
-                                              images);
+                                              images, shared);
     if (rc != HSW_OK) { delete g; return rc; }
     *out = g;
     return HSW_OK;
@@ -963,7 +1149,7 @@ int hsw_gadget_set_origin(hsw_gadget *g, uint64_t column, uint64_t row, int zero
     // A prover that synthesizes the same circuit pass after pass keeps its tape.
     if (old[2] != (zero_cell_loaded ? 1u : 0u)) { hsw::free_region_tape(g->tape); g->tape = nullptr; }
     else if (old[1] != row) hsw::drop_region_tape_positions(g->tape);
-    if (c.max_rows && (old[1] != row || old[2] != (zero_cell_loaded ? 1u : 0u))) {
+    if (c.max_rows && (c.shared || old[1] != row || old[2] != (zero_cell_loaded ? 1u : 0u))) {
         // the column breaks follow from where the stream starts: lay the image out again
         rc = c.set_columns(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, c.max_rows);
         if (rc != HSW_OK) {                                      // e.g. one column too many now: keep the old layout
@@ -971,6 +1157,31 @@ int hsw_gadget_set_origin(hsw_gadget *g, uint64_t column, uint64_t row, int zero
             return rc;
         }
     }
+    return HSW_OK;
+} HSW_NO_UNWIND
+
+int hsw_gadget_set_digest_origin(hsw_gadget *g, size_t h, uint64_t column, uint64_t row, uint64_t lookups_queued) try {
+    if (!g) return HSW_ERR_INVALID_ARG;
+    hsw::Context &c = *g->ctx;
+    const size_t n = g->cfg.max_variable_byte_sizes.size();
+    if (!c.shared || !c.max_rows || h < 1 || h >= n || h < g->cfg.cur_hash_idx || row >= c.max_rows)
+        return HSW_ERR_INVALID_ARG;
+    const hsw::Context::DigestOrigin &was = c.declared[h];
+    // the same declaration again (the next pass declaring what the last one did) changes nothing: the later digests'
+    // layout depends on it only, so their declarations stay too
+    if (was.set && was.column == column && was.row == row && was.lookups == lookups_queued) return HSW_OK;
+    // digest h's declaration replaces the old one and drops the later ones (their layout follows from it)
+    std::vector<hsw::Context::DigestOrigin> decl(c.declared.begin(), c.declared.begin() + (ptrdiff_t)h);
+    decl.resize(n);
+    decl[h].set = true; decl[h].column = column; decl[h].row = row; decl[h].lookups = lookups_queued;
+    int rc = hsw_engine_synchronize(c.engine);           // the image may grow: nothing may still write the old one
+    if (rc != HSW_OK) return rc;
+    // (cells past digest h-1's end: the same in both layouts up to there, stale beyond it if the layout changes)
+    const uint64_t clear_from = c.image_cell(c.digest_cell0[h] - 1) + 1;
+    rc = c.shared_relayout(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, c.max_rows, decl, clear_from);
+    if (rc != HSW_OK) return rc;
+    c.declared.swap(decl);
+    hsw::drop_region_tape_positions(g->tape);           // the witnesses' image positions follow the layout
     return HSW_OK;
 } HSW_NO_UNWIND
 
@@ -996,6 +1207,7 @@ int hsw_gadget_reset(hsw_gadget *g) try {
 int hsw_gadget_place(hsw_gadget *g, unsigned candidates, float *ms_each, unsigned *kept) try {
     if (!g || candidates == 0 || candidates > 16) return HSW_ERR_INVALID_ARG;
     hsw::Context &c = *g->ctx;
+    if (c.shared) return HSW_ERR_UNSUPPORTED;                     // (its trial batch would run over the declared interludes)
     if (g->cfg.cur_hash_idx != 0 || c.blocks_done != 0) return HSW_ERR_INVALID_ARG;      // a fresh or reset gadget
     const size_t n = g->cfg.max_variable_byte_sizes.size();
     if (n == 0) return HSW_ERR_INVALID_ARG;
@@ -1090,6 +1302,14 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
                 const uint64_t first = k == 0 ? c.origin_row : 0;    // rows above the origin are the caller's
                 if (used > first) copy(dst->gate, c.d_gate, (size_t)(h * S + k * c.max_rows + first), (size_t)(used - first));
             }
+    } else if (dst->gate && c.shared && c.max_rows) {
+        // shared context: the stream in its runs between jumps -- the interludes' cells are the caller's, never touched
+        uint64_t lo = 0;
+        for (size_t k = 0; k <= c.break_cell.size() && lo < c.gate_cursor; k++) {
+            const uint64_t hi = k < c.break_cell.size() && c.break_cell[k] < c.gate_cursor ? c.break_cell[k] : c.gate_cursor;
+            if (hi > lo) copy(dst->gate, c.d_gate, (size_t)c.image_cell(lo), (size_t)(hi - lo));
+            lo = hi > lo ? hi : lo;
+        }
     } else if (dst->gate) {
         if (c.whole && c.max_rows) {
             // used rows of column k: up to its break (max_rows - gap), the last column up to the cursor
@@ -1110,6 +1330,12 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
         const uint64_t Lp = c.ctx_lookups();               // Context h: its own entries after the caller's queued cells
         for (uint64_t h = 0; h < g->cfg.cur_hash_idx; h++)
             copy(dst->lookup, c.d_lookup, (size_t)(h * Lp + c.origin_lookups), (size_t)c.ctx_own_lookups);
+    } else if (dst->lookup && c.d_lookup && c.shared && !c.digest_lookup0.empty()) {
+        for (size_t h = 0; h < g->cfg.cur_hash_idx; h++) {     // every digest's own entries; the interludes' are the caller's
+            const uint64_t end = h + 1 < c.digest_entry0.size() ? c.digest_entry0[h + 1]
+                                                               : c.own_lookup_capacity;
+            copy(dst->lookup, c.d_lookup, (size_t)c.digest_lookup0[h], (size_t)(end - c.digest_entry0[h]));
+        }
     } else if (dst->lookup && c.d_lookup) {
         copy(dst->lookup, c.d_lookup, (size_t)c.origin_lookups, (size_t)(c.lookup_cursor - c.origin_lookups));
     }
@@ -1128,6 +1354,7 @@ int hsw_gadget_download_region_compact(hsw_gadget *g, hsw_region_compact *dst) t
     hsw::Context &c = *g->ctx;
     if (c.repr_flags != HSW_REPR_CANONICAL) return HSW_ERR_UNSUPPORTED;      // packs canonical 32-byte cells
     if (c.context_images) return HSW_ERR_UNSUPPORTED;                         // one image per Context: not packed here
+    if (c.shared && c.max_rows) return HSW_ERR_UNSUPPORTED;                   // shared context: interludes are the caller's
     if (!dst->wide && dst->wide_cap) return HSW_ERR_INVALID_ARG;
     hipStream_t stream = nullptr;
     int device = 0;
@@ -1213,6 +1440,7 @@ int hsw_region_widen(const uint64_t *compact, size_t n_cells, uint64_t stream_id
 int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx) try {
     if (!g || hash_idx > g->cfg.max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
     if (g->ctx->context_images) return HSW_ERR_UNSUPPORTED;       // K proofs of one circuit: nothing to deal out
+    if (g->ctx->shared) return HSW_ERR_UNSUPPORTED;               // shared context: the layout follows the declared origins
     int rc = hsw_engine_synchronize(g->ctx->engine);
     if (rc != HSW_OK) return rc;
     hsw::Context &c = *g->ctx;
@@ -1246,6 +1474,17 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
     std::memset(report, 0, sizeof *report);
     hsw::Context &c = *g->ctx;
     if (c.repr_flags & HSW_REPR_COMPACT64) return HSW_ERR_UNSUPPORTED;         // 32-byte cells only
+    // shared context: every launch checks through the jump table (the layout of the digests so far is final)
+    const bool table = c.shared && c.max_rows;
+    if (table) {
+        const int rc0 = c.upload_place();
+        if (rc0 != HSW_OK) return rc0;
+    }
+    const uint64_t *d_place = static_cast<const uint64_t *>(c.d_place);
+    const size_t n_jumps = c.break_cell.size();
+    hsw::PlaceTable tbl{};
+    if (table) tbl = hsw::PlaceTable{d_place, d_place + n_jumps, d_place + 2 * n_jumps, n_jumps, 0};
+    const hsw::ContextPeriod tper{0, 0, &tbl};
     const size_t G = c.shape.gate_cells_per_block, cb = HSW_CELL_BYTES;
     const uint32_t ncols = c.shape.num_advice_columns;
     auto merge = [&](const hsw_verify_report &r) {
@@ -1255,12 +1494,13 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
         report->violations += r.violations; report->checks += r.checks; report->kernel_ms += r.kernel_ms;
     };
     hsw_pack_plan abs_plan{};
-    abs_plan.n_breaks = (uint32_t)c.break_cell.size();
-    for (size_t k = 0; k < c.break_cell.size(); k++) { abs_plan.break_cell[k] = c.break_cell[k]; abs_plan.break_gap[k] = c.break_gap[k]; }
+    abs_plan.n_breaks = table ? 0u : (uint32_t)c.break_cell.size();
+    for (size_t k = 0; k < abs_plan.n_breaks; k++) { abs_plan.break_cell[k] = c.break_cell[k]; abs_plan.break_gap[k] = c.break_gap[k]; }
     const bool own_zero = c.independent && !c.origin_zero_loaded;
     const hsw::ContextPeriod period{c.ctx_stream(), c.ctx_image()};
     const hsw::ContextPeriod *per = c.context_images && c.max_rows ? &period : nullptr;
     const uint64_t per_C = per ? period.stream_cells : 0, per_S = per ? period.image_cells : 0;
+    const hsw::ContextPeriod *vper = table ? &tper : per;
     for (const hsw::Context::BatchRecord &b : c.batches) {
         const uint8_t *in_blocks = b.inputs_in_pinned ? c.dp_blocks : c.d_blocks;
         const uint32_t *in_pre = b.inputs_in_pinned ? c.dp_pre : c.d_pre_states;
@@ -1305,7 +1545,10 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
             a.frame_lookups = fs.epilogue_lookups + fs.prologue_lookups + (c.context_images ? c.origin_lookups : 0u);
             a.flags = b.repr_flags;
             hsw_pack_plan rel{};
-            if (c.max_rows) {
+            if (table) {
+                tbl.base = local_block_cell;
+                tbl.lk_shift = d_place + 2 * n_jumps + (b.first_digest + i);
+            } else if (c.max_rows) {
                 rel.n_breaks = abs_plan.n_breaks;
                 for (uint32_t k = 0; k < rel.n_breaks; k++) {
                     rel.break_cell[k] = abs_plan.break_cell[k] > local_block_cell ? abs_plan.break_cell[k] - local_block_cell : 0;
@@ -1314,7 +1557,7 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
                 a.pack = &rel;
             }
             hsw_verify_report r;
-            rc = hsw_verify_blocks_impl(c.engine, &a, &r, per);
+            rc = hsw_verify_blocks_impl(c.engine, &a, &r, vper);
             if (rc != HSW_OK) return rc;
             merge(r);
             std::vector<hsw_frame_desc> descs(j - i);
@@ -1331,7 +1574,7 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
                 blk += rk.n_blocks;
             }
             rc = hsw_verify_frames_impl(c.engine, descs.data(), descs.size(), in_blocks, in_pre, c.d_next_states, c.gate_stream(),
-                                        c.d_lookup, c.max_rows ? &abs_plan : nullptr, b.repr_flags, &r, per);
+                                        c.d_lookup, c.max_rows && !table ? &abs_plan : nullptr, b.repr_flags, &r, vper);
             if (rc != HSW_OK) return rc;
             merge(r);
             ob += run_blocks;

@@ -75,7 +75,7 @@ class Sha256DynamicConfig {
     // lib.rs:351-360: a context sized for every hash this config will assign.
     // whole_digest: also lay out digest()'s own cells (HSW_GADGET_WHOLE_DIGEST)
     int new_context(hsw_engine *engine, Context **out, bool whole_digest = false, bool independent = false,
-                    bool context_images = false) const;
+                    bool context_images = false, bool shared = false) const;
 
     // lib.rs:71-349.  precomputed_input_len = 0 is the reference's None.
     int digest(Context &ctx, const uint8_t *input, size_t input_len, size_t precomputed_input_len,
@@ -142,6 +142,30 @@ class Context {
     // stream cell i sits at i + the gaps of all breaks at or before i (assumption A3-iii)
     uint64_t max_rows = 0, columns = 0;
     std::vector<uint64_t> break_cell, break_gap;
+    std::vector<uint64_t> break_cum;                   // break_cum[k] = break_gap[0..k] summed (the search in position / image_cell)
+    void set_breaks(std::vector<uint64_t> &bc, std::vector<uint64_t> &bg);   // swaps them in, rebuilds break_cum
+    uint64_t gap_at(uint64_t cell) const;              // the gaps of all breaks at or before `cell`
+    // HSW_GADGET_SHARED_CONTEXT: the same Context for every digest of the pass, the caller's own cells in between
+    // (interludes, hsw_gadget_set_digest_origin).  break_cell / break_gap are then every jump of the stream-to-image
+    // map -- column breaks and interludes -- of any number (up to HSW_GADGET_MAX_COLUMNS columns)
+    bool shared = false;
+    struct DigestOrigin { bool set = false; uint64_t column = 0, row = 0, lookups = 0; };
+    std::vector<DigestOrigin> declared;                // per digest of the pass ([0] unused)
+    std::vector<uint64_t> digest_lookup0;              // per digest: d_lookup cell of its first own entry (its layout)
+    std::vector<uint64_t> digest_entry0;               // per digest: its first entry among the gadget's own lookup entries
+    std::vector<uint64_t> digest_cell0;                // per digest: its first gate-stream cell
+    std::vector<uint64_t> place_host;                  // what d_place holds (an unchanged table is not uploaded again)
+    uint64_t image_columns = 0;                        // image columns allocated (>= columns)
+    void *d_place = nullptr;                           // device copy of the jump table (hsw_kernels.h PlaceTable)
+    size_t place_cap = 0;                              // uint64 words of d_place
+    bool place_dirty = true;                           // the layout changed since the last upload
+    // lays the pass out again from the origin and the declarations; commits only on success (image / lookup grown).
+    // If the layout changed, image cells [clear_from, end) -- what an earlier layout may have written there -- are
+    // zeroed again (unassigned advice cells are 0); clear_from = ~0: none
+    int shared_relayout(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows, const std::vector<DigestOrigin> &decl,
+                        uint64_t clear_from);
+    int upload_place();                                // d_place from the layout, if it changed
+    uint64_t lookup_cell(uint64_t entry) const;        // d_lookup cell of the gadget's own lookup entry `entry`
     // Where the caller's halo2-base Context stood when it handed the region to the gadget (hsw_gadget_set_origin;
     // the reference's digest takes whatever Context it is given, lib.rs:71-76,351-360): stream cell 0 lands at
     // (origin_column, origin_row) = ctx.advice_alloc[0]; the Context may already cache its zero cell

@@ -84,8 +84,23 @@ hipError_t launch_gather32(const void *image, const uint32_t *pos, void *dst, si
 
 // The period of a context-image launch (library-internal: the gadget passes it next to the public argument
 // structs, whose layouts are fixed): a Context's gate stream is stream_cells cells long, its image image_cells.
+struct PlaceTable;
 struct ContextPeriod {
     uint64_t stream_cells, image_cells;
+    const PlaceTable *place = nullptr;   // shared context (HSW_GADGET_SHARED_CONTEXT): the table path; stream_cells = image_cells = 0
+};
+
+// Shared-context placement (HSW_GADGET_SHARED_CONTEXT, library-internal): the map from gate-stream cell to image
+// cell as a device-resident table of jumps -- column breaks and interludes (the caller's own cells between two
+// digests) -- of any length.  Stream cell i sits at i + cum[k], k the last jump with cell[k] <= i (0 before the
+// first).  The table-path kernels take it as an extra kernel argument, so ExpandParams / SmallFrames / FrameBreaks
+// and every existing launch keep their 16-entry break tables.
+struct PlaceTable {
+    const uint64_t *cell;       // n jump cells, ascending (equal cells allowed), absolute gate-stream cells
+    const uint64_t *cum;        // cum[k]: the gaps of jumps 0..k summed
+    const uint64_t *lk_shift;   // expansion: per digest of the launch (blk / frame_every), cumulative caller lookup entries
+    uint64_t n;
+    uint64_t base;              // expansion: gate-stream cell that ExpandParams::gate (no gaps added) stands for
 };
 
 struct FrameDesc;   // hsw_frame.hpp
@@ -94,10 +109,18 @@ struct SmallFrames;
 // The small-batch kernel (hsw_small.hpp; 8-bit table only): 37 waves per block, one sub-unit program each;
 // with `frames` the digest frames are written by extra waves of the same launch.
 hipError_t launch_small(const ExpandParams &p, const SmallFrames *frames, int limbs, hipStream_t stream);
+// The same with a placement table (whole-digest launches only): hsw_small_table_kernel.
+hipError_t launch_small_table(const ExpandParams &p, const SmallFrames *frames, const PlaceTable &t, hipStream_t stream);
+// Whole-digest expansion with a placement table (8-bit table only): hsw_expand_table_kernel.
+hipError_t launch_expand_table(const ExpandParams &p, const PlaceTable &t, int tile, hipStream_t stream);
 // d_inv_tbl: k^-1 mod p for k = 0..(largest n_blocks), 4 x u64 each, in the output representation
 hipError_t launch_frames(const FrameDesc *d_descs, size_t n, const uint8_t *blocks, const uint32_t *pre_states,
                          const uint32_t *next_states, const uint64_t *d_inv_tbl, void *gate, void *lookup,
                          const FrameBreaks &brk, unsigned slices, bool montgomery, hipStream_t stream);
+// The same placed by a table (brk.n = 0): hsw_frame_table_kernel.
+hipError_t launch_frames_table(const FrameDesc *d_descs, size_t n, const uint8_t *blocks, const uint32_t *pre_states,
+                               const uint32_t *next_states, const uint64_t *d_inv_tbl, void *gate, void *lookup,
+                               const PlaceTable &t, unsigned slices, bool montgomery, hipStream_t stream);
 
 }  // namespace hsw
 #endif

@@ -2,6 +2,7 @@
 // The expansion kernel template lives in hsw_expand.hpp and is instantiated per
 // table width in hsw_expand_l{1,2,4,8,16}.hip (parallel compilation).
 #include "hsw_expand.hpp"
+#include "hsw_small.hpp"   // (the table-path kernels of shared contexts, below)
 
 namespace hsw {
 
@@ -226,4 +227,19 @@ hipError_t launch_chain_var(const uint8_t *blocks, size_t n_messages, const uint
     return hipGetLastError();
 }
 
+// The table-path kernels of shared contexts (HSW_GADGET_SHARED_CONTEXT), 8-bit spread table.  In this translation unit
+// rather than next to their kernel-argument twins (hsw_small_l2.hip): there they changed the code the compiler
+// scheduled for the existing instantiations.
+// Whole-digest expansion placed by a jump table (shared contexts): the internals-mode tiles of launch_expand_L<2>.
+hipError_t launch_expand_table(const ExpandParams &p, const PlaceTable &t, int tile, hipStream_t stream) {
+    if (p.n_blocks == 0) return hipSuccess;
+    switch (tile) {
+        case 64: return launch_expand_table_LTR<2, 64, 32>(p, t, stream);
+        case 128: return launch_expand_table_LTR<2, 128, 16>(p, t, stream);
+        default: return launch_expand_table_LTR<2, 32, 64>(p, t, stream);
+    }
+}
+hipError_t launch_small_table(const ExpandParams &p, const SmallFrames *frames, const PlaceTable &t, hipStream_t stream) {
+    return launch_small_table_L<2>(p, frames, t, stream);
+}
 }  // namespace hsw

@@ -39,6 +39,7 @@ struct RegionTape {
     std::vector<fr::Fe> const_canon, const_mont;
     // device side of the gather: image position of every witness cell, staging of the packed values
     uint32_t *d_wit_pos = nullptr;
+    std::vector<uint64_t> pos_layout;                     // the layout d_wit_pos was computed for (layout_key)
     void *d_distinct = nullptr;
     int device = 0;
 };
@@ -202,6 +203,14 @@ static int ensure_tape(hsw_gadget *g) {
 
 // what the digests assigned so far cover
 struct Extent { uint64_t cells, wit, lookups, limbs; };
+// Everything image_cell() depends on besides the stream cell
+static std::vector<uint64_t> layout_key(const Context &c) {
+    std::vector<uint64_t> k{c.max_rows, c.origin_row, c.context_images ? c.ctx_stream() : 0, c.ctx_image()};
+    k.insert(k.end(), c.break_cell.begin(), c.break_cell.end());
+    k.insert(k.end(), c.break_gap.begin(), c.break_gap.end());
+    return k;
+}
+
 static Extent extent_so_far(const hsw_gadget *g) {
     const size_t h = g->cfg.cur_hash_idx;
     if (h == 0) return Extent{0, 0, 0, 0};
@@ -254,6 +263,9 @@ int hsw_gadget_download_region_distinct(hsw_gadget *g, void *distinct, size_t ca
     (void)hipGetDevice(&prev);
     if (prev != device && hipSetDevice(device) != hipSuccess) return HSW_ERR_NO_DEVICE;
     hipError_t he = hipSuccess;
+    // (positions follow the layout: one that has changed since -- a shared context's declarations, say -- is recomputed)
+    const std::vector<uint64_t> key = layout_key(c);
+    if (t.d_wit_pos && key != t.pos_layout) drop_region_tape_positions(&t);
     if (!t.d_wit_pos) {                                   // first delivery with this layout: where every witness sits in the image
         // (image positions are 32-bit: every Context's image together must stay below 2^32 cells)
         if (c.max_rows && c.columns * c.max_rows * (c.context_images ? c.init_capacity : 1) >= (1ull << 32)) {
@@ -266,6 +278,7 @@ int hsw_gadget_download_region_distinct(hsw_gadget *g, void *distinct, size_t ca
         he = hipMalloc((void **)&t.d_wit_pos, pos.size() * sizeof(uint32_t));
         if (he == hipSuccess) he = hipMalloc(&t.d_distinct, pos.size() * (size_t)HSW_CELL_BYTES);
         if (he == hipSuccess) he = hipMemcpy(t.d_wit_pos, pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (he == hipSuccess) t.pos_layout = key;
         if (he != hipSuccess) {
             (void)hipFree(t.d_wit_pos); (void)hipFree(t.d_distinct);
             t.d_wit_pos = nullptr; t.d_distinct = nullptr;
@@ -315,6 +328,11 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
         if (c.context_images) {                                   // entry j of Context h = j / own: its own lookup column
             const uint64_t own = c.ctx_own_lookups, Lp = c.ctx_lookups();
             for (uint64_t j = lo; j < hi; j++) lk[(j / own) * Lp + j % own] = value(t.lookup_code[j]);
+            return;
+        }
+        if (c.shared && !c.digest_entry0.empty()) {               // shared context: past the caller's entries of the interludes
+            Cell *lk0 = static_cast<Cell *>(dst->lookup);
+            for (uint64_t j = lo; j < hi; j++) lk0[c.lookup_cell(j)] = value(t.lookup_code[j]);
             return;
         }
         for (uint64_t j = lo; j < hi; j++) lk[j] = value(t.lookup_code[j]);

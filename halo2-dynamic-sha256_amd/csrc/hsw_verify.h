@@ -8,6 +8,8 @@
 
 namespace hsw {
 
+struct PlaceTable;   // hsw_kernels.h
+
 enum : uint32_t {      // mirrors HSW_VERIFY_* of include/hsw.h
     VERIFY_CONSTANT = 1, VERIFY_COPY = 2, VERIFY_GATE_ROW = 3, VERIFY_ASSERT_EQ = 4, VERIFY_RANGE = 5,
     VERIFY_CHIP = 6, VERIFY_LOOKUP = 7, VERIFY_NEXT_STATE = 8,
@@ -73,6 +75,9 @@ struct FrameVerifyParams {
     VerifyReport *report;
 };
 hipError_t launch_verify_frames(const FrameVerifyParams &p, size_t n_digests, hipStream_t stream);
+// Shared contexts (HSW_GADGET_SHARED_CONTEXT): the same checks with the cells placed by a jump table (hsw_kernels.h).
+hipError_t launch_verify_table(const VerifyParams &p, const PlaceTable &t, size_t n_blocks, hipStream_t stream);
+hipError_t launch_verify_frames_table(const FrameVerifyParams &p, const PlaceTable &t, size_t n_digests, hipStream_t stream);
 
 }  // namespace hsw
 #endif

@@ -36,12 +36,15 @@ class Sha256DynamicConfig:
     """configure (lib.rs:49-69) + new_context (lib.rs:351-360) in one object."""
 
     def __init__(self, engine, max_variable_byte_sizes, is_input_range_check=True, whole_digest=False, independent=False,
-                 context_images=False):
+                 context_images=False, shared_context=False):
         """whole_digest: also emit the cells digest() itself allocates (lib.rs:122-178, 294-341;
         SURVEY 8 f4, assumption A4) -- needs an engine in HSW_MODE_HALO2_INTERNALS.
         independent: every digest is a synthesis of its own (HSW_GADGET_INDEPENDENT: K proofs in one launch).
         context_images: with independent, every proof gets a column image and lookup column of its own at the same
-        Context origin (HSW_GADGET_CONTEXT_IMAGES; all max_variable_byte_sizes equal)."""
+        Context origin (HSW_GADGET_CONTEXT_IMAGES; all max_variable_byte_sizes equal).
+        shared_context: with whole_digest, every digest works on the same Context and the circuit may assign cells
+        of its own between two digests (HSW_GADGET_SHARED_CONTEXT, set_digest_origin); layouts of up to
+        HSW_GADGET_MAX_COLUMNS columns."""
         self.engine = engine
         self.whole_digest = bool(whole_digest)
         self.context_images = bool(context_images)
@@ -53,7 +56,8 @@ class Sha256DynamicConfig:
                                            1 if is_input_range_check else 0,
                                            (N.HSW_GADGET_WHOLE_DIGEST if whole_digest else 0) |
                                            (N.HSW_GADGET_INDEPENDENT if independent else 0) |
-                                           (N.HSW_GADGET_CONTEXT_IMAGES if context_images else 0), C.byref(h))
+                                           (N.HSW_GADGET_CONTEXT_IMAGES if context_images else 0) |
+                                           (N.HSW_GADGET_SHARED_CONTEXT if shared_context else 0), C.byref(h))
         if rc != N.HSW_OK:
             raise N.HswError(rc, self.lib.hsw_last_error(engine.h).decode())
         self.h = h
@@ -119,6 +123,11 @@ class Sha256DynamicConfig:
         """Where the caller's halo2-base Context stands when the gadget takes over (hsw_gadget_set_origin):
         ctx.advice_alloc[0] = (column, row), ctx.zero_cell.is_some(), ctx.cells_to_lookup.len()."""
         self._ok(self.lib.hsw_gadget_set_origin(self.h, column, row, 1 if zero_cell_loaded else 0, lookups_queued))
+
+    def set_digest_origin(self, h, column, row, lookups_queued):
+        """Where the shared Context stands just before digest h (hsw_gadget_set_digest_origin): ctx.advice_alloc[0] =
+        (column, row) and ctx.cells_to_lookup.len() after the circuit's own cells since digest h-1."""
+        self._ok(self.lib.hsw_gadget_set_digest_origin(self.h, h, column, row, lookups_queued))
 
     def reset(self):
         """Next synthesis pass: all cursors back to their start, buffers and layout kept

@@ -563,6 +563,25 @@ int hsw_gadget_create(hsw_engine *e, const size_t *max_variable_byte_sizes, size
  * only); the region tape, distinct delivery and hsw_gadget_replay_region keep their meaning; hsw_gadget_verify and
  * hsw_gadget_place work.  hsw_gadget_download_region_compact and hsw_gadget_seek return HSW_ERR_UNSUPPORTED. */
 #define HSW_GADGET_CONTEXT_IMAGES 4u
+/* With HSW_GADGET_WHOLE_DIGEST, not with HSW_GADGET_INDEPENDENT / HSW_GADGET_CONTEXT_IMAGES (HSW_ERR_INVALID_ARG);
+ * engines with the 8-bit spread table only (HSW_ERR_UNSUPPORTED): every digest of the pass works on the SAME halo2-base
+ * Context, and the circuit may assign cells of its own between two digests (the gate / range chips, lib.rs:71-76 takes
+ * whatever Context it is handed) -- an interlude, declared with hsw_gadget_set_digest_origin.
+ *   - hsw_gadget_set_columns / hsw_gadget_set_origin accept layouts of up to HSW_GADGET_MAX_COLUMNS columns (instead
+ *     of HSW_MAX_BREAKS + 1) and clear every declaration; hsw_gadget_reset keeps them, as it keeps the origin.
+ *   - hsw_hash_result gate cells stay gadget-stream indices (the interludes take none); hsw_gadget_cell_position /
+ *     hsw_gadget_result_cells report the FlexGate (column, row) after the jumps; *_lookup indices are d_lookup cells,
+ *     i.e. positions in the Context's whole lookup queue, the caller's entries included.
+ *   - interlude cells and lookup entries are the caller's: never written on the device, never touched in the
+ *     caller's host buffers by hsw_gadget_download_region / hsw_gadget_replay_region.
+ *   - a declaration may grow the image (or the lookup column): the engine is drained, the buffers reallocated and
+ *     copied, so device pointers from earlier hsw_gadget_streams calls are stale after it.
+ *   - hsw_gadget_verify checks the interludes' layout (the caller's lookup entries are skipped).
+ *   - hsw_gadget_seek, hsw_gadget_download_region_compact and hsw_gadget_place return HSW_ERR_UNSUPPORTED.
+ * Without the flag every call behaves as before. */
+#define HSW_GADGET_SHARED_CONTEXT 8u
+/* Columns a HSW_GADGET_SHARED_CONTEXT layout may span (at k = 17 one 1024-byte digest fills 9) */
+#define HSW_GADGET_MAX_COLUMNS 1024u
 int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, size_t n_hashes,
                          int is_input_range_check, uint32_t flags, hsw_gadget **out);
 void hsw_gadget_destroy(hsw_gadget *g);
@@ -572,7 +591,7 @@ void hsw_gadget_destroy(hsw_gadget *g);
  * `row + len >= max_rows -> next column` (assumption A3-iii), unassigned tail rows 0.
  * max_rows = the gate's usable rows (RangeConfig.gate.max_rows, lib.rs:355).  The
  * layout depends only on max_variable_byte_sizes, never on the messages.
- * HSW_ERR_TOO_LARGE: more than HSW_MAX_BREAKS + 1 columns. */
+ * HSW_ERR_TOO_LARGE: more than HSW_MAX_BREAKS + 1 columns (HSW_GADGET_MAX_COLUMNS with HSW_GADGET_SHARED_CONTEXT). */
 int hsw_gadget_set_columns(hsw_gadget *g, uint64_t max_rows, uint64_t *n_columns);
 /* HSW_GADGET_WHOLE_DIGEST, before the first digest of a synthesis pass (fresh, or after hsw_gadget_reset;
  * before or after hsw_gadget_set_columns): where the caller's halo2-base Context stands when it hands
@@ -598,6 +617,18 @@ int hsw_gadget_set_columns(hsw_gadget *g, uint64_t max_rows, uint64_t *n_columns
  * origin and layout are kept). */
 int hsw_gadget_set_origin(hsw_gadget *g, uint64_t column, uint64_t row, int zero_cell_loaded,
                           uint64_t lookups_already_queued);
+/* HSW_GADGET_SHARED_CONTEXT with a column image: where the Context stands just before digest h of the pass, after the
+ * caller's own cells since digest h-1 -- column, row = ctx.advice_alloc[0], lookups_queued = ctx.cells_to_lookup.len().
+ * Digest h's prologue lands at (column, row); its lookup entries start at d_lookup cell lookups_queued.  The layout
+ * depends only on max_variable_byte_sizes and the declarations, never on the messages: a batch prover may declare
+ * every origin first and run the pass as one hsw_gadget_digest_batch.  Declaring h drops the declarations of every
+ * later digest -- unless it repeats h's current declaration, which changes nothing (a prover that declares the same
+ * interludes pass after pass keeps its layout, its device table and its tape positions).  A declaration that changes
+ * the layout zeroes the image cells past digest h-1's end again (what an earlier layout wrote there).  HSW_ERR_INVALID_ARG, with the layout unchanged: not a shared context or no column image, h = 0 or
+ * h >= n_hashes, digest h already assigned in this pass, row >= max_rows, (column, row) before the next free cell
+ * after digest h-1's layout (in (column, row) order), or lookups_queued below the queue length after digest h-1.
+ * HSW_ERR_TOO_LARGE: the layout would need more than HSW_GADGET_MAX_COLUMNS columns. */
+int hsw_gadget_set_digest_origin(hsw_gadget *g, size_t h, uint64_t column, uint64_t row, uint64_t lookups_queued);
 /* Start the next synthesis pass with the same buffers and layout: every cursor back to
  * its initial value (cur_hash_idx, num_limb_sum, the stream cursors, the Context's zero
  * cell).  What the reference's harnesses do by cloning the config per synthesis
@@ -667,7 +698,8 @@ typedef struct hsw_region_tape {
     uint64_t distinct_capacity;          /* ... of all digests of the gadget: size a reusable buffer with this */
     uint64_t gate_cells, lookup_cells, limb_calls;   /* entries of the code arrays that are assigned so far */
     const uint32_t *gate_code;           /* per gate-stream cell (hsw_gadget_cell_position gives its column / row) */
-    const uint32_t *lookup_code;         /* per lookup entry of the gadget (entry j sits at d_lookup cell origin_lookups + j) */
+    const uint32_t *lookup_code;         /* per lookup entry of the gadget (entry j sits at d_lookup cell origin_lookups + j;
+                                            shared contexts: after the caller's entries of every interlude before it) */
     const uint32_t *chip_dense_code, *chip_spread_code;   /* per limb call n: column n % ncols, row n / ncols */
     const void *consts;                  /* n_consts 32-byte cells in the gadget's current representation */
     uint64_t n_consts;

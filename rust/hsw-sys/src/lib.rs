@@ -30,6 +30,8 @@ pub const HSW_CELL_BYTES: usize = 32;
 pub const HSW_GADGET_WHOLE_DIGEST: u32 = 1;
 pub const HSW_GADGET_INDEPENDENT: u32 = 2;
 pub const HSW_GADGET_CONTEXT_IMAGES: u32 = 4;
+pub const HSW_GADGET_SHARED_CONTEXT: u32 = 8;
+pub const HSW_GADGET_MAX_COLUMNS: u32 = 1024;
 
 #[repr(C)]
 #[derive(Default, Clone, Copy, Debug)]
@@ -407,6 +409,8 @@ extern "C" {
     /// Where the caller's `Context` stands: `ctx.advice_alloc[0]`, `ctx.zero_cell.is_some()`, `ctx.cells_to_lookup.len()`.
     pub fn hsw_gadget_set_origin(g: *mut hsw_gadget, column: u64, row: u64, zero_cell_loaded: c_int,
                                  lookups_already_queued: u64) -> c_int;
+    /// Shared context: where the `Context` stands just before digest `h` (`ctx.advice_alloc[0]`, `ctx.cells_to_lookup.len()`).
+    pub fn hsw_gadget_set_digest_origin(g: *mut hsw_gadget, h: usize, column: u64, row: u64, lookups_queued: u64) -> c_int;
     pub fn hsw_gadget_reset(g: *mut hsw_gadget) -> c_int;
     pub fn hsw_gadget_seek(g: *mut hsw_gadget, hash_idx: usize) -> c_int;
     /// Buffer placement: try `candidates` allocations of the chip columns, keep the one the gadget's own batch runs fastest on.

@@ -19,7 +19,7 @@
 //! ```
 //!
 //! `digest_gpu` NEVER turns a circuit that works on the CPU into an error: whatever the C side refuses (no device,
-//! a layout with more than 17 columns, a `Context` that moved between two digests, ...) makes it return `Ok(None)`
+//! a layout past HSW_GADGET_MAX_COLUMNS columns, an interlude it cannot place, ...) makes it return `Ok(None)`
 //! before it has touched `ctx`, and `digest` runs the reference's own body.  Only errors of `Region::assign_advice`
 //! itself propagate.
 //!
@@ -108,6 +108,11 @@ struct Backend {
     // delivery: 0.33 ms instead of 0.81 ms for the bench circuit's region)
     distinct: *mut [u64; 4],
     distinct_cells: usize,
+    // HSW_GADGET_SHARED_CONTEXT (8-bit spread tables: the table-path kernels): interludes and layouts past 17 columns
+    shared: bool,
+    // the origin the gadget's layout was last based on (set_origin is skipped when a pass starts at the same place:
+    // the declarations of the previous pass, and the table on the device, then stay as they are)
+    origin: Option<((usize, usize), usize, bool)>,
 }
 
 thread_local! { static BACKEND: RefCell<Option<Backend>> = RefCell::new(None); }
@@ -118,11 +123,14 @@ impl Backend {
         // `be` owns whatever exists so far: an early `?` drops it and Drop releases engine / gadget / staging
         let mut be = Self { engine: ptr::null_mut(), gadget: ptr::null_mut(), key, expect: None,
                             chip_columns: sha256.spread_config.num_advice_columns,
-                            distinct: ptr::null_mut(), distinct_cells: 0 };
+                            distinct: ptr::null_mut(), distinct_cells: 0, shared: false, origin: None };
+        be.shared = be.key.1 == 8;
         check(unsafe { sys::hsw_engine_create_ex(device, ptr::null_mut(), be.key.1 as u32, be.key.2 as u32,
                                                  sys::HSW_MODE_HALO2_INTERNALS, &mut be.engine) })?;
         check(unsafe { sys::hsw_gadget_create_ex(be.engine, be.key.0.as_ptr(), be.key.0.len(), be.key.3 as i32,
-                                                 sys::HSW_GADGET_WHOLE_DIGEST, &mut be.gadget) })?;
+                                                 sys::HSW_GADGET_WHOLE_DIGEST |
+                                                     if be.shared { sys::HSW_GADGET_SHARED_CONTEXT } else { 0 },
+                                                 &mut be.gadget) })?;
         // halo2curves' in-memory Fr IS the cell format: no from_repr (a Montgomery multiplication) per cell
         check(unsafe { sys::hsw_gadget_set_repr(be.gadget, sys::HSW_REPR_MONTGOMERY) })?;
         // the column image from (0, 0); every synthesis pass re-bases it on where its Context stands (set_origin)
@@ -130,7 +138,8 @@ impl Backend {
         check(unsafe { sys::hsw_gadget_set_columns(be.gadget, be.key.4, &mut columns) })?;
         // where the chip columns sit relative to the gate stream is worth up to 8 % of an HBM-bound batch (DESIGN.md
         // 5.1): for circuits of a few hundred blocks or more let the gadget try three allocations, once
-        if be.key.0.iter().sum::<usize>() / 64 >= 256 {
+        // (not for shared-context gadgets: hsw_gadget_place refuses them, the default placement stays)
+        if !be.shared && be.key.0.iter().sum::<usize>() / 64 >= 256 {
             check(unsafe { sys::hsw_gadget_place(be.gadget, 3, ptr::null_mut(), ptr::null_mut()) })?;
         }
         let mut tape = unsafe { std::mem::zeroed::<sys::hsw_region_tape>() };
@@ -260,10 +269,21 @@ fn fetch<F: PrimeField>(be: &mut Backend, sha256: &Sha256DynamicConfig<F>, here:
         // a new synthesis pass (= config.sha256.clone(), lib.rs:440): all cursors back, the region starts where the
         // Context stands now.  HSW_ERR_TOO_LARGE (more than 17 columns from this row) and friends => CPU path.
         ok(unsafe { sys::hsw_gadget_reset(be.gadget) })?;
-        ok(unsafe { sys::hsw_gadget_set_origin(be.gadget, (here.0).0 as u64, (here.0).1 as u64, zero_loaded as i32, here.1 as u64) })?;
+        if be.origin != Some((here.0, here.1, zero_loaded)) {
+            be.origin = None;
+            ok(unsafe { sys::hsw_gadget_set_origin(be.gadget, (here.0).0 as u64, (here.0).1 as u64, zero_loaded as i32, here.1 as u64) })?;
+            be.origin = Some((here.0, here.1, zero_loaded));
+        }
+    } else if be.shared {
+        // digest h >= 1 of a shared-context gadget: declare where the Context stands now -- after the circuit's own
+        // cells since digest h-1 (an interlude), or right where digest h-1 ended.  Declaring every digest keeps a
+        // declaration of an earlier pass from outliving it; an unchanged one costs nothing.  A refusal means the CPU
+        // path takes over.
+        ok(unsafe { sys::hsw_gadget_set_digest_origin(be.gadget, sha256.cur_hash_idx, (here.0).0 as u64, (here.0).1 as u64,
+                                                      here.1 as u64) })?;
     } else if be.expect != Some(here) {
-        // the circuit used the gate / range chips between two digests: the gadget's layout (fixed when the pass
-        // started) no longer describes the region.  INTEGRATION.md section 3 -- the CPU path takes over.
+        // no shared context (a spread table other than 8 bits): the circuit used the gate / range chips between two
+        // digests, and the gadget's layout no longer describes the region -- the CPU path takes over
         return None;
     }
     let mut view = unsafe { std::mem::zeroed::<sys::hsw_gadget_view>() };

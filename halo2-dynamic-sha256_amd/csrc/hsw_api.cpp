@@ -15,6 +15,7 @@
 #include "../../include/hsw.h"
 #include "hsw_fr.hpp"
 #include "hsw_frame.hpp"
+#include "hsw_gadget_layout.hpp"
 #include "hsw_nounwind.hpp"
 #include "hsw_kernels.h"
 #include "hsw_layout.h"
@@ -580,30 +581,20 @@ int hsw_pack_plan_query(const hsw_shape *shape, size_t n_blocks, uint64_t start_
     std::memset(out, 0, sizeof *out);
     const std::vector<uint8_t> lens =
         hsw::TapeBuilder((int)shape->limbs_per_spread, shape->mode == HSW_MODE_HALO2_INTERNALS).block();
-    const uint64_t G = shape->gate_cells_per_block;
-    uint64_t row = start_row, cell = 0, gaps = 0;
-    for (size_t b = 0; b < n_blocks; b++) {
-        if (row + G + 4 < max_rows) {          // no call of this block can reach the end of the column
-            row += G;
-            cell += G;
-            continue;
-        }
-        for (uint8_t len : lens) {
-            if (row + len >= max_rows) {       // halo2-lib v0.2.x assign_region: move to the next column (A3)
-                if (out->n_breaks == HSW_MAX_BREAKS) return HSW_ERR_TOO_LARGE;
-                out->break_cell[out->n_breaks] = cell;
-                out->break_gap[out->n_breaks] = max_rows - row;
-                out->n_breaks++;
-                gaps += max_rows - row;
-                row = 0;
-            }
-            row += len;
-            cell += len;
-        }
+    // n_blocks block tapes without frames, by the walk that lays a gadget's whole pass out (hsw_gadget_layout.hpp)
+    std::vector<uint64_t> bc, bg;
+    hsw::ColumnWalk w{max_rows, 0, start_row, 0, bc, bg};
+    for (size_t b = 0; b < n_blocks && bc.size() <= HSW_MAX_BREAKS; b++) w.block(lens, shape->gate_cells_per_block);
+    uint64_t gaps = 0;
+    for (size_t k = 0; k < bc.size() && k < HSW_MAX_BREAKS; k++) {
+        out->break_cell[k] = bc[k];
+        gaps += out->break_gap[k] = bg[k];
+        out->n_breaks++;
     }
+    if (bc.size() > HSW_MAX_BREAKS) return HSW_ERR_TOO_LARGE;
     out->columns_touched = out->n_breaks + 1;
-    out->span_cells = cell + gaps;
-    out->end_row = row;
+    out->span_cells = w.cell + gaps;
+    out->end_row = w.row;
     return HSW_OK;
 } HSW_NO_UNWIND
 

@@ -142,6 +142,21 @@ struct DeviceScope {
     ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
+int hip_status(hipError_t he) { return he == hipSuccess ? HSW_OK : he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP; }
+
+// A zeroed device buffer of `bytes` (at least one cell; unassigned advice cells are 0) whose first `keep` bytes are
+// those of `old`.  `old` itself is left alone: a caller can get several buffers and commit only when it has them all.
+hipError_t fresh_zeroed(void **out, size_t bytes, const void *old = nullptr, size_t keep = 0) {
+    if (!bytes) bytes = HSW_CELL_BYTES;
+    void *p = nullptr;
+    hipError_t he = hipMalloc(&p, bytes);
+    if (he == hipSuccess) he = hipMemset(p, 0, bytes);
+    if (he == hipSuccess && old && keep) he = hipMemcpy(p, old, keep, hipMemcpyDeviceToDevice);
+    if (he != hipSuccess) { (void)hipFree(p); p = nullptr; }
+    *out = p;
+    return he;
+}
+
 }  // namespace
 
 struct DeviceScopeG : DeviceScope { using DeviceScope::DeviceScope; };   // for the C ABI functions below
@@ -326,51 +341,60 @@ int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool who
     if (he == hipSuccess) he = hipMemset(c->d_chip_spread, 0, col_bytes);
     if (he != hipSuccess) {
         delete c;
-        return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP;
+        return hip_status(he);
     }
     *out = c;
     return HSW_OK;
 }
 
-// The FlexGate column breaks of `sizes` digests laid out from row `row0` with a Context that has (or has not)
-// already loaded its zero cell: break k before stream cell bc[k], leaving bg[k] tail rows of its column unused.
-static int column_breaks(const hsw_shape &shape, const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows,
-                         uint64_t row0, bool zero_loaded, std::vector<uint64_t> &bc, std::vector<uint64_t> &bg) {
-    const uint64_t G = shape.gate_cells_per_block;
-    size_t n = 0;
-    if (hsw_gate_tape(&shape, nullptr, 0, &n) != HSW_OK) return HSW_ERR_INVALID_ARG;
-    std::vector<uint8_t> block_tape(n);
-    hsw_gate_tape(&shape, block_tape.data(), n, nullptr);
-    bc.clear(); bg.clear();
-    uint64_t row = row0, cell = 0;                        // the Context's next free row (hsw_gadget_set_origin)
-    auto walk = [&](const std::vector<uint8_t> &lens) {
-        for (uint8_t len : lens) {
-            if (row + len >= rows) {                      // halo2-lib v0.2.x assign_region: next column (A3-iii)
-                bc.push_back(cell); bg.push_back(rows - row);
-                row = 0;
-            }
-            row += len; cell += len;
-        }
-    };
-    bool zero = zero_loaded;                              // a Context that already caches its zero cell assigns none
-    for (size_t b : sizes) {
-        for (int section = 0; section < 2; section++) {
-            if (section == 1) {
-                if (!zero) { walk({1}); zero = true; }    // Context.zero_cell, first load_zero
-                for (size_t k = 0; k < b / 64; k++) {
-                    if (row + G + 8 < rows) { row += G; cell += G; }
-                    else walk(block_tape);
-                }
-            }
-            size_t m = 0;
-            int rc = hsw_frame_tape(&shape, b, rc_inputs ? 1 : 0, section, nullptr, 0, &m);
-            if (rc != HSW_OK) return rc;
-            std::vector<uint8_t> t(m);
-            hsw_frame_tape(&shape, b, rc_inputs ? 1 : 0, section, t.data(), m, nullptr);
-            walk(t);
-        }
+int Context::plan_layout(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows, const std::vector<DigestOrigin> &decl,
+                         Layout *out) const {
+    if (!rows) return HSW_OK;                             // no image: the stream as it is, from the origin
+    // context images: ONE Context's walk (every Context is laid out alike), K images of it
+    const size_t n = context_images && !sizes.empty() ? 1 : sizes.size();
+    const int rc = layout_walk(shape, sizes.data(), n, rc_inputs, rows, shared ? &decl : nullptr, out);
+    if (rc != HSW_OK) return rc;
+    if (shared) return out->columns > HSW_GADGET_MAX_COLUMNS ? HSW_ERR_TOO_LARGE : HSW_OK;
+    out->digest_cell0.clear(); out->digest_entry0.clear(); out->digest_lookup0.clear();   // (one lookup run, no table)
+    if (context_images) out->period = ctx_digest_cells + (out->origin_zero_loaded ? 0u : 1u);
+    return out->break_cell.size() > HSW_MAX_BREAKS ? HSW_ERR_TOO_LARGE : HSW_OK;
+}
+
+int Context::adopt(Layout &nl, bool fresh_image, bool fresh_lookup, uint64_t clear_from) {
+    const size_t K = context_images ? init_capacity : 1, none = ~(size_t)0;
+    const bool table = shared && nl.max_rows, changed = !nl.same_map(layout);
+    size_t img_cells = none, img_keep = 0, lk_cells = none, lk_keep = 0;
+    if (table) {                                          // the image grows: the columns so far are copied over
+        const uint64_t have = nl.max_rows == layout.max_rows ? image_columns : 0;   // (another column height: a fresh image)
+        if (nl.columns > have) { img_cells = (size_t)nl.image_cells(); img_keep = (size_t)(have * nl.max_rows); }
+    } else if (fresh_image) {
+        img_cells = K * (size_t)nl.image_cells();
     }
-    return bc.size() > HSW_MAX_BREAKS ? HSW_ERR_TOO_LARGE : HSW_OK;
+    // the lookup-advice stream is indexed from the Context's first queued cell: [0, origin_lookups) are the caller's
+    if (fresh_lookup) lk_cells = (size_t)own_lookup_capacity + K * (size_t)nl.origin_lookups;
+    else if (table && nl.lookups_end > lookup_capacity) { lk_cells = (size_t)nl.lookups_end; lk_keep = (size_t)lookup_capacity; }   // the interludes' entries
+    const bool clear = table && changed;
+    if (img_cells != none || lk_cells != none || clear) {
+        int device = 0;
+        hsw_engine_stream(engine, nullptr, &device);
+        DeviceScope ds(device);
+        if (!ds.ok) return HSW_ERR_NO_DEVICE;
+        // (the callers run on a drained engine: nothing still writes the buffers replaced here)
+        void *img = nullptr, *lk = nullptr;
+        hipError_t he = hipSuccess;
+        if (img_cells != none) he = fresh_zeroed(&img, img_cells * HSW_CELL_BYTES, d_gate, img_keep * HSW_CELL_BYTES);
+        if (he == hipSuccess && lk_cells != none) he = fresh_zeroed(&lk, lk_cells * HSW_CELL_BYTES, d_lookup, lk_keep * HSW_CELL_BYTES);
+        if (he != hipSuccess) { (void)hipFree(img); return hip_status(he); }
+        if (img) { (void)hipFree(d_gate); d_gate = img; image_columns = nl.columns; }
+        if (lk) { (void)hipFree(d_lookup); d_lookup = lk; lookup_capacity = lk_cells; }
+        if (img || lk) free_compact_staging();            // sized for the old geometry
+        const uint64_t end = image_columns * nl.max_rows;
+        if (clear && clear_from < end)                    // cells an earlier layout wrote past the unchanged part
+            (void)hipMemset(static_cast<uint8_t *>(d_gate) + (size_t)clear_from * HSW_CELL_BYTES, 0, (size_t)(end - clear_from) * HSW_CELL_BYTES);
+    }
+    layout = std::move(nl);
+    place_dirty = place_dirty || changed;
+    return HSW_OK;
 }
 
 int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows) {
@@ -378,192 +402,24 @@ int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint6
     if (independent && !context_images) return HSW_ERR_UNSUPPORTED;   // K regions in one stream: linear only
     const uint64_t G = shape.gate_cells_per_block;
     if (rows < G + 16) return HSW_ERR_INVALID_ARG;        // keeps a block inside <= 2 columns (kernel: <= 2 breaks per block)
-    if (origin_row >= rows) return HSW_ERR_INVALID_ARG;   // the Context's next free row lies inside its column
-    if (shared) {                                         // a new layout: the declarations made for the old one are dropped
-        const uint64_t old_rows = max_rows, old_cols = image_columns;
-        if (rows != max_rows) image_columns = 0;          // (a different column height: a fresh image)
-        max_rows = rows;
-        const int rc = shared_relayout(sizes, rc_inputs, rows, std::vector<DigestOrigin>(declared.size()), 0);
-        if (rc != HSW_OK) { max_rows = old_rows; image_columns = old_cols; return rc; }
-        declared.assign(declared.size(), DigestOrigin{});
-        return HSW_OK;
-    }
-    std::vector<uint64_t> bc, bg;
-    // context images: ONE Context's walk (every Context is laid out alike), K images of it
-    const std::vector<size_t> one(sizes.begin(), sizes.begin() + (sizes.empty() ? 0 : 1));
-    int rc = column_breaks(shape, context_images ? one : sizes, rc_inputs, rows, origin_row, origin_zero_loaded, bc, bg);
-    if (rc != HSW_OK) return rc;
-    const uint64_t cols = bc.size() + 1;
-    const size_t image_cells = (size_t)(cols * rows) * (context_images ? init_capacity : 1);
-    int device = 0;
-    hsw_engine_stream(engine, nullptr, &device);
-    DeviceScope ds2(device);
-    if (!ds2.ok) return HSW_ERR_NO_DEVICE;
-    // (outstanding work on the old image: the callers -- hsw_gadget_set_columns / _set_origin -- run on a drained engine)
-    void *img = nullptr;
-    hipError_t he = hipMalloc(&img, image_cells * HSW_CELL_BYTES);
-    if (he == hipSuccess) he = hipMemset(img, 0, image_cells * HSW_CELL_BYTES);   // unassigned advice cells are 0
-    if (he != hipSuccess) { if (img) (void)hipFree(img); return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP; }
-    (void)hipFree(d_gate);
-    d_gate = img;
-    free_compact_staging();                               // sized for the old geometry
-    max_rows = rows;
-    columns = cols;
-    set_breaks(bc, bg);
-    return HSW_OK;
-}
-
-void Context::set_breaks(std::vector<uint64_t> &bc, std::vector<uint64_t> &bg) {
-    break_cell.swap(bc);
-    break_gap.swap(bg);
-    break_cum.resize(break_gap.size());
-    uint64_t sum = 0;
-    for (size_t k = 0; k < break_gap.size(); k++) break_cum[k] = sum += break_gap[k];
-}
-
-uint64_t Context::gap_at(uint64_t cell) const {      // breaks are ascending: a binary search
-    const size_t k = (size_t)(std::upper_bound(break_cell.begin(), break_cell.end(), cell) - break_cell.begin());
-    return k ? break_cum[k - 1] : 0;
-}
-
-void Context::position(uint64_t cell, uint64_t *column, uint64_t *row) const {
-    if (context_images && max_rows) cell %= ctx_stream();  // the owning Context's own stream cell
-    uint64_t at = cell + origin_row + gap_at(cell);
-    if (max_rows) { if (column) *column = origin_column + at / max_rows; if (row) *row = at % max_rows; }
-    else { if (column) *column = origin_column; if (row) *row = at; }
-}
-
-uint64_t Context::image_cell(uint64_t cell) const {
-    uint64_t base = 0;
-    if (context_images && max_rows) {
-        const uint64_t C = ctx_stream(), h = cell / C;
-        base = h * ctx_image();
-        cell -= h * C;
-    }
-    return base + cell + (max_rows ? origin_row : 0) + gap_at(cell);
-}
-
-// Shared context: the pass laid out digest by digest from the origin, with a jump wherever a digest's declared origin
-// lies further on than the next free cell (an interlude; its gap may span columns) and its lookup entries
-// starting at the declared queue length.  bc / bg: every jump; lk0 / e0 per digest; cols: image columns used.
-static int shared_breaks(const hsw_shape &shape, const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows,
-                         uint64_t origin_column, uint64_t row0, bool zero_loaded, uint64_t lookups0,
-                         const std::vector<Context::DigestOrigin> &decl, std::vector<uint64_t> &bc,
-                         std::vector<uint64_t> &bg, std::vector<uint64_t> &lk0, std::vector<uint64_t> &e0,
-                         std::vector<uint64_t> &c0, uint64_t *cols, uint64_t *lookups_end) {
-    const uint64_t G = shape.gate_cells_per_block;
-    size_t n = 0;
-    if (hsw_gate_tape(&shape, nullptr, 0, &n) != HSW_OK) return HSW_ERR_INVALID_ARG;
-    std::vector<uint8_t> block_tape(n);
-    hsw_gate_tape(&shape, block_tape.data(), n, nullptr);
-    bc.clear(); bg.clear(); lk0.clear(); e0.clear(); c0.clear();
-    uint64_t col = 0, row = row0, cell = 0, lk = lookups0, own = 0;
-    auto walk = [&](const std::vector<uint8_t> &lens) {
-        for (uint8_t len : lens) {
-            if (row + len >= rows) {                      // halo2-lib v0.2.x assign_region: next column (A3-iii)
-                bc.push_back(cell); bg.push_back(rows - row);
-                row = 0; col++;
-            }
-            row += len; cell += len;
-        }
-    };
-    bool zero = zero_loaded;
-    for (size_t h = 0; h < sizes.size(); h++) {
-        const size_t b = sizes[h];
-        if (h < decl.size() && decl[h].set) {             // the caller's interlude ends at (column, row)
-            const Context::DigestOrigin &d = decl[h];
-            if (d.column < origin_column || d.row >= rows) return HSW_ERR_INVALID_ARG;
-            const uint64_t want = (d.column - origin_column) * rows + d.row, here = col * rows + row;
-            if (want < here || d.lookups < lk) return HSW_ERR_INVALID_ARG;
-            if (want > here) { bc.push_back(cell); bg.push_back(want - here); }
-            col = d.column - origin_column; row = d.row; lk = d.lookups;
-        }
-        lk0.push_back(lk);
-        c0.push_back(cell);
-        e0.push_back(own);
-        hsw_frame_shape fs;
-        int rc = hsw_frame_query(&shape, b, rc_inputs ? 1 : 0, &fs);
-        if (rc != HSW_OK) return rc;
-        lk += fs.digest_lookups;
-        own += fs.digest_lookups;
-        for (int section = 0; section < 2; section++) {
-            if (section == 1) {
-                if (!zero) { walk({1}); zero = true; }    // Context.zero_cell, first load_zero
-                for (size_t k = 0; k < b / 64; k++) {
-                    if (row + G + 8 < rows) { row += G; cell += G; }
-                    else walk(block_tape);
-                }
-            }
-            size_t m = 0;
-            rc = hsw_frame_tape(&shape, b, rc_inputs ? 1 : 0, section, nullptr, 0, &m);
-            if (rc != HSW_OK) return rc;
-            std::vector<uint8_t> t(m);
-            hsw_frame_tape(&shape, b, rc_inputs ? 1 : 0, section, t.data(), m, nullptr);
-            walk(t);
-        }
-    }
-    *cols = col + 1;
-    *lookups_end = lk;
-    return *cols > HSW_GADGET_MAX_COLUMNS ? HSW_ERR_TOO_LARGE : HSW_OK;
-}
-
-int Context::shared_relayout(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows,
-                             const std::vector<DigestOrigin> &decl, uint64_t clear_from) {
-    std::vector<uint64_t> bc, bg, lk0, e0, c0;
-    uint64_t cols = 0, lk_end = 0;
-    int rc = shared_breaks(shape, sizes, rc_inputs, rows, origin_column, origin_row, origin_zero_loaded, origin_lookups,
-                           decl, bc, bg, lk0, e0, c0, &cols, &lk_end);
-    if (rc != HSW_OK) return rc;
-    const bool changed = !(bc == break_cell && bg == break_gap && lk0 == digest_lookup0 && cols == columns);
-    if (!changed && cols <= image_columns && lk_end <= lookup_capacity) return HSW_OK;   // nothing to do
-    int device = 0;
-    hsw_engine_stream(engine, nullptr, &device);
-    DeviceScope ds(device);
-    if (!ds.ok) return HSW_ERR_NO_DEVICE;
-    // (the callers run on a drained engine: nothing still writes the buffers replaced here)
-    void *img = nullptr, *lk = nullptr;
-    hipError_t he = hipSuccess;
-    if (cols > image_columns) {                           // the image grows: the columns so far are copied over
-        const size_t bytes = (size_t)(cols * rows) * HSW_CELL_BYTES;
-        he = hipMalloc(&img, bytes);
-        if (he == hipSuccess) he = hipMemset(img, 0, bytes);   // unassigned advice cells are 0
-        if (he == hipSuccess && image_columns && d_gate)
-            he = hipMemcpy(img, d_gate, (size_t)(image_columns * rows) * HSW_CELL_BYTES, hipMemcpyDeviceToDevice);
-    }
-    if (he == hipSuccess && lk_end > lookup_capacity) {  // room for the caller's entries of the interludes
-        const size_t bytes = (size_t)lk_end * HSW_CELL_BYTES;
-        he = hipMalloc(&lk, bytes);
-        if (he == hipSuccess) he = hipMemset(lk, 0, bytes);
-        if (he == hipSuccess && d_lookup && lookup_capacity)
-            he = hipMemcpy(lk, d_lookup, (size_t)lookup_capacity * HSW_CELL_BYTES, hipMemcpyDeviceToDevice);
-    }
-    if (he != hipSuccess) {
-        if (img) (void)hipFree(img);
-        if (lk) (void)hipFree(lk);
-        return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP;
-    }
-    if (img) { (void)hipFree(d_gate); d_gate = img; image_columns = cols; }
-    if (lk) { (void)hipFree(d_lookup); d_lookup = lk; lookup_capacity = lk_end; }
-    if (img || lk) free_compact_staging();
-    if (changed && clear_from < image_columns * rows)      // cells an earlier layout wrote past the unchanged part
-        (void)hipMemset(static_cast<uint8_t *>(d_gate) + (size_t)clear_from * HSW_CELL_BYTES, 0,
-                        (size_t)(image_columns * rows - clear_from) * HSW_CELL_BYTES);
-    columns = cols;
-    set_breaks(bc, bg);
-    digest_lookup0.swap(lk0);
-    digest_entry0.swap(e0);
-    digest_cell0.swap(c0);
-    place_dirty = true;
-    return HSW_OK;
+    if (layout.origin_row >= rows) return HSW_ERR_INVALID_ARG;   // the Context's next free row lies inside its column
+    Layout nl = layout.origin();
+    // (shared context -- a new layout: the declarations made for the old one are dropped)
+    const std::vector<DigestOrigin> none(declared.size());
+    int rc = plan_layout(sizes, rc_inputs, rows, none, &nl);
+    if (rc == HSW_OK) rc = adopt(nl, true, false, 0);
+    if (rc == HSW_OK) declared = none;
+    return rc;
 }
 
 int Context::upload_place() {
     if (!place_dirty && d_place) return HSW_OK;
     // [jump cells n][cumulative gaps n][per digest: the caller's lookup entries before it, cumulative]
-    const size_t n = break_cell.size(), H = digest_lookup0.size();
+    const Layout &l = layout;
+    const size_t n = l.break_cell.size(), H = l.digest_lookup0.size();
     std::vector<uint64_t> h(2 * n + (H ? H : 1), 0);
-    for (size_t k = 0; k < n; k++) { h[k] = break_cell[k]; h[n + k] = break_cum[k]; }
-    for (size_t d = 0; d < H; d++) h[2 * n + d] = digest_lookup0[d] - origin_lookups - digest_entry0[d];
+    for (size_t k = 0; k < n; k++) { h[k] = l.break_cell[k]; h[n + k] = l.break_cum[k]; }
+    for (size_t d = 0; d < H; d++) h[2 * n + d] = l.digest_lookup0[d] - l.origin_lookups - l.digest_entry0[d];
     if (d_place && h == place_host) { place_dirty = false; return HSW_OK; }   // the device already holds this table
     int device = 0;
     hsw_engine_stream(engine, nullptr, &device);
@@ -573,7 +429,7 @@ int Context::upload_place() {
     if (h.size() > place_cap) {
         void *p = nullptr;
         he = hipMalloc(&p, h.size() * sizeof(uint64_t));
-        if (he != hipSuccess) return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP;
+        if (he != hipSuccess) return hip_status(he);
         (void)hipFree(d_place);
         d_place = p;
         place_cap = h.size();
@@ -585,93 +441,107 @@ int Context::upload_place() {
     return HSW_OK;
 }
 
-uint64_t Context::lookup_cell(uint64_t entry) const {
-    if (!shared || digest_entry0.empty()) return origin_lookups + entry;
-    const size_t h = (size_t)(std::upper_bound(digest_entry0.begin(), digest_entry0.end(), entry) - digest_entry0.begin()) - 1;
-    return digest_lookup0[h] + (entry - digest_entry0[h]);
-}
-
-int Context::set_origin(uint64_t column, uint64_t row, bool zero_cell_loaded, uint64_t lookups_queued) {
-    const bool same_lookups = lookups_queued == origin_lookups;   // (d_lookup is kept)
-    if (!whole || blocks_done != 0 || gate_cursor != 0 || lookup_cursor != origin_lookups) return HSW_ERR_INVALID_ARG;
-    if (independent) return HSW_ERR_UNSUPPORTED;          // (context images: set_origin_images)
-    if (max_rows && row >= max_rows) return HSW_ERR_INVALID_ARG;
-    if (lookups_queued != origin_lookups) {
-        // the lookup-advice stream is indexed from the Context's first queued cell: [0, lookups_queued) are the caller's
-        int device = 0;
-        hsw_engine_stream(engine, nullptr, &device);
-        DeviceScope ds(device);
-        if (!ds.ok) return HSW_ERR_NO_DEVICE;
-        const size_t lbytes = (size_t)(own_lookup_capacity + lookups_queued ? own_lookup_capacity + lookups_queued : 1) * HSW_CELL_BYTES;
-        void *lk = nullptr;
-        hipError_t he = hipMalloc(&lk, lbytes);
-        if (he == hipSuccess) he = hipMemset(lk, 0, lbytes);
-        if (he != hipSuccess) { if (lk) (void)hipFree(lk); return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP; }
-        (void)hipFree(d_lookup);
-        d_lookup = lk;
-        free_compact_staging();
-    }
-    origin_column = column; origin_row = row; origin_zero_loaded = zero_cell_loaded; origin_lookups = lookups_queued;
-    // (shared context: a buffer grown for interlude entries keeps its size while it is kept)
-    if (!(shared && same_lookups && lookup_capacity > own_lookup_capacity + lookups_queued))
-        lookup_capacity = own_lookup_capacity + lookups_queued;
+int Context::set_origin(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t column, uint64_t row, bool zero_cell_loaded,
+                        uint64_t lookups_queued) {
+    if (!whole || blocks_done != 0 || gate_cursor != 0 || lookup_cursor != layout.origin_lookups) return HSW_ERR_INVALID_ARG;
+    if (independent && !context_images) return HSW_ERR_UNSUPPORTED;
+    if (layout.max_rows && row >= layout.max_rows) return HSW_ERR_INVALID_ARG;
+    // the new layout, checked in full: nothing is touched if it cannot be had.  The column breaks follow from where
+    // the stream starts: a new row, or a zero cell that comes or goes, lays the image out again (a fresh image); a
+    // shared context drops its declarations and has every cell of an earlier layout zeroed
+    Layout nl;
+    nl.origin_column = column; nl.origin_row = row; nl.origin_lookups = lookups_queued; nl.origin_zero_loaded = zero_cell_loaded;
+    const std::vector<DigestOrigin> none(declared.size());
+    const int rc = plan_layout(sizes, rc_inputs, layout.max_rows, none, &nl);
+    if (rc != HSW_OK) return rc;
+    const bool fresh_image = layout.max_rows && (row != layout.origin_row || zero_cell_loaded != layout.origin_zero_loaded);
+    const int rc2 = adopt(nl, fresh_image, lookups_queued != layout.origin_lookups, 0);
+    if (rc2 != HSW_OK) return rc2;
+    declared = none;
     lookup_cursor = lookups_queued;
-    zero_loaded = zero_cell_loaded;
-    // without the zero cell the stream is one cell shorter
+    zero_loaded = zero_cell_loaded;                       // (without the zero cell the stream is one cell shorter)
     return HSW_OK;
 }
 
-int Context::set_origin_images(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t column, uint64_t row,
-                               bool zero_cell_loaded, uint64_t lookups_queued) {
-    if (!whole || !context_images || blocks_done != 0 || gate_cursor != 0 || lookup_cursor != origin_lookups)
-        return HSW_ERR_INVALID_ARG;
-    if (max_rows && row >= max_rows) return HSW_ERR_INVALID_ARG;
-    // 1. the new layout, checked in full: nothing is touched if it cannot be had
-    std::vector<uint64_t> bc, bg;
-    const bool relayout = max_rows && (row != origin_row || zero_cell_loaded != origin_zero_loaded);
-    if (relayout) {
-        const std::vector<size_t> one(sizes.begin(), sizes.begin() + (sizes.empty() ? 0 : 1));
-        const int rc = column_breaks(shape, one, rc_inputs, max_rows, row, zero_cell_loaded, bc, bg);
-        if (rc != HSW_OK) return rc;
+// Where the launches of a batch write -- or, for hsw_gadget_verify, read: the generator and the verifier build
+// their arguments here and nowhere else, so they agree in every kind of layout.  Made once per batch (what the
+// frame launches need too), then filled in per launch.  `a`, `tbl` and `period` point at each other: not copyable.
+struct Launch {
+    const Context &c;
+    const uint8_t *in_blocks;                 // the staging the batch's inputs are in, indexed by absolute block
+    const uint32_t *in_pre;
+    uint32_t flags;
+    hsw_witness_args a{};
+    hsw_pack_plan rel{};                      // plain image, context images: the breaks relative to the launch's first cell
+    hsw_pack_plan abs{};                      // ... and as they are, for the frames (cell indices from stream cell 0)
+    const hsw_pack_plan *frame_pack = nullptr;
+    PlaceTable tbl{};                         // shared context: the jump table on the device (upload_place)
+    ContextPeriod period{0, 0};
+    const ContextPeriod *per = nullptr;       // context images: one Context's period; shared context: the table; else NULL
+
+    Launch(const Context &ctx, bool inputs_in_pinned, uint32_t repr_flags)
+        : c(ctx), in_blocks(inputs_in_pinned ? ctx.dp_blocks : ctx.d_blocks), in_pre(inputs_in_pinned ? ctx.dp_pre : ctx.d_pre_states),
+          flags(repr_flags) {
+        const Layout &l = c.layout;
+        if (c.shared && l.max_rows) {
+            const uint64_t *d_place = static_cast<const uint64_t *>(c.d_place);
+            const size_t n = l.break_cell.size();
+            tbl = PlaceTable{d_place, d_place + n, d_place + 2 * n, n, 0};
+            period.place = &tbl;
+            per = &period;
+        } else if (l.max_rows) {
+            abs.n_breaks = (uint32_t)l.break_cell.size();
+            for (size_t k = 0; k < abs.n_breaks; k++) { abs.break_cell[k] = l.break_cell[k]; abs.break_gap[k] = l.break_gap[k]; }
+            frame_pack = &abs;
+            if (l.period) { period = ContextPeriod{l.period, l.image_cells()}; per = &period; }
+        }
     }
-    // 2. the new buffers: every Context's lookup column, every Context's image (zeroed: unassigned advice cells are 0)
-    int device = 0;
-    hsw_engine_stream(engine, nullptr, &device);
-    DeviceScope ds(device);
-    if (!ds.ok) return HSW_ERR_NO_DEVICE;
-    const size_t K = init_capacity;
-    void *lk = nullptr, *img = nullptr;
-    hipError_t he = hipSuccess;
-    const size_t lcells = K * (size_t)(lookups_queued + ctx_own_lookups);
-    if (lookups_queued != origin_lookups) {
-        he = hipMalloc(&lk, (lcells ? lcells : 1) * HSW_CELL_BYTES);
-        if (he == hipSuccess) he = hipMemset(lk, 0, (lcells ? lcells : 1) * HSW_CELL_BYTES);
+    Launch(const Launch &) = delete;
+
+    // n_blocks blocks from absolute block first_block on.  The chip cursor is the running num_limb_sum; column buffers
+    // are addressed from absolute row 0 (cursor origin of the context).  Block-stream contexts: that is all
+    void blocks(size_t first_block, size_t n_blocks) {
+        const size_t cb = hsw_cell_bytes(flags);
+        a = hsw_witness_args{};
+        a.d_blocks = in_blocks + 64 * first_block; a.d_pre_states = in_pre + 8 * first_block; a.n_blocks = n_blocks;
+        a.spread_cursor0 = (uint64_t)first_block * c.shape.limb_calls_per_block;
+        const size_t row_shift = (size_t)(a.spread_cursor0 / c.shape.num_advice_columns);
+        a.d_gate = static_cast<uint8_t *>(c.d_gate) + first_block * (size_t)c.shape.gate_cells_per_block * cb;
+        a.d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + row_shift * cb;
+        a.d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + row_shift * cb;
+        a.chip_col_stride = c.chip_col_stride;
+        a.d_next_states = c.d_next_states + 8 * first_block;
+        a.flags = flags;
     }
-    const uint64_t cols = bc.size() + 1;
-    if (he == hipSuccess && relayout) {
-        he = hipMalloc(&img, K * (size_t)(cols * max_rows) * HSW_CELL_BYTES);
-        if (he == hipSuccess) he = hipMemset(img, 0, K * (size_t)(cols * max_rows) * HSW_CELL_BYTES);
+
+    // Whole-digest contexts: the block streams of n_digests equally sized digests (shape fs) as ONE launch -- the
+    // kernel skips the frame between two of them.  digest0: the first one's index in the pass, r0: its cells
+    void run(size_t digest0, const AssignedHashResult &r0, size_t first_block, size_t n_digests, const hsw_frame_shape &fs) {
+        blocks(first_block, (size_t)fs.n_blocks * n_digests);
+        const size_t cb = hsw_cell_bytes(flags);
+        const Layout &l = c.layout;
+        // (context images: the run's first block in ITS Context's image; the breaks are that Context's)
+        const uint64_t ctx0 = l.period ? r0.block_cell / l.period : 0, local = r0.block_cell - ctx0 * l.period;
+        a.d_gate = static_cast<uint8_t *>(c.gate_stream()) + (size_t)(ctx0 * l.image_cells() + local) * cb;
+        a.d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)r0.block_lookup * cb;
+        a.frame_every = fs.n_blocks;
+        // between the block streams of two digests: one epilogue, the next prologue -- and the next Context's zero cell
+        // when every digest is a Context of its own, and (context images) its caller-owned lookup cells
+        a.frame_cells = fs.epilogue_cells + fs.prologue_cells + (c.independent && !l.origin_zero_loaded ? 1u : 0u);
+        a.frame_lookups = fs.epilogue_lookups + fs.prologue_lookups + (c.context_images ? l.origin_lookups : 0u);
+        if (period.place) {                              // the run's first block cell, its digests' lookup shifts
+            tbl.base = local;
+            tbl.lk_shift = tbl.cell + 2 * tbl.n + digest0;
+        } else if (frame_pack) {                         // breaks before the launch's first cell are pure offsets
+            rel.n_breaks = abs.n_breaks;
+            for (uint32_t k = 0; k < rel.n_breaks; k++) {
+                rel.break_cell[k] = abs.break_cell[k] > local ? abs.break_cell[k] - local : 0;
+                rel.break_gap[k] = abs.break_gap[k];
+            }
+            a.pack = &rel;
+        }
     }
-    if (he != hipSuccess) {
-        if (lk) (void)hipFree(lk);
-        if (img) (void)hipFree(img);
-        return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP;
-    }
-    // 3. commit
-    if (lk) { (void)hipFree(d_lookup); d_lookup = lk; }
-    if (img) {
-        (void)hipFree(d_gate);
-        d_gate = img;
-        columns = cols;
-        set_breaks(bc, bg);
-    }
-    if (lk || img) free_compact_staging();
-    origin_column = column; origin_row = row; origin_zero_loaded = zero_cell_loaded; origin_lookups = lookups_queued;
-    lookup_capacity = K * (lookups_queued + ctx_own_lookups);
-    lookup_cursor = lookups_queued;
-    zero_loaded = zero_cell_loaded;
-    return HSW_OK;
-}
+};
 
 int Sha256DynamicConfig::digest(Context &ctx, const uint8_t *input, size_t input_len,
                                 size_t precomputed_input_len, AssignedHashResult *result) {
@@ -750,10 +620,7 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
     // (whole-digest contexts: one such launch per run of equally sized digests, each with its own frames)
     const bool small = hsw_small_eligible(ctx.engine, batch_blocks);
     const bool zero_copy = host_chain && (ctx.whole ? small : (small || batch_blocks <= 32));
-    const uint8_t *in_blocks = zero_copy ? ctx.dp_blocks : ctx.d_blocks;        // bases, indexed by absolute block
-    const uint32_t *in_pre = zero_copy ? ctx.dp_pre : ctx.d_pre_states;
-    const uint8_t *d_blk = in_blocks + 64 * b0;
-    const uint32_t *d_pre = in_pre + 8 * b0;
+    const uint8_t *d_blk = (zero_copy ? ctx.dp_blocks : ctx.d_blocks) + 64 * b0;
     uint32_t *d_next = ctx.d_next_states + 8 * b0;
     uint32_t *d_off = ctx.d_offsets;
     uint32_t *h_next = ctx.hp_next + 8 * b0;                                     // pinned: the D2H below is asynchronous
@@ -775,22 +642,13 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
             if ((he = launch_chain_var(d_blk, n, d_off, ctx.d_init_states, ctx.d_pre_states + 8 * b0, stream)) != hipSuccess) break;
         }
         const size_t G = ctx.shape.gate_cells_per_block;
-        const size_t cb = hsw_cell_bytes(ctx.repr_flags);
-        const uint32_t ncols = ctx.shape.num_advice_columns;
+        // shared context: every launch placed by the jump table (uploaded when the layout changed)
+        if (ctx.shared && ctx.layout.max_rows && (rc = ctx.upload_place()) != HSW_OK) break;
+        Launch L(ctx, zero_copy, ctx.repr_flags);
         if (!ctx.whole) {
-            // one call covers every block of the batch; the chip cursor is the running num_limb_sum.
-            // Column buffers are addressed from absolute row 0 (cursor origin of the context).
-            const uint64_t row_shift = ctx.num_limb_sum / ncols;
-            hsw_witness_args a{};
-            a.d_blocks = d_blk; a.d_pre_states = d_pre; a.n_blocks = batch_blocks;
-            a.spread_cursor0 = ctx.num_limb_sum;
-            a.d_gate = static_cast<uint8_t *>(ctx.d_gate) + b0 * G * cb;
-            a.d_chip_dense = static_cast<uint8_t *>(ctx.d_chip_dense) + (size_t)row_shift * cb;
-            a.d_chip_spread = static_cast<uint8_t *>(ctx.d_chip_spread) + (size_t)row_shift * cb;
-            a.chip_col_stride = ctx.chip_col_stride;
-            a.d_next_states = d_next;
-            a.flags = ctx.repr_flags;
-            rc = hsw_witness_blocks_impl(ctx.engine, &a, nullptr, small ? ctx.dp_next + 8 * b0 : nullptr, nullptr);
+            // one call covers every block of the batch
+            L.blocks(b0, batch_blocks);
+            rc = hsw_witness_blocks_impl(ctx.engine, &L.a, nullptr, small ? ctx.dp_next + 8 * b0 : nullptr, nullptr);
             next_in_pinned = small && rc == HSW_OK;
         } else {
             // whole-digest stream: prologue | [zero cell] | blocks | epilogue per digest (hsw_frame.hpp).
@@ -800,19 +658,8 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
             uint64_t gc = ctx.gate_cursor, lc = ctx.lookup_cursor;
             bool zero_loaded = ctx.zero_loaded;
             // every digest a Context of its own: its own zero cell unless the Contexts come with one (context images)
-            const bool own_zero = ctx.independent && !ctx.origin_zero_loaded;
-            // context images: one Context's period in the gate image and the lookup column (NULL: linear streams)
-            const ContextPeriod period{ctx.ctx_stream(), ctx.ctx_image()};
-            const ContextPeriod *per = ctx.context_images && ctx.max_rows ? &period : nullptr;
-            // shared context: every launch placed by the jump table (uploaded when the layout changed)
-            const bool table = ctx.shared && ctx.max_rows;
-            if (table && (rc = ctx.upload_place()) != HSW_OK) break;
-            const uint64_t *d_place = static_cast<const uint64_t *>(ctx.d_place);
-            const size_t n_jumps = ctx.break_cell.size();
-            PlaceTable tbl{};
-            if (table) tbl = PlaceTable{d_place, d_place + n_jumps, d_place + 2 * n_jumps, n_jumps, 0};
-            const ContextPeriod tper{0, 0, &tbl};
-            if (table) per = &tper;
+            const bool own_zero = ctx.independent && !ctx.layout.origin_zero_loaded;
+            const bool table = L.period.place != nullptr;
             frames.resize(n);
             std::vector<hsw_frame_shape> fss(n);
             size_t ob = 0;
@@ -828,8 +675,8 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 d.precomputed_round = (uint32_t)plans[i].precomputed_round;
                 d.is_input_range_check = is_input_range_check ? 1u : 0u;
                 // context images: Context h's lookup column is cells [h*Lp, (h+1)*Lp), the caller's queued cells first
-                if (ctx.context_images) lc = (uint64_t)(cur_hash_idx + i) * ctx.ctx_lookups() + ctx.origin_lookups;
-                if (table) lc = ctx.digest_lookup0[cur_hash_idx + i];   // after the caller's entries of the interlude
+                if (ctx.context_images) lc = (uint64_t)(cur_hash_idx + i) * ctx.ctx_lookups() + ctx.layout.origin_lookups;
+                if (table) lc = ctx.layout.digest_lookup0[cur_hash_idx + i];   // after the caller's entries of the interlude
                 r.prologue_cell = d.prologue_cell = gc;      gc += fss[i].prologue_cells;
                 r.prologue_lookup = d.prologue_lookup = lc;  lc += fss[i].prologue_lookups;
                 d.zero_cell = ~0ull;
@@ -846,77 +693,27 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
             for (size_t i = 0; i < n && rc == HSW_OK;) {
                 size_t j = i + 1;                            // run [i, j) of equally sized digests
                 while (j < n && frames[j].n_blocks == frames[i].n_blocks) j++;
-                const size_t nb = frames[i].n_blocks, run_blocks = nb * (j - i);
-                const uint64_t cursor = ctx.num_limb_sum + (uint64_t)ob * ctx.shape.limb_calls_per_block;
-                const uint64_t row_shift = cursor / ncols;
-                hsw_witness_args a{};
-                a.d_blocks = d_blk + 64 * ob;
-                a.d_pre_states = d_pre + 8 * ob;
-                a.n_blocks = run_blocks;
-                a.spread_cursor0 = cursor;
-                // (context images: the run's first block in ITS Context's image; the breaks below are that Context's)
-                const uint64_t per_C = per && !table ? per->stream_cells : 0, per_S = per && !table ? per->image_cells : 0;
-                const uint64_t ctx0 = per && !table ? results[i].block_cell / per_C : 0;
-                const uint64_t local_block_cell = results[i].block_cell - ctx0 * per_C;
-                a.d_gate = static_cast<uint8_t *>(ctx.gate_stream()) + (size_t)(ctx0 * per_S + local_block_cell) * cb;
-                a.d_chip_dense = static_cast<uint8_t *>(ctx.d_chip_dense) + (size_t)row_shift * cb;
-                a.d_chip_spread = static_cast<uint8_t *>(ctx.d_chip_spread) + (size_t)row_shift * cb;
-                a.chip_col_stride = ctx.chip_col_stride;
-                a.d_next_states = d_next + 8 * ob;
-                a.d_lookup = static_cast<uint8_t *>(ctx.d_lookup) + (size_t)results[i].block_lookup * cb;
-                a.flags = ctx.repr_flags;
-                a.frame_every = nb;
-                // (between the block streams of two digests: one epilogue, the next prologue -- and the next Context's
-                //  zero cell when every digest is a Context of its own)
-                a.frame_cells = fss[i].epilogue_cells + fss[i].prologue_cells + (own_zero ? 1u : 0u);
-                // (context images: and the next Context's caller-owned lookup cells)
-                a.frame_lookups = fss[i].epilogue_lookups + fss[i].prologue_lookups + (ctx.context_images ? ctx.origin_lookups : 0u);
-                hsw_pack_plan plan{};
-                tbl.base = local_block_cell;                 // (table: the run's first block cell, its lookup shifts)
-                if (table) tbl.lk_shift = d_place + 2 * n_jumps + (cur_hash_idx + i);
-                if (ctx.max_rows && !table) {
-                    // column breaks relative to this launch's first cell; breaks before it are pure offsets
-                    const uint64_t base = local_block_cell;
-                    plan.n_breaks = (uint32_t)ctx.break_cell.size();
-                    for (size_t k = 0; k < ctx.break_cell.size(); k++) {
-                        plan.break_cell[k] = ctx.break_cell[k] > base ? ctx.break_cell[k] - base : 0;
-                        plan.break_gap[k] = ctx.break_gap[k];
-                    }
-                    a.pack = &plan;
-                }
+                L.run(cur_hash_idx + i, results[i], b0 + ob, j - i, fss[i]);
                 if (small) {
                     hsw_digests_args da{};
-                    da.blocks = a;
+                    da.blocks = L.a;
                     da.descs = frames.data() + i; da.n_digests = j - i;      // this run's digests: frames in the same launch
-                    da.d_blocks0 = in_blocks; da.d_pre_states0 = in_pre; da.d_next_states0 = ctx.d_next_states;
+                    da.d_blocks0 = L.in_blocks; da.d_pre_states0 = L.in_pre; da.d_next_states0 = ctx.d_next_states;
                     da.d_gate0 = ctx.gate_stream(); da.d_lookup0 = ctx.d_lookup;
-                    hsw_pack_plan abs_plan{};
-                    abs_plan.n_breaks = table ? 0u : (uint32_t)ctx.break_cell.size();
-                    for (size_t k = 0; k < abs_plan.n_breaks; k++) {
-                        abs_plan.break_cell[k] = ctx.break_cell[k];
-                        abs_plan.break_gap[k] = ctx.break_gap[k];
-                    }
-                    da.frame_pack = ctx.max_rows && !table ? &abs_plan : nullptr;
+                    da.frame_pack = L.frame_pack;
                     da.host_next_states = h_next + 8 * ob;
                     // (the device alias of the context's own pinned staging: no runtime lookup per call)
-                    rc = hsw_witness_digests_impl(ctx.engine, &da, ctx.dp_next + 8 * (b0 + ob), per);
+                    rc = hsw_witness_digests_impl(ctx.engine, &da, ctx.dp_next + 8 * (b0 + ob), L.per);
                     next_in_pinned = rc == HSW_OK;
                 } else {
-                    rc = hsw_witness_blocks_impl(ctx.engine, &a, nullptr, nullptr, per);
+                    rc = hsw_witness_blocks_impl(ctx.engine, &L.a, nullptr, nullptr, L.per);
                 }
-                ob += run_blocks;
+                ob += L.a.n_blocks;
                 i = j;
             }
-            if (rc == HSW_OK && !small) {
-                hsw_pack_plan plan{};
-                plan.n_breaks = table ? 0u : (uint32_t)ctx.break_cell.size();
-                for (size_t k = 0; k < plan.n_breaks; k++) {
-                    plan.break_cell[k] = ctx.break_cell[k];
-                    plan.break_gap[k] = ctx.break_gap[k];
-                }
-                rc = hsw_witness_frames_impl(ctx.engine, frames.data(), n, in_blocks, in_pre, ctx.d_next_states,
-                                             ctx.gate_stream(), ctx.d_lookup, ctx.max_rows && !table ? &plan : nullptr, ctx.repr_flags, per);
-            }
+            if (rc == HSW_OK && !small)
+                rc = hsw_witness_frames_impl(ctx.engine, frames.data(), n, L.in_blocks, L.in_pre, ctx.d_next_states,
+                                             ctx.gate_stream(), ctx.d_lookup, L.frame_pack, ctx.repr_flags, L.per);
             if (rc == HSW_OK) { new_gate_cursor = gc; new_lookup_cursor = lc; }
         }
         if (rc != HSW_OK) break;
@@ -925,7 +722,7 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
         he = hipStreamSynchronize(stream);
     } while (0);
     if (rc != HSW_OK) return rc;
-    if (he != hipSuccess) return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP;
+    if (he != hipSuccess) return hip_status(he);
 
     // ---- results: the "select state #target_round" rule (lib.rs:294-310) ----
     off = 0;
@@ -1075,12 +872,12 @@ int hsw_gadget_streams(hsw_gadget *g, hsw_gadget_view *view) try {
     view->d_lookup = g->ctx->d_lookup;
     view->lookup_cells = g->ctx->lookup_cursor;
     view->lookup_capacity = g->ctx->lookup_capacity;
-    view->max_rows = g->ctx->max_rows;
-    view->columns = g->ctx->columns;
-    view->origin_column = g->ctx->origin_column;
-    view->origin_row = g->ctx->origin_row;
-    view->origin_lookups = g->ctx->origin_lookups;
-    view->origin_zero_loaded = g->ctx->origin_zero_loaded ? 1u : 0u;
+    view->max_rows = g->ctx->layout.max_rows;
+    view->columns = g->ctx->layout.columns;
+    view->origin_column = g->ctx->layout.origin_column;
+    view->origin_row = g->ctx->layout.origin_row;
+    view->origin_lookups = g->ctx->layout.origin_lookups;
+    view->origin_zero_loaded = g->ctx->layout.origin_zero_loaded ? 1u : 0u;
     view->reserved_ = 0;
     return HSW_OK;
 } HSW_NO_UNWIND
@@ -1104,14 +901,14 @@ int hsw_gadget_result_cells(const hsw_gadget *g, size_t hash_idx, hsw_result_cel
     out->input_len_cell = r.prologue_cell + hsw::frame::P_LEN;
     out->input_bytes_cell0 = r.prologue_cell + hsw::frame::P_BYTES;
     out->n_input_bytes = (uint64_t)r.n_blocks * 64;
-    g->ctx->position(out->input_len_cell, &out->input_len_pos[0], &out->input_len_pos[1]);
-    g->ctx->position(out->input_bytes_cell0, &out->input_bytes_pos0[0], &out->input_bytes_pos0[1]);
+    g->ctx->layout.position(out->input_len_cell, &out->input_len_pos[0], &out->input_len_pos[1]);
+    g->ctx->layout.position(out->input_bytes_cell0, &out->input_bytes_pos0[0], &out->input_bytes_pos0[1]);
     for (uint32_t w = 0; w < 8; w++)
         for (uint32_t i = 0; i < 4; i++) {
             const uint64_t cell = r.epilogue_cell + (uint64_t)hsw::frame::E_STATE * (r.n_blocks + 1) +
                                   (uint64_t)hsw::frame::E_WORD * w + 5u * i;
             out->output_byte_cells[4 * w + i] = cell;
-            g->ctx->position(cell, &out->output_byte_pos[4 * w + i][0], &out->output_byte_pos[4 * w + i][1]);
+            g->ctx->layout.position(cell, &out->output_byte_pos[4 * w + i][0], &out->output_byte_pos[4 * w + i][1]);
         }
     return HSW_OK;
 } HSW_NO_UNWIND
@@ -1120,7 +917,7 @@ int hsw_gadget_set_columns(hsw_gadget *g, uint64_t max_rows, uint64_t *n_columns
     if (!g) return HSW_ERR_INVALID_ARG;
     int rc = hsw_engine_synchronize(g->ctx->engine);          // the image is reallocated: nothing may still write the old one
     if (rc == HSW_OK) rc = g->ctx->set_columns(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, max_rows);
-    if (rc == HSW_OK && n_columns) *n_columns = g->ctx->columns;
+    if (rc == HSW_OK && n_columns) *n_columns = g->ctx->layout.columns;
     if (rc == HSW_OK) hsw::drop_region_tape_positions(g->tape);     // the codes are per stream cell; image positions follow the layout
     return rc;
 } HSW_NO_UNWIND
@@ -1132,31 +929,16 @@ int hsw_gadget_set_origin(hsw_gadget *g, uint64_t column, uint64_t row, int zero
     if (!c.whole || g->cfg.cur_hash_idx != 0) return HSW_ERR_INVALID_ARG;   // before the first digest of a synthesis pass
     int rc = hsw_engine_synchronize(c.engine);
     if (rc != HSW_OK) return rc;
-    const uint64_t old[4] = {c.origin_column, c.origin_row, c.origin_zero_loaded ? 1u : 0u, c.origin_lookups};
-    if (c.context_images) {
-        // every Context alike; the whole new layout is checked before anything is freed or reallocated
-        rc = c.set_origin_images(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, column, row,
-                                 zero_cell_loaded != 0, lookups_already_queued);
-        if (rc != HSW_OK) return rc;
-        if (old[2] != (zero_cell_loaded ? 1u : 0u)) { hsw::free_region_tape(g->tape); g->tape = nullptr; }
-        else if (old[1] != row) hsw::drop_region_tape_positions(g->tape);
-        return HSW_OK;
-    }
-    rc = c.set_origin(column, row, zero_cell_loaded != 0, lookups_already_queued);
-    if (rc != HSW_OK) return rc;
+    const uint64_t old_row = c.layout.origin_row;
+    const bool old_zero = c.layout.origin_zero_loaded;
+    rc = c.set_origin(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, column, row, zero_cell_loaded != 0,
+                      lookups_already_queued);
+    if (rc != HSW_OK) return rc;                                  // (nothing was touched: origin, layout and tape as before)
     // the region tape (hsw_replay.cpp) numbers stream cells: only a zero cell that comes or goes changes it; a new
     // origin row moves the witnesses' image positions; column and queued lookups are offsets applied at delivery.
     // A prover that synthesizes the same circuit pass after pass keeps its tape.
-    if (old[2] != (zero_cell_loaded ? 1u : 0u)) { hsw::free_region_tape(g->tape); g->tape = nullptr; }
-    else if (old[1] != row) hsw::drop_region_tape_positions(g->tape);
-    if (c.max_rows && (c.shared || old[1] != row || old[2] != (zero_cell_loaded ? 1u : 0u))) {
-        // the column breaks follow from where the stream starts: lay the image out again
-        rc = c.set_columns(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, c.max_rows);
-        if (rc != HSW_OK) {                                      // e.g. one column too many now: keep the old layout
-            (void)c.set_origin(old[0], old[1], old[2] != 0, old[3]);
-            return rc;
-        }
-    }
+    if (old_zero != (zero_cell_loaded != 0)) { hsw::free_region_tape(g->tape); g->tape = nullptr; }
+    else if (old_row != row) hsw::drop_region_tape_positions(g->tape);
     return HSW_OK;
 } HSW_NO_UNWIND
 
@@ -1164,21 +946,23 @@ int hsw_gadget_set_digest_origin(hsw_gadget *g, size_t h, uint64_t column, uint6
     if (!g) return HSW_ERR_INVALID_ARG;
     hsw::Context &c = *g->ctx;
     const size_t n = g->cfg.max_variable_byte_sizes.size();
-    if (!c.shared || !c.max_rows || h < 1 || h >= n || h < g->cfg.cur_hash_idx || row >= c.max_rows)
+    if (!c.shared || !c.layout.max_rows || h < 1 || h >= n || h < g->cfg.cur_hash_idx || row >= c.layout.max_rows)
         return HSW_ERR_INVALID_ARG;
-    const hsw::Context::DigestOrigin &was = c.declared[h];
+    const hsw::DigestOrigin &was = c.declared[h];
     // the same declaration again (the next pass declaring what the last one did) changes nothing: the later digests'
     // layout depends on it only, so their declarations stay too
     if (was.set && was.column == column && was.row == row && was.lookups == lookups_queued) return HSW_OK;
     // digest h's declaration replaces the old one and drops the later ones (their layout follows from it)
-    std::vector<hsw::Context::DigestOrigin> decl(c.declared.begin(), c.declared.begin() + (ptrdiff_t)h);
+    std::vector<hsw::DigestOrigin> decl(c.declared.begin(), c.declared.begin() + (ptrdiff_t)h);
     decl.resize(n);
     decl[h].set = true; decl[h].column = column; decl[h].row = row; decl[h].lookups = lookups_queued;
     int rc = hsw_engine_synchronize(c.engine);           // the image may grow: nothing may still write the old one
     if (rc != HSW_OK) return rc;
     // (cells past digest h-1's end: the same in both layouts up to there, stale beyond it if the layout changes)
-    const uint64_t clear_from = c.image_cell(c.digest_cell0[h] - 1) + 1;
-    rc = c.shared_relayout(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, c.max_rows, decl, clear_from);
+    const uint64_t clear_from = c.layout.image_cell(c.layout.digest_cell0[h] - 1) + 1;
+    hsw::Layout nl = c.layout.origin();
+    rc = c.plan_layout(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, c.layout.max_rows, decl, &nl);
+    if (rc == HSW_OK) rc = c.adopt(nl, false, false, clear_from);
     if (rc != HSW_OK) return rc;
     c.declared.swap(decl);
     hsw::drop_region_tape_positions(g->tape);           // the witnesses' image positions follow the layout
@@ -1193,8 +977,8 @@ int hsw_gadget_reset(hsw_gadget *g) try {
     c.blocks_done = 0;
     c.num_limb_sum = 0;                 // spread.rs:70-71
     c.gate_cursor = 0;
-    c.lookup_cursor = c.origin_lookups; // the Context as the caller hands it over (hsw_gadget_set_origin)
-    c.zero_loaded = c.origin_zero_loaded;
+    c.lookup_cursor = c.layout.origin_lookups; // the Context as the caller hands it over (hsw_gadget_set_origin)
+    c.zero_loaded = c.layout.origin_zero_loaded;
     c.batches.clear();
     g->cfg.cur_hash_idx = 0;            // lib.rs:66
     g->results.clear();
@@ -1289,55 +1073,36 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
             he = hipMemcpyAsync(static_cast<uint8_t *>(h) + cell0 * cb, static_cast<const uint8_t *>(d) + cell0 * cb,
                                 cells * cb, hipMemcpyDeviceToHost, stream);
     };
-    if (dst->gate && c.context_images && c.max_rows) {
-        // K images back to back, host layout = device layout: used rows of every assigned Context's columns
-        const uint64_t C = c.ctx_stream(), S = c.ctx_image();
-        uint64_t last_col = 0, last_row = 0;
-        c.position(C - 1, &last_col, &last_row);
-        last_row += 1;
-        last_col -= c.origin_column;
-        for (uint64_t h = 0; h < g->cfg.cur_hash_idx; h++)
-            for (uint64_t k = 0; k <= last_col; k++) {
-                const uint64_t used = k < last_col ? c.max_rows - c.break_gap[k] : last_row;
-                const uint64_t first = k == 0 ? c.origin_row : 0;    // rows above the origin are the caller's
-                if (used > first) copy(dst->gate, c.d_gate, (size_t)(h * S + k * c.max_rows + first), (size_t)(used - first));
+    if (dst->gate && c.whole && c.layout.max_rows) {
+        // the runs of the stream between two jumps up to the cursor, for every assigned Context (one, unless context
+        // images: K images back to back, host layout = device layout).  Rows above the origin, the gaps at column ends
+        // and the interludes' cells are the caller's or nobody's: never touched
+        const hsw::Layout &l = c.layout;
+        const uint64_t end = l.period ? l.period : c.gate_cursor, K = l.period ? g->cfg.cur_hash_idx : 1;
+        for (uint64_t h = 0; h < K; h++) {
+            uint64_t lo = 0;
+            for (size_t k = 0; k <= l.break_cell.size() && lo < end; k++) {
+                const uint64_t hi = k < l.break_cell.size() && l.break_cell[k] < end ? l.break_cell[k] : end;
+                if (hi > lo) copy(dst->gate, c.d_gate, (size_t)l.image_cell(h * l.period + lo), (size_t)(hi - lo));
+                lo = hi > lo ? hi : lo;
             }
-    } else if (dst->gate && c.shared && c.max_rows) {
-        // shared context: the stream in its runs between jumps -- the interludes' cells are the caller's, never touched
-        uint64_t lo = 0;
-        for (size_t k = 0; k <= c.break_cell.size() && lo < c.gate_cursor; k++) {
-            const uint64_t hi = k < c.break_cell.size() && c.break_cell[k] < c.gate_cursor ? c.break_cell[k] : c.gate_cursor;
-            if (hi > lo) copy(dst->gate, c.d_gate, (size_t)c.image_cell(lo), (size_t)(hi - lo));
-            lo = hi > lo ? hi : lo;
         }
     } else if (dst->gate) {
-        if (c.whole && c.max_rows) {
-            // used rows of column k: up to its break (max_rows - gap), the last column up to the cursor
-            uint64_t last_col = 0, last_row = 0;
-            if (c.gate_cursor) { c.position(c.gate_cursor - 1, &last_col, &last_row); last_row += 1; }
-            last_col -= c.origin_column;                              // image column
-            for (uint64_t k = 0; k <= last_col && c.gate_cursor; k++) {
-                const uint64_t used = k < last_col ? c.max_rows - c.break_gap[k] : last_row;
-                const uint64_t first = k == 0 ? c.origin_row : 0;    // rows above the origin are the caller's
-                if (used > first) copy(dst->gate, c.d_gate, (size_t)(k * c.max_rows + first), (size_t)(used - first));
-            }
-        } else {
-            const size_t cells = c.whole ? (size_t)c.gate_cursor : c.blocks_done * (size_t)c.shape.gate_cells_per_block;
-            copy(dst->gate, c.d_gate, 0, cells);
-        }
+        const size_t cells = c.whole ? (size_t)c.gate_cursor : c.blocks_done * (size_t)c.shape.gate_cells_per_block;
+        copy(dst->gate, c.d_gate, 0, cells);
     }
     if (dst->lookup && c.d_lookup && c.context_images) {
         const uint64_t Lp = c.ctx_lookups();               // Context h: its own entries after the caller's queued cells
         for (uint64_t h = 0; h < g->cfg.cur_hash_idx; h++)
-            copy(dst->lookup, c.d_lookup, (size_t)(h * Lp + c.origin_lookups), (size_t)c.ctx_own_lookups);
-    } else if (dst->lookup && c.d_lookup && c.shared && !c.digest_lookup0.empty()) {
+            copy(dst->lookup, c.d_lookup, (size_t)(h * Lp + c.layout.origin_lookups), (size_t)c.ctx_own_lookups);
+    } else if (dst->lookup && c.d_lookup && c.shared && !c.layout.digest_lookup0.empty()) {
         for (size_t h = 0; h < g->cfg.cur_hash_idx; h++) {     // every digest's own entries; the interludes' are the caller's
-            const uint64_t end = h + 1 < c.digest_entry0.size() ? c.digest_entry0[h + 1]
+            const uint64_t end = h + 1 < c.layout.digest_entry0.size() ? c.layout.digest_entry0[h + 1]
                                                                : c.own_lookup_capacity;
-            copy(dst->lookup, c.d_lookup, (size_t)c.digest_lookup0[h], (size_t)(end - c.digest_entry0[h]));
+            copy(dst->lookup, c.d_lookup, (size_t)c.layout.digest_lookup0[h], (size_t)(end - c.layout.digest_entry0[h]));
         }
     } else if (dst->lookup && c.d_lookup) {
-        copy(dst->lookup, c.d_lookup, (size_t)c.origin_lookups, (size_t)(c.lookup_cursor - c.origin_lookups));
+        copy(dst->lookup, c.d_lookup, (size_t)c.layout.origin_lookups, (size_t)(c.lookup_cursor - c.layout.origin_lookups));
     }
     const uint32_t ncols = c.shape.num_advice_columns;
     const size_t rows = (size_t)((c.num_limb_sum + ncols - 1) / ncols);
@@ -1354,7 +1119,7 @@ int hsw_gadget_download_region_compact(hsw_gadget *g, hsw_region_compact *dst) t
     hsw::Context &c = *g->ctx;
     if (c.repr_flags != HSW_REPR_CANONICAL) return HSW_ERR_UNSUPPORTED;      // packs canonical 32-byte cells
     if (c.context_images) return HSW_ERR_UNSUPPORTED;                         // one image per Context: not packed here
-    if (c.shared && c.max_rows) return HSW_ERR_UNSUPPORTED;                   // shared context: interludes are the caller's
+    if (c.shared && c.layout.max_rows) return HSW_ERR_UNSUPPORTED;                   // shared context: interludes are the caller's
     if (!dst->wide && dst->wide_cap) return HSW_ERR_INVALID_ARG;
     hipStream_t stream = nullptr;
     int device = 0;
@@ -1363,7 +1128,7 @@ int hsw_gadget_download_region_compact(hsw_gadget *g, hsw_region_compact *dst) t
     if (!ds.ok) return HSW_ERR_NO_DEVICE;
     const uint32_t ncols = c.shape.num_advice_columns;
     const size_t chip_cells = (size_t)ncols * (c.chip_col_stride ? c.chip_col_stride : 1);
-    const size_t gate_cells = c.whole ? (c.max_rows ? (size_t)(c.max_rows * (c.break_cell.size() + 1)) : (size_t)c.gate_capacity)
+    const size_t gate_cells = c.whole ? (c.layout.max_rows ? (size_t)(c.layout.max_rows * (c.layout.break_cell.size() + 1)) : (size_t)c.gate_capacity)
                                       : c.capacity_blocks * (size_t)c.shape.gate_cells_per_block;
     hipError_t he = hipSuccess;
     if (!c.d_wide) {        // first use (or the geometry changed: set_columns / set_origin drop the staging):
@@ -1377,7 +1142,7 @@ int hsw_gadget_download_region_compact(hsw_gadget *g, hsw_region_compact *dst) t
         if (he == hipSuccess) he = hipMalloc((void **)&c.d_wide_count, sizeof(uint32_t));
         if (he == hipSuccess) he = hipHostMalloc((void **)&c.hp_wide_count, sizeof(uint32_t), hipHostMallocDefault);
         if (he == hipSuccess) he = hipMalloc(&c.d_wide, c.wide_cap * 48);
-        if (he != hipSuccess) { c.free_compact_staging(); return he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP; }
+        if (he != hipSuccess) { c.free_compact_staging(); return hsw::hip_status(he); }
     }
     he = hipMemsetAsync(c.d_wide_count, 0, sizeof(uint32_t), stream);
     auto pack = [&](uint64_t *h, void *d8, const void *d32, uint64_t sid, size_t cell0, size_t cells) {
@@ -1387,21 +1152,21 @@ int hsw_gadget_download_region_compact(hsw_gadget *g, hsw_region_compact *dst) t
         if (he == hipSuccess)
             he = hipMemcpyAsync(h + cell0, static_cast<uint8_t *>(d8) + cell0 * 8, cells * 8, hipMemcpyDeviceToHost, stream);
     };
-    if (c.whole && c.max_rows) {
+    if (c.whole && c.layout.max_rows) {
         // ONE pass over the image from (column 0, row 0) to the last assigned cell: the few unassigned rows at
         // the end of every column are zero on the device and travel as zeros (a launch and a copy per column
         // would cost more than the bytes they save)
         uint64_t last_col = 0, last_row = 0;
-        if (c.gate_cursor) { c.position(c.gate_cursor - 1, &last_col, &last_row); last_row += 1; last_col -= c.origin_column; }
+        if (c.gate_cursor) { c.layout.position(c.gate_cursor - 1, &last_col, &last_row); last_row += 1; last_col -= c.layout.origin_column; }
         // (from the origin row on: the rows above it in image column 0 are the caller's cells)
-        pack(dst->gate, c.d_c_gate, c.d_gate, HSW_STREAM_GATE, (size_t)c.origin_row,
-             c.gate_cursor ? (size_t)(last_col * c.max_rows + last_row - c.origin_row) : 0);
+        pack(dst->gate, c.d_c_gate, c.d_gate, HSW_STREAM_GATE, (size_t)c.layout.origin_row,
+             c.gate_cursor ? (size_t)(last_col * c.layout.max_rows + last_row - c.layout.origin_row) : 0);
     } else {
         pack(dst->gate, c.d_c_gate, c.d_gate, HSW_STREAM_GATE, 0,
              c.whole ? (size_t)c.gate_cursor : c.blocks_done * (size_t)c.shape.gate_cells_per_block);
     }
     if (c.d_lookup)
-        pack(dst->lookup, c.d_c_lookup, c.d_lookup, HSW_STREAM_LOOKUP, (size_t)c.origin_lookups, (size_t)(c.lookup_cursor - c.origin_lookups));
+        pack(dst->lookup, c.d_c_lookup, c.d_lookup, HSW_STREAM_LOOKUP, (size_t)c.layout.origin_lookups, (size_t)(c.lookup_cursor - c.layout.origin_lookups));
     const size_t rows = (size_t)((c.num_limb_sum + ncols - 1) / ncols);
     if (rows == c.chip_col_stride) {         // every column full: one pass per family
         pack(dst->chip_dense, c.d_c_dense, c.d_chip_dense, HSW_STREAM_CHIP_DENSE, 0, rows * ncols);
@@ -1445,7 +1210,7 @@ int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx) try {
     if (rc != HSW_OK) return rc;
     hsw::Context &c = *g->ctx;
     size_t blocks = 0;
-    uint64_t gate = 0, lookup = c.origin_lookups;
+    uint64_t gate = 0, lookup = c.layout.origin_lookups;
     for (size_t h = 0; h < hash_idx; h++) {
         const size_t b = g->cfg.max_variable_byte_sizes[h];
         blocks += b / 64;
@@ -1453,7 +1218,7 @@ int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx) try {
             hsw_frame_shape fs;
             rc = hsw_frame_query(&c.shape, b, g->cfg.is_input_range_check ? 1 : 0, &fs);
             if (rc != HSW_OK) return rc;
-            gate += fs.digest_cells + (c.independent || (h == 0 && !c.origin_zero_loaded) ? 1 : 0);   // + the Context's zero cell, loaded by digest #0
+            gate += fs.digest_cells + (c.independent || (h == 0 && !c.layout.origin_zero_loaded) ? 1 : 0);   // + the Context's zero cell, loaded by digest #0
             lookup += fs.digest_lookups;
         }
     }
@@ -1461,7 +1226,7 @@ int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx) try {
     c.num_limb_sum = (uint64_t)blocks * c.shape.limb_calls_per_block;       // spread.rs:228-231
     c.gate_cursor = gate;
     c.lookup_cursor = lookup;
-    c.zero_loaded = c.origin_zero_loaded || hash_idx > 0;
+    c.zero_loaded = c.layout.origin_zero_loaded || hash_idx > 0;
     g->cfg.cur_hash_idx = hash_idx;
     c.batches.clear();
     g->results.clear();
@@ -1475,109 +1240,54 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
     hsw::Context &c = *g->ctx;
     if (c.repr_flags & HSW_REPR_COMPACT64) return HSW_ERR_UNSUPPORTED;         // 32-byte cells only
     // shared context: every launch checks through the jump table (the layout of the digests so far is final)
-    const bool table = c.shared && c.max_rows;
-    if (table) {
+    if (c.shared && c.layout.max_rows) {
         const int rc0 = c.upload_place();
         if (rc0 != HSW_OK) return rc0;
     }
-    const uint64_t *d_place = static_cast<const uint64_t *>(c.d_place);
-    const size_t n_jumps = c.break_cell.size();
-    hsw::PlaceTable tbl{};
-    if (table) tbl = hsw::PlaceTable{d_place, d_place + n_jumps, d_place + 2 * n_jumps, n_jumps, 0};
-    const hsw::ContextPeriod tper{0, 0, &tbl};
-    const size_t G = c.shape.gate_cells_per_block, cb = HSW_CELL_BYTES;
-    const uint32_t ncols = c.shape.num_advice_columns;
     auto merge = [&](const hsw_verify_report &r) {
         if (r.violations && !report->violations) {
             report->first_block = r.first_block; report->first_cell = r.first_cell; report->first_class = r.first_class;
         }
         report->violations += r.violations; report->checks += r.checks; report->kernel_ms += r.kernel_ms;
     };
-    hsw_pack_plan abs_plan{};
-    abs_plan.n_breaks = table ? 0u : (uint32_t)c.break_cell.size();
-    for (size_t k = 0; k < abs_plan.n_breaks; k++) { abs_plan.break_cell[k] = c.break_cell[k]; abs_plan.break_gap[k] = c.break_gap[k]; }
-    const bool own_zero = c.independent && !c.origin_zero_loaded;
-    const hsw::ContextPeriod period{c.ctx_stream(), c.ctx_image()};
-    const hsw::ContextPeriod *per = c.context_images && c.max_rows ? &period : nullptr;
-    const uint64_t per_C = per ? period.stream_cells : 0, per_S = per ? period.image_cells : 0;
-    const hsw::ContextPeriod *vper = table ? &tper : per;
     for (const hsw::Context::BatchRecord &b : c.batches) {
-        const uint8_t *in_blocks = b.inputs_in_pinned ? c.dp_blocks : c.d_blocks;
-        const uint32_t *in_pre = b.inputs_in_pinned ? c.dp_pre : c.d_pre_states;
+        hsw::Launch L(c, b.inputs_in_pinned, b.repr_flags);
+        hsw_verify_report r;
         if (!c.whole) {
-            hsw_witness_args a{};
-            a.d_blocks = in_blocks + 64 * b.first_block; a.d_pre_states = in_pre + 8 * b.first_block; a.n_blocks = b.n_blocks;
-            a.spread_cursor0 = (uint64_t)b.first_block * c.shape.limb_calls_per_block;
-            const uint64_t row_shift = a.spread_cursor0 / ncols;
-            a.d_gate = static_cast<uint8_t *>(c.d_gate) + b.first_block * G * cb;
-            a.d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + (size_t)row_shift * cb;
-            a.d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + (size_t)row_shift * cb;
-            a.chip_col_stride = c.chip_col_stride;
-            a.d_next_states = c.d_next_states + 8 * b.first_block;
-            a.flags = b.repr_flags;
-            hsw_verify_report r;
-            const int rc = hsw_verify_blocks(c.engine, &a, &r);
+            L.blocks(b.first_block, b.n_blocks);
+            const int rc = hsw_verify_blocks(c.engine, &L.a, &r);
             if (rc != HSW_OK) return rc;
             merge(r);
             continue;
         }
-        size_t ob = 0;
+        size_t fb = b.first_block;
         for (size_t i = 0; i < b.n_digests;) {                       // runs of equally sized digests, as generated
             const hsw::AssignedHashResult &r0 = g->results[b.first_digest + i];
             size_t j = i + 1;
             while (j < b.n_digests && g->results[b.first_digest + j].n_blocks == r0.n_blocks) j++;
-            const size_t nb = r0.n_blocks, run_blocks = nb * (j - i), fb = b.first_block + ob;
             hsw_frame_shape fs;
-            int rc = hsw_frame_query(&c.shape, nb * 64, g->cfg.is_input_range_check ? 1 : 0, &fs);
+            int rc = hsw_frame_query(&c.shape, r0.n_blocks * 64, g->cfg.is_input_range_check ? 1 : 0, &fs);
             if (rc != HSW_OK) return rc;
-            hsw_witness_args a{};
-            a.d_blocks = in_blocks + 64 * fb; a.d_pre_states = in_pre + 8 * fb; a.n_blocks = run_blocks;
-            a.spread_cursor0 = (uint64_t)fb * c.shape.limb_calls_per_block;
-            const uint64_t row_shift = a.spread_cursor0 / ncols;
-            const uint64_t ctx0 = per ? r0.block_cell / per_C : 0, local_block_cell = r0.block_cell - ctx0 * per_C;
-            a.d_gate = static_cast<uint8_t *>(c.gate_stream()) + (size_t)(ctx0 * per_S + local_block_cell) * cb;
-            a.d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + (size_t)row_shift * cb;
-            a.d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + (size_t)row_shift * cb;
-            a.chip_col_stride = c.chip_col_stride;
-            a.d_next_states = c.d_next_states + 8 * fb;
-            a.d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)r0.block_lookup * cb;
-            a.frame_every = nb; a.frame_cells = fs.epilogue_cells + fs.prologue_cells + (own_zero ? 1u : 0u);
-            a.frame_lookups = fs.epilogue_lookups + fs.prologue_lookups + (c.context_images ? c.origin_lookups : 0u);
-            a.flags = b.repr_flags;
-            hsw_pack_plan rel{};
-            if (table) {
-                tbl.base = local_block_cell;
-                tbl.lk_shift = d_place + 2 * n_jumps + (b.first_digest + i);
-            } else if (c.max_rows) {
-                rel.n_breaks = abs_plan.n_breaks;
-                for (uint32_t k = 0; k < rel.n_breaks; k++) {
-                    rel.break_cell[k] = abs_plan.break_cell[k] > local_block_cell ? abs_plan.break_cell[k] - local_block_cell : 0;
-                    rel.break_gap[k] = abs_plan.break_gap[k];
-                }
-                a.pack = &rel;
-            }
-            hsw_verify_report r;
-            rc = hsw_verify_blocks_impl(c.engine, &a, &r, vper);
+            L.run(b.first_digest + i, r0, fb, j - i, fs);
+            rc = hsw_verify_blocks_impl(c.engine, &L.a, &r, L.per);
             if (rc != HSW_OK) return rc;
             merge(r);
             std::vector<hsw_frame_desc> descs(j - i);
-            size_t blk = fb;
             for (size_t k = i; k < j; k++) {
                 const hsw::AssignedHashResult &rk = g->results[b.first_digest + k];
                 hsw_frame_desc &d = descs[k - i];
-                d.input_len = rk.input_len; d.first_block = blk; d.n_blocks = (uint32_t)rk.n_blocks;
+                d.input_len = rk.input_len; d.first_block = fb; d.n_blocks = (uint32_t)rk.n_blocks;
                 d.num_round = (uint32_t)rk.num_round; d.precomputed_round = (uint32_t)(rk.num_round - rk.target_round);
                 d.is_input_range_check = g->cfg.is_input_range_check ? 1u : 0u;
                 d.prologue_cell = rk.prologue_cell; d.epilogue_cell = rk.epilogue_cell;
                 d.prologue_lookup = rk.prologue_lookup; d.epilogue_lookup = rk.epilogue_lookup;
                 d.zero_cell = rk.block_cell == rk.prologue_cell + fs.prologue_cells + 1 ? rk.block_cell - 1 : ~0ull;
-                blk += rk.n_blocks;
+                fb += rk.n_blocks;
             }
-            rc = hsw_verify_frames_impl(c.engine, descs.data(), descs.size(), in_blocks, in_pre, c.d_next_states, c.gate_stream(),
-                                        c.d_lookup, c.max_rows && !table ? &abs_plan : nullptr, b.repr_flags, &r, vper);
+            rc = hsw_verify_frames_impl(c.engine, descs.data(), descs.size(), L.in_blocks, L.in_pre, c.d_next_states, c.gate_stream(),
+                                        c.d_lookup, L.frame_pack, b.repr_flags, &r, L.per);
             if (rc != HSW_OK) return rc;
             merge(r);
-            ob += run_blocks;
             i = j;
         }
     }
@@ -1594,13 +1304,13 @@ int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region 
     const uint64_t nb = g->cfg.max_variable_byte_sizes[h] / 64, C = c.ctx_stream();
     out->stream_cells = C;
     out->first_stream_cell = h * C;
-    out->columns = c.columns;
-    out->max_rows = c.max_rows;
-    if (c.max_rows) {
+    out->columns = c.layout.columns;
+    out->max_rows = c.layout.max_rows;
+    if (c.layout.max_rows) {
         uint64_t col = 0, row = 0;
-        c.position(C - 1, &col, &row);
+        c.layout.position(C - 1, &col, &row);
         out->last_column_rows = row + 1;
-        out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * c.ctx_image()) * cb;
+        out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * c.layout.image_cells()) * cb;
     } else {
         out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * C) * cb;   // linear: the Context's stream
     }
@@ -1611,16 +1321,16 @@ int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region 
     const size_t chip_row0 = (size_t)(h * nb * c.shape.limb_calls_per_block / ncols);
     out->d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + chip_row0 * cb;
     out->d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + chip_row0 * cb;
-    out->origin_column = c.origin_column;
-    out->origin_row = c.origin_row;
-    out->origin_lookups = c.origin_lookups;
+    out->origin_column = c.layout.origin_column;
+    out->origin_row = c.layout.origin_row;
+    out->origin_lookups = c.layout.origin_lookups;
     out->assigned = h < g->cfg.cur_hash_idx ? 1u : 0u;
     return HSW_OK;
 } HSW_NO_UNWIND
 
 int hsw_gadget_cell_position(const hsw_gadget *g, uint64_t cell, uint64_t *column, uint64_t *row) try {
     if (!g) return HSW_ERR_INVALID_ARG;
-    g->ctx->position(cell, column, row);
+    g->ctx->layout.position(cell, column, row);
     return HSW_OK;
 } HSW_NO_UNWIND
 

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/hsw.h"
+#include "hsw_gadget_layout.hpp"
 
 namespace hsw {
 
@@ -125,72 +126,52 @@ class Context {
     bool independent = false;        // HSW_GADGET_INDEPENDENT: every digest is a Context of its own (K proofs in flight)
     // HSW_GADGET_CONTEXT_IMAGES (with independent, all digests of one size): every Context has an origin, a column
     // image and a lookup column of its own, laid out alike -- Context h's image is cells [h*S, (h+1)*S) of d_gate,
-    // its lookup column cells [h*Lp, (h+1)*Lp) of d_lookup; break_cell / break_gap are ONE Context's
+    // its lookup column cells [h*Lp, (h+1)*Lp) of d_lookup; the layout's breaks are ONE Context's
     bool context_images = false;
     uint64_t ctx_digest_cells = 0, ctx_own_lookups = 0;   // one Context's digest cells (zero cell not counted) and lookups
-    uint64_t ctx_stream() const { return ctx_digest_cells + (origin_zero_loaded ? 0u : 1u); }   // C: stream cells per Context
-    uint64_t ctx_image() const { return columns * max_rows; }                                    // S (0 without an image)
-    uint64_t ctx_lookups() const { return origin_lookups + ctx_own_lookups; }                   // Lp
+    uint64_t ctx_stream() const { return ctx_digest_cells + (layout.origin_zero_loaded ? 0u : 1u); }   // C: stream cells per Context
+    uint64_t ctx_lookups() const { return layout.origin_lookups + ctx_own_lookups; }             // Lp
     bool zero_loaded = false;        // Context.zero_cell (first load_zero: compression.rs:34 of the first block)
     uint64_t gate_cursor = 0, gate_capacity = 0;       // cells
     void *d_lookup = nullptr;
     uint64_t lookup_cursor = 0, lookup_capacity = 0;
+    uint64_t own_lookup_capacity = 0;                  // the gadget's own lookup entries (all Contexts)
     // what every digest_batch call wrote, for hsw_gadget_verify
     struct BatchRecord { size_t first_digest, n_digests, first_block, n_blocks; bool inputs_in_pinned; uint32_t repr_flags; };
     std::vector<BatchRecord> batches;
-    // FlexGate column image (set_columns): d_gate is `columns` advice columns of max_rows cells;
-    // stream cell i sits at i + the gaps of all breaks at or before i (assumption A3-iii)
-    uint64_t max_rows = 0, columns = 0;
-    std::vector<uint64_t> break_cell, break_gap;
-    std::vector<uint64_t> break_cum;                   // break_cum[k] = break_gap[0..k] summed (the search in position / image_cell)
-    void set_breaks(std::vector<uint64_t> &bc, std::vector<uint64_t> &bg);   // swaps them in, rebuilds break_cum
-    uint64_t gap_at(uint64_t cell) const;              // the gaps of all breaks at or before `cell`
+    // The origin and the stream-to-image map (hsw_gadget_layout.hpp).  With an image, d_gate is layout.columns
+    // advice columns of layout.max_rows cells (context images: one such image per Context, back to back)
+    Layout layout;
     // HSW_GADGET_SHARED_CONTEXT: the same Context for every digest of the pass, the caller's own cells in between
-    // (interludes, hsw_gadget_set_digest_origin).  break_cell / break_gap are then every jump of the stream-to-image
-    // map -- column breaks and interludes -- of any number (up to HSW_GADGET_MAX_COLUMNS columns)
+    // (interludes, hsw_gadget_set_digest_origin).  The layout's jumps are then column breaks and interludes, of any
+    // number (up to HSW_GADGET_MAX_COLUMNS columns), and the kernels read them from a table on the device
     bool shared = false;
-    struct DigestOrigin { bool set = false; uint64_t column = 0, row = 0, lookups = 0; };
     std::vector<DigestOrigin> declared;                // per digest of the pass ([0] unused)
-    std::vector<uint64_t> digest_lookup0;              // per digest: d_lookup cell of its first own entry (its layout)
-    std::vector<uint64_t> digest_entry0;               // per digest: its first entry among the gadget's own lookup entries
-    std::vector<uint64_t> digest_cell0;                // per digest: its first gate-stream cell
     std::vector<uint64_t> place_host;                  // what d_place holds (an unchanged table is not uploaded again)
-    uint64_t image_columns = 0;                        // image columns allocated (>= columns)
+    uint64_t image_columns = 0;                        // shared context: image columns allocated (>= layout.columns)
     void *d_place = nullptr;                           // device copy of the jump table (hsw_kernels.h PlaceTable)
     size_t place_cap = 0;                              // uint64 words of d_place
     bool place_dirty = true;                           // the layout changed since the last upload
-    // lays the pass out again from the origin and the declarations; commits only on success (image / lookup grown).
-    // If the layout changed, image cells [clear_from, end) -- what an earlier layout may have written there -- are
-    // zeroed again (unassigned advice cells are 0); clear_from = ~0: none
-    int shared_relayout(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows, const std::vector<DigestOrigin> &decl,
-                        uint64_t clear_from);
     int upload_place();                                // d_place from the layout, if it changed
-    uint64_t lookup_cell(uint64_t entry) const;        // d_lookup cell of the gadget's own lookup entry `entry`
-    // Where the caller's halo2-base Context stood when it handed the region to the gadget (hsw_gadget_set_origin;
-    // the reference's digest takes whatever Context it is given, lib.rs:71-76,351-360): stream cell 0 lands at
-    // (origin_column, origin_row) = ctx.advice_alloc[0]; the Context may already cache its zero cell
-    // (ctx.zero_cell, A4-iii: then no digest of this gadget assigns one) and may have queued
-    // origin_lookups cells for the lookup-advice column (ctx.cells_to_lookup.len()).  With a column image,
-    // image column k is FlexGate column origin_column + k and rows [0, origin_row) of image column 0 are
-    // the caller's: never written, never delivered.
-    uint64_t origin_column = 0, origin_row = 0, origin_lookups = 0;
-    bool origin_zero_loaded = false;
-    uint64_t own_lookup_capacity = 0;                  // lookup_capacity - origin_lookups
-    int set_origin(uint64_t column, uint64_t row, bool zero_cell_loaded, uint64_t lookups_queued);
-    // context images: the same, validated in full (layout included) before anything is freed or reallocated
-    int set_origin_images(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t column, uint64_t row,
-                          bool zero_cell_loaded, uint64_t lookups_queued);
+    // The layout this context would have with columns of `rows` cells (0: none) at the origin of *out, checked
+    // against the limit of its kind (HSW_ERR_TOO_LARGE); decl: a shared context's declarations.  Touches nothing.
+    int plan_layout(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows, const std::vector<DigestOrigin> &decl,
+                    Layout *out) const;
+    // Makes `nl` the layout.  fresh_image / fresh_lookup: the image / the lookup column is replaced by a zeroed
+    // one sized for nl; a shared context's buffers grow instead, keeping what they hold, and if the map changed its
+    // image cells [clear_from, end) -- what an earlier layout may have written there -- are zeroed again (unassigned
+    // advice cells are 0).  Nothing is touched unless every allocation succeeded.
+    int adopt(Layout &nl, bool fresh_image, bool fresh_lookup, uint64_t clear_from);
+    // hsw_gadget_set_origin: validated in full (layout included) before anything is freed or reallocated
+    int set_origin(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t column, uint64_t row, bool zero_cell_loaded,
+                   uint64_t lookups_queued);
     // device address of stream cell 0 (32-byte cells: whole-digest contexts have no compact form)
     void *gate_stream() const {
-        return static_cast<uint8_t *>(d_gate) + (size_t)(max_rows ? origin_row : 0) * HSW_CELL_BYTES;
+        return static_cast<uint8_t *>(d_gate) + (size_t)(layout.max_rows ? layout.origin_row : 0) * HSW_CELL_BYTES;
     }
     // Lay the whole-digest stream out as FlexGate (Vertical) advice columns of max_rows usable rows.
     // Only before the first digest.  HSW_ERR_TOO_LARGE: more than HSW_MAX_BREAKS + 1 columns.
     int set_columns(const std::vector<size_t> &max_variable_byte_sizes, bool is_input_range_check, uint64_t max_rows);
-    // (column, row) of stream cell i (context images: inside its own Context's image)
-    void position(uint64_t cell, uint64_t *column, uint64_t *row) const;
-    // offset of stream cell i from d_gate, in cells (origin row, column breaks and, with context images, h*S included)
-    uint64_t image_cell(uint64_t cell) const;
     void free_compact_staging();                       // the 8-byte staging follows the geometry: dropped when it changes
 };
 

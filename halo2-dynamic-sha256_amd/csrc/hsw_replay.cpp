@@ -132,7 +132,7 @@ static int build_region_tape(const hsw_gadget *g, RegionTape **out) {
     const bool rc_in = g->cfg.is_input_range_check;
     uint64_t gc = 0;
     int64_t zero_abs = INT64_MIN;                       // INT64_MIN: a zero cell outside the stream (origin_zero_loaded)
-    bool zero_seen = c.origin_zero_loaded;
+    bool zero_seen = c.layout.origin_zero_loaded;
     FrameStructureBuilder fb;
     for (size_t h = 0; h < g->cfg.max_variable_byte_sizes.size(); h++) {
         const uint64_t mx = g->cfg.max_variable_byte_sizes[h], nb = mx / 64;
@@ -142,7 +142,7 @@ static int build_region_tape(const hsw_gadget *g, RegionTape **out) {
         if (!b.section(pro, g0, pro_ext)) return HSW_ERR_INVALID_ARG;
         for (int64_t src : pro.lookup_src) t->lookup_code.push_back(b.code_of(pro_ext(src)));
         gc += P;
-        if (!zero_seen || (c.independent && !c.origin_zero_loaded)) {   // this digest's Context loads its zero cell (A4-iii)
+        if (!zero_seen || (c.independent && !c.layout.origin_zero_loaded)) {   // this digest's Context loads its zero cell (A4-iii)
             zero_abs = (int64_t)gc;
             t->gate_code[(size_t)gc] = b.constant(0);
             gc += 1;
@@ -189,7 +189,7 @@ static int build_region_tape(const hsw_gadget *g, RegionTape **out) {
     }
     // (a Context that came with its zero cell leaves the one cell reserved for it unused -- one per Context when
     //  every digest is a Context of its own)
-    const uint64_t unused = c.origin_zero_loaded ? (c.independent ? (uint64_t)g->cfg.max_variable_byte_sizes.size() : 1) : 0;
+    const uint64_t unused = c.layout.origin_zero_loaded ? (c.independent ? (uint64_t)g->cfg.max_variable_byte_sizes.size() : 1) : 0;
     if (gc + unused != c.gate_capacity || t->lookup_code.size() != c.own_lookup_capacity) return HSW_ERR_INVALID_ARG;
     guard.p = nullptr;
     *out = t;
@@ -205,9 +205,9 @@ static int ensure_tape(hsw_gadget *g) {
 struct Extent { uint64_t cells, wit, lookups, limbs; };
 // Everything image_cell() depends on besides the stream cell
 static std::vector<uint64_t> layout_key(const Context &c) {
-    std::vector<uint64_t> k{c.max_rows, c.origin_row, c.context_images ? c.ctx_stream() : 0, c.ctx_image()};
-    k.insert(k.end(), c.break_cell.begin(), c.break_cell.end());
-    k.insert(k.end(), c.break_gap.begin(), c.break_gap.end());
+    std::vector<uint64_t> k{c.layout.max_rows, c.layout.origin_row, c.context_images ? c.ctx_stream() : 0, c.layout.image_cells()};
+    k.insert(k.end(), c.layout.break_cell.begin(), c.layout.break_cell.end());
+    k.insert(k.end(), c.layout.break_gap.begin(), c.layout.break_gap.end());
     return k;
 }
 
@@ -268,12 +268,12 @@ int hsw_gadget_download_region_distinct(hsw_gadget *g, void *distinct, size_t ca
     if (t.d_wit_pos && key != t.pos_layout) drop_region_tape_positions(&t);
     if (!t.d_wit_pos) {                                   // first delivery with this layout: where every witness sits in the image
         // (image positions are 32-bit: every Context's image together must stay below 2^32 cells)
-        if (c.max_rows && c.columns * c.max_rows * (c.context_images ? c.init_capacity : 1) >= (1ull << 32)) {
+        if (c.layout.max_rows && c.layout.columns * c.layout.max_rows * (c.context_images ? c.init_capacity : 1) >= (1ull << 32)) {
             if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
             return HSW_ERR_TOO_LARGE;
         }
         std::vector<uint32_t> pos(t.wit_cell.size());
-        for (size_t w = 0; w < pos.size(); w++) pos[w] = (uint32_t)c.image_cell(t.wit_cell[w]);
+        for (size_t w = 0; w < pos.size(); w++) pos[w] = (uint32_t)c.layout.image_cell(t.wit_cell[w]);
         t.device = device;
         he = hipMalloc((void **)&t.d_wit_pos, pos.size() * sizeof(uint32_t));
         if (he == hipSuccess) he = hipMalloc(&t.d_distinct, pos.size() * (size_t)HSW_CELL_BYTES);
@@ -310,29 +310,29 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
     auto gate_part = [&](uint64_t lo, uint64_t hi) {
         if (!dst->gate) return;
         Cell *img = static_cast<Cell *>(dst->gate);
-        if (c.context_images && c.max_rows) {                     // K images: every Context walks its own breaks
-            for (uint64_t i = lo; i < hi; i++) img[c.image_cell(i)] = value(t.gate_code[i]);
+        if (c.context_images && c.layout.max_rows) {                     // K images: every Context walks its own breaks
+            for (uint64_t i = lo; i < hi; i++) img[c.layout.image_cell(i)] = value(t.gate_code[i]);
             return;
         }
         size_t nb = 0;
-        uint64_t shift = c.max_rows ? c.origin_row : 0;
-        while (nb < c.break_cell.size() && c.break_cell[nb] <= lo) shift += c.break_gap[nb++];
+        uint64_t shift = c.layout.max_rows ? c.layout.origin_row : 0;
+        while (nb < c.layout.break_cell.size() && c.layout.break_cell[nb] <= lo) shift += c.layout.break_gap[nb++];
         for (uint64_t i = lo; i < hi; i++) {
-            while (nb < c.break_cell.size() && c.break_cell[nb] <= i) shift += c.break_gap[nb++];
+            while (nb < c.layout.break_cell.size() && c.layout.break_cell[nb] <= i) shift += c.layout.break_gap[nb++];
             img[i + shift] = value(t.gate_code[i]);
         }
     };
     auto lookup_part = [&](uint64_t lo, uint64_t hi) {
         if (!dst->lookup) return;
-        Cell *lk = static_cast<Cell *>(dst->lookup) + c.origin_lookups;
+        Cell *lk = static_cast<Cell *>(dst->lookup) + c.layout.origin_lookups;
         if (c.context_images) {                                   // entry j of Context h = j / own: its own lookup column
             const uint64_t own = c.ctx_own_lookups, Lp = c.ctx_lookups();
             for (uint64_t j = lo; j < hi; j++) lk[(j / own) * Lp + j % own] = value(t.lookup_code[j]);
             return;
         }
-        if (c.shared && !c.digest_entry0.empty()) {               // shared context: past the caller's entries of the interludes
+        if (c.shared && !c.layout.digest_entry0.empty()) {               // shared context: past the caller's entries of the interludes
             Cell *lk0 = static_cast<Cell *>(dst->lookup);
-            for (uint64_t j = lo; j < hi; j++) lk0[c.lookup_cell(j)] = value(t.lookup_code[j]);
+            for (uint64_t j = lo; j < hi; j++) lk0[c.layout.lookup_cell(j)] = value(t.lookup_code[j]);
             return;
         }
         for (uint64_t j = lo; j < hi; j++) lk[j] = value(t.lookup_code[j]);

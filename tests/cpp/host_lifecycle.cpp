@@ -231,10 +231,68 @@ static void pinned_pointer_validation() {
     for (void *p : {blocks, pre, next, gate, lookup, cd, cs}) CHECK(hipFree(p) == hipSuccess);
 }
 
+// hsw_gadget_set_origin validates before it commits: a new origin whose layout no longer fits HSW_MAX_BREAKS + 1
+// columns is refused with the origin, the layout, d_lookup and the region tape exactly as they were
+static void refused_origin_keeps_everything() {
+    hsw_engine *e = nullptr;
+    CHECK(hsw_engine_create_ex(0, nullptr, 8, 2, HSW_MODE_HALO2_INTERNALS, &e) == HSW_OK);
+    size_t sizes[16];
+    for (size_t &b : sizes) b = 64;
+    hsw_gadget *g = nullptr;
+    CHECK(hsw_gadget_create_ex(e, sizes, 16, 0, HSW_GADGET_WHOLE_DIGEST, &g) == HSW_OK);
+    uint64_t rows = 69348 + 16, columns = 0;                   // the smallest column height (in steps) that fits 17 columns
+    for (int rc = HSW_ERR_TOO_LARGE; rc != HSW_OK; rows += rc == HSW_OK ? 0 : 97) {
+        rc = hsw_gadget_set_columns(g, rows, &columns);
+        CHECK(rc == HSW_OK || rc == HSW_ERR_TOO_LARGE);
+    }
+    CHECK(columns == HSW_MAX_BREAKS + 1);
+    CHECK(hsw_gadget_set_origin(g, 3, 11, 0, 4) == HSW_OK);    // (still 17 columns: eleven rows further down)
+    hsw_hash_result r[16];
+    for (int h = 0; h < 16; h++) CHECK(hsw_gadget_digest(g, (const uint8_t *)"abc", 3, 0, &r[h]) == HSW_OK);
+    hsw_region_tape tape;
+    CHECK(hsw_gadget_region_tape(g, &tape) == HSW_OK && tape.gate_cells == r[15].end_cell);
+    const std::vector<uint32_t> codes(tape.gate_code, tape.gate_code + tape.gate_cells);
+    const std::vector<uint32_t> lookup_codes(tape.lookup_code, tape.lookup_code + tape.lookup_cells);
+    CHECK(hsw_gadget_reset(g) == HSW_OK);
+    hsw_gadget_view v0, v1;
+    CHECK(hsw_gadget_streams(g, &v0) == HSW_OK && v0.columns == 17 && v0.origin_lookups == 4 && v0.lookup_cells == 4);
+    const uint64_t probes[5] = {0, 1, r[0].end_cell, r[7].block_cell + 60000, r[15].end_cell - 1};
+    uint64_t at0[5][2], at1[2];
+    for (int k = 0; k < 5; k++) CHECK(hsw_gadget_cell_position(g, probes[k], &at0[k][0], &at0[k][1]) == HSW_OK);
+    CHECK(at0[0][0] == 3 && at0[0][1] == 11);
+    // from the last rows of a column the same stream needs an 18th column; other queued lookups would need another d_lookup
+    CHECK(hsw_gadget_set_origin(g, 5, rows - 2, 0, 9) == HSW_ERR_TOO_LARGE);
+    CHECK(hsw_gadget_set_origin(g, 5, rows - 2, 1, 9) == HSW_ERR_TOO_LARGE);          // (nor with the zero cell gone)
+    CHECK(hsw_gadget_streams(g, &v1) == HSW_OK && std::memcmp(&v0, &v1, sizeof v0) == 0);   // pointers, cursors, origin, layout
+    for (int k = 0; k < 5; k++) {
+        CHECK(hsw_gadget_cell_position(g, probes[k], &at1[0], &at1[1]) == HSW_OK);
+        CHECK(at1[0] == at0[k][0] && at1[1] == at0[k][1]);
+    }
+    // the tape handed out before is alive and says what it said (under ASan a freed tape is a report)
+    CHECK(std::memcmp(codes.data(), tape.gate_code, codes.size() * sizeof(uint32_t)) == 0);
+    CHECK(std::memcmp(lookup_codes.data(), tape.lookup_code, lookup_codes.size() * sizeof(uint32_t)) == 0);
+    hsw_region_tape again;
+    CHECK(hsw_gadget_region_tape(g, &again) == HSW_OK && again.gate_code == tape.gate_code && again.lookup_code == tape.lookup_code);
+    // the next pass runs at the old origin; deliveries into exact-size buffers are clean
+    for (int h = 0; h < 16; h++) {
+        hsw_hash_result rh;
+        CHECK(hsw_gadget_digest(g, (const uint8_t *)"abc", 3, 0, &rh) == HSW_OK);
+        CHECK(rh.prologue_cell == r[h].prologue_cell && rh.prologue_lookup == r[h].prologue_lookup && rh.end_cell == r[h].end_cell);
+    }
+    CHECK(hsw_gadget_streams(g, &v1) == HSW_OK && v1.lookup_cells == v1.lookup_capacity);
+    std::vector<uint64_t> gate((size_t)(v1.max_rows * v1.columns) * 4), lookup((size_t)v1.lookup_cells * 4);
+    std::vector<uint64_t> cd(2 * v1.chip_col_stride * 4), cs(2 * v1.chip_col_stride * 4);
+    hsw_region_host dst = {gate.data(), lookup.data(), cd.data(), cs.data()};
+    CHECK(hsw_gadget_download_region(g, &dst) == HSW_OK);
+    hsw_gadget_destroy(g);
+    hsw_engine_destroy(e);
+}
+
 int main() {
     block_batches();
     device_ranges();
     whole_region();
+    refused_origin_keeps_everything();
     pinned_pointer_validation();
     // everything the library allocated is gone with its engines and gadgets
     CHECK(hip_stub_live_device_allocations() == 0 && hip_stub_live_pinned_allocations() == 0 && hip_stub_live_events() == 0);

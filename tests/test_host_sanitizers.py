@@ -37,13 +37,13 @@ def _compile(hipcc, src, outdir):
 
 @pytest.fixture(scope="module")
 def host_objects(tmp_path_factory):
-    """The three host translation units of libhsw, instrumented, + the (uninstrumented) kernel objects."""
+    """The host translation units of libhsw, instrumented, + the (uninstrumented) kernel objects."""
     hipcc = _hipcc()
     kernels = [os.path.join(CSRC, f) for f in KERNEL_OBJS]
     if not all(os.path.exists(k) for k in kernels):
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j8"])
     out = str(tmp_path_factory.mktemp("san"))
-    objs = [_compile(hipcc, os.path.join(CSRC, f), out) for f in ("hsw_api.cpp", "hsw_api_region.cpp", "hsw_gadget.cpp", "hsw_replay.cpp", "hsw_devmem.cpp")]
+    objs = [_compile(hipcc, os.path.join(CSRC, f), out) for f in ("hsw_api.cpp", "hsw_api_region.cpp", "hsw_gadget.cpp", "hsw_gadget_layout.cpp", "hsw_replay.cpp", "hsw_devmem.cpp")]
     objs.append(_compile(hipcc, os.path.join(ROOT, "tests", "cpp", "hip_stub.cpp"), out))     # the only HIP runtime linked
     return hipcc, out, objs, kernels
 

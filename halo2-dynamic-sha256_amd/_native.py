@@ -70,10 +70,10 @@ class WitnessArgs(C.Structure):
 
 class LaunchInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("limbs", "tile_cells", "tile_rows", "repr", "internals", "parts", "split",
-                                          "reserved_")] + [("n_blocks", C.c_uint64), ("grid", C.c_uint64)]
+                                          "seq")] + [("n_blocks", C.c_uint64), ("grid", C.c_uint64)]
 
     def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved_"}
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
     def kernel_name(self):
         if self.split == 2:
@@ -199,7 +199,7 @@ SYMBOLS = (
     "hsw_verify_frames", "hsw_gadget_verify", "hsw_last_launch", "hsw_witness_digests",
     "hsw_gadget_download_region_compact", "hsw_region_widen", "hsw_gadget_result_cells",
     "hsw_gadget_set_origin", "hsw_gadget_region_tape", "hsw_gadget_download_region_distinct", "hsw_gadget_replay_region",
-    "hsw_gadget_context_region", "hsw_gadget_set_digest_origin",
+    "hsw_gadget_context_region", "hsw_gadget_set_digest_origin", "hsw_gadget_create_contexts",
 )
 
 
@@ -351,6 +351,9 @@ def lib():
         L.hsw_gadget_set_digest_origin.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64]
         L.hsw_gadget_context_region.restype = C.c_int
         L.hsw_gadget_context_region.argtypes = [vp, C.c_size_t, C.POINTER(ContextRegion)]
+        L.hsw_gadget_create_contexts.restype = C.c_int
+        L.hsw_gadget_create_contexts.argtypes = [vp, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_int, C.c_uint32,
+                                                 C.POINTER(vp)]
         L.hsw_gadget_create_ex.restype = C.c_int
         L.hsw_gadget_create_ex.argtypes = [vp, C.POINTER(C.c_size_t), C.c_size_t, C.c_int, C.c_uint32,
                                            C.POINTER(vp)]

@@ -1389,11 +1389,21 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
     const u32 parts = p.parts;                   // waves per block (power of two <= 16)
     const size_t blk = blockIdx.x / parts;
     const u32 part = blockIdx.x % parts;
+    // the block whose inputs, next state and chip cursor these are: blk itself, or (Context groups: the launch is one
+    // digest index of several Contexts) the same block of that digest ctx_blocks further per Context
+    // (table path: the block's digest of the launch -- of a group's launch, its Context -- computed ONCE, wave-uniform
+    //  and in 32 bits; the launch checks frame_every != 0)
+    size_t in_blk = blk;
+    u32 tctx = 0;
+    if constexpr (TABLE) {
+        tctx = (u32)blk / (u32)p.frame_every;
+        if (tbl->ctx_blocks) in_blk = (size_t)tctx * (size_t)tbl->ctx_blocks + (size_t)((u32)blk - tctx * (u32)p.frame_every);
+    }
 
     // ---- chain phase: plain SHA-256 of this block, wave-uniform -------------
     if constexpr (EMITS) {
-        const u32 *bw = reinterpret_cast<const u32 *>(p.blocks + 64 * blk);
-        const u32 *ps = p.pre_states + 8 * blk;
+        const u32 *bw = reinterpret_cast<const u32 *>(p.blocks + 64 * in_blk);
+        const u32 *ps = p.pre_states + 8 * in_blk;
         u32 w[16];
 #pragma unroll
         for (int i = 0; i < 16; i++) {
@@ -1424,7 +1434,7 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
             if (lane == 0) { sA[t + 4] = a; sE[t + 4] = e; }
         }
         if (p.next_states != nullptr && lane == 0 && part == 0) {
-            u32 *ns = p.next_states + 8 * blk;               // compression.rs:197-212
+            u32 *ns = p.next_states + 8 * in_blk;             // compression.rs:197-212
             ns[0] = ps[0] + a; ns[1] = ps[1] + b; ns[2] = ps[2] + c; ns[3] = ps[3] + d;
             ns[4] = ps[4] + e; ns[5] = ps[5] + f; ns[6] = ps[6] + g; ns[7] = ps[7] + h;
         }
@@ -1467,7 +1477,8 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
         u64 first = (u64)blk * (u64)LY::GATE_CELLS, ctx_base = 0;
         if constexpr (RC)          // whole-digest streams: every frame_every blocks a digest frame sits in between
             if (p.frame_every) {
-                const u32 ctx = (u32)blk / (u32)p.frame_every;       // wave-uniform (blk is the workgroup's block)
+                u32 ctx;                                             // wave-uniform (blk is the workgroup's block)
+                if constexpr (TABLE) ctx = tctx; else ctx = (u32)blk / (u32)p.frame_every;
                 if (p.ctx_cells) {     // context images: the breaks are one context's, the image of context ctx follows ctx_cells further
                     first -= (u64)ctx * (u64)p.frame_every * (u64)LY::GATE_CELLS;
                     ctx_base = (u64)ctx * p.ctx_cells;
@@ -1496,12 +1507,15 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
             em.out = reinterpret_cast<uint4 *>(p.gate) + (size_t)(ctx_base + first + gap0) * 2u;
     }
     size_t lk_blk = (size_t)blk * (size_t)LY::LOOKUP_CELLS;
-    if constexpr (RC)
+    if constexpr (TABLE) {         // shared context: the caller's lookup entries queued before this block's digest
+        lk_blk += (size_t)tctx * (size_t)p.frame_lookups;
+        if (!tbl->ctx_blocks)      // (a Context group's launch is ONE digest index: its shift is in p.lookup, frame_lookups steps a Context)
+            lk_blk += (size_t)(tbl_uniform(tbl->lk_shift, (u64)tctx) - tbl_uniform(tbl->lk_shift, 0));
+    } else if constexpr (RC) {
         if (p.frame_every) lk_blk += (size_t)(blk / p.frame_every) * (size_t)p.frame_lookups;
-    if constexpr (TABLE)           // shared context: the caller's lookup entries queued before this block's digest
-        lk_blk += (size_t)(tbl_uniform(tbl->lk_shift, (u64)(blk / p.frame_every)) - tbl_uniform(tbl->lk_shift, 0));
+    }
     em.write_gate = (p.flags & HSW_K_SKIP_GATE) == 0u;
-    const u64 blk_limb0 = p.cursor0 + (u64)blk * (u64)LY::LIMB_CALLS;   // first limb call of this block
+    const u64 blk_limb0 = p.cursor0 + (u64)in_blk * (u64)LY::LIMB_CALLS;   // first limb call of this block
 
     // ---- words: compression.rs:31-47, 16 units of 4 mul_add ----------------
     if (in_phase[PH_WORDS] && phase_begin(em, wp[PH_WORDS], wn[PH_WORDS], 16, LY::WORD, LY::OFF_WORDS, 0, 0)) {

@@ -33,7 +33,8 @@ __global__ __launch_bounds__(256) void hsw_frame_table_kernel(const FrameDesc *d
                                                               const u32 *pre_states, const u32 *next_states,
                                                               const u64 *inv_tbl, uint4 *gate, uint4 *lookup,
                                                               u32 slices, PlaceTable t) {
-    const FrameBreaks brk{};   // (no break table, no context images: the placement is the table's)
+    FrameBreaks brk{};         // (no break table: the placement is the table's -- ONE Context's, repeated for a Context group)
+    brk.ctx_stream = t.ctx_stream; brk.ctx_image = t.ctx_image;
     const u32 slice = blockIdx.x % slices;
     const FrameDesc d = descs[blockIdx.x / slices];
     framedev::frame_cells<MONT, true>(d, blocks, inv_tbl, gate, lookup, brk, framedev::FRAME_ALL, slice * blockDim.x + threadIdx.x,

@@ -255,7 +255,7 @@ void Context::free_compact_staging() {
 }
 
 int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool whole_digest, bool independent,
-                                     bool context_images, bool shared) const {
+                                     bool context_images, bool shared, size_t group_m) const {
     if (!engine || !out) return HSW_ERR_INVALID_ARG;
     *out = nullptr;
     hsw_shape s;
@@ -284,7 +284,8 @@ int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool who
         c->independent = independent;
         c->context_images = context_images;
         c->shared = shared;
-        if (shared) c->declared.resize(max_variable_byte_sizes.size());
+        if (shared) c->declared.resize(group_m ? group_m : max_variable_byte_sizes.size());
+        c->group_m = group_m;
         // the Context's zero cell: one, or one per digest when every digest is a Context of its own
         uint64_t cells = independent ? max_variable_byte_sizes.size() : 1, lookups = 0;
         for (size_t b : max_variable_byte_sizes) {
@@ -300,6 +301,17 @@ int Sha256DynamicConfig::new_context(hsw_engine *engine, Context **out, bool who
             lookups += fs.digest_lookups;
             c->ctx_digest_cells = fs.digest_cells;            // (context images: every digest has this shape)
             c->ctx_own_lookups = fs.digest_lookups;
+        }
+        if (group_m) {                                        // K Contexts alike: a zero cell each, one Context's sums
+            const uint64_t K = max_variable_byte_sizes.size() / group_m;
+            c->ctx_digest_cells = (cells - 1) / K;
+            c->ctx_own_lookups = lookups / K;
+            c->ctx_blocks = total / (size_t)K;
+            cells += K - 1;
+            if (((uint64_t)c->ctx_blocks * s.limb_calls_per_block) % s.num_advice_columns != 0) {
+                delete c;
+                return HSW_ERR_UNSUPPORTED;                   // a Context's chip rows must start on a row of their own
+            }
         }
         c->gate_capacity = cells;
         c->lookup_capacity = c->own_lookup_capacity = lookups;
@@ -351,9 +363,11 @@ int Context::plan_layout(const std::vector<size_t> &sizes, bool rc_inputs, uint6
                          Layout *out) const {
     if (!rows) return HSW_OK;                             // no image: the stream as it is, from the origin
     // context images: ONE Context's walk (every Context is laid out alike), K images of it
-    const size_t n = context_images && !sizes.empty() ? 1 : sizes.size();
+    // (a Context group: ONE Context's group_m digests, with the declarations)
+    const size_t n = context_images && !sizes.empty() ? 1 : group_m ? group_m : sizes.size();
     const int rc = layout_walk(shape, sizes.data(), n, rc_inputs, rows, shared ? &decl : nullptr, out);
     if (rc != HSW_OK) return rc;
+    if (group_m) out->period = ctx_digest_cells + (out->origin_zero_loaded ? 0u : 1u);
     if (shared) return out->columns > HSW_GADGET_MAX_COLUMNS ? HSW_ERR_TOO_LARGE : HSW_OK;
     out->digest_cell0.clear(); out->digest_entry0.clear(); out->digest_lookup0.clear();   // (one lookup run, no table)
     if (context_images) out->period = ctx_digest_cells + (out->origin_zero_loaded ? 0u : 1u);
@@ -361,10 +375,16 @@ int Context::plan_layout(const std::vector<size_t> &sizes, bool rc_inputs, uint6
 }
 
 int Context::adopt(Layout &nl, bool fresh_image, bool fresh_lookup, uint64_t clear_from) {
-    const size_t K = context_images ? init_capacity : 1, none = ~(size_t)0;
+    const size_t K = contexts(), none = ~(size_t)0;
     const bool table = shared && nl.max_rows, changed = !nl.same_map(layout);
     size_t img_cells = none, img_keep = 0, lk_cells = none, lk_keep = 0;
-    if (table) {                                          // the image grows: the columns so far are copied over
+    if (table && group_m) {
+        // a Context group: K images and K lookup columns whose places follow from one Context's size -- a layout
+        // that differs gets fresh, zeroed ones (the same layout again, pass after pass, keeps them)
+        if (fresh_image || changed || nl.max_rows != layout.max_rows) img_cells = K * (size_t)nl.image_cells();
+        if (fresh_lookup || nl.lookups_end != layout.lookups_end || K * (size_t)nl.lookups_end != lookup_capacity) lk_cells = K * (size_t)nl.lookups_end;
+        fresh_lookup = false;
+    } else if (table) {                                   // the image grows: the columns so far are copied over
         const uint64_t have = nl.max_rows == layout.max_rows ? image_columns : 0;   // (another column height: a fresh image)
         if (nl.columns > have) { img_cells = (size_t)nl.image_cells(); img_keep = (size_t)(have * nl.max_rows); }
     } else if (fresh_image) {
@@ -372,8 +392,8 @@ int Context::adopt(Layout &nl, bool fresh_image, bool fresh_lookup, uint64_t cle
     }
     // the lookup-advice stream is indexed from the Context's first queued cell: [0, origin_lookups) are the caller's
     if (fresh_lookup) lk_cells = (size_t)own_lookup_capacity + K * (size_t)nl.origin_lookups;
-    else if (table && nl.lookups_end > lookup_capacity) { lk_cells = (size_t)nl.lookups_end; lk_keep = (size_t)lookup_capacity; }   // the interludes' entries
-    const bool clear = table && changed;
+    else if (table && !group_m && nl.lookups_end > lookup_capacity) { lk_cells = (size_t)nl.lookups_end; lk_keep = (size_t)lookup_capacity; }   // the interludes' entries
+    const bool clear = table && changed && !group_m;
     if (img_cells != none || lk_cells != none || clear) {
         int device = 0;
         hsw_engine_stream(engine, nullptr, &device);
@@ -489,6 +509,10 @@ struct Launch {
             tbl = PlaceTable{d_place, d_place + n, d_place + 2 * n, n, 0};
             period.place = &tbl;
             per = &period;
+            if (c.group_m) {                             // the periodic table: one Context's, every l.period stream cells
+                tbl.ctx_blocks = c.ctx_blocks; tbl.ctx_stream = l.period; tbl.ctx_image = l.image_cells();
+                period.stream_cells = l.period; period.image_cells = l.image_cells();
+            }
         } else if (l.max_rows) {
             abs.n_breaks = (uint32_t)l.break_cell.size();
             for (size_t k = 0; k < abs.n_breaks; k++) { abs.break_cell[k] = l.break_cell[k]; abs.break_gap[k] = l.break_gap[k]; }
@@ -529,9 +553,12 @@ struct Launch {
         // when every digest is a Context of its own, and (context images) its caller-owned lookup cells
         a.frame_cells = fs.epilogue_cells + fs.prologue_cells + (c.independent && !l.origin_zero_loaded ? 1u : 0u);
         a.frame_lookups = fs.epilogue_lookups + fs.prologue_lookups + (c.context_images ? l.origin_lookups : 0u);
+        // (a Context group: the "digests" of the run are the SAME digest index of consecutive Contexts, whose lookup
+        //  columns lie ctx_lookups() apart and whose blocks ctx_blocks apart -- PlaceTable::ctx_blocks)
+        if (c.group_m) a.frame_lookups = c.ctx_lookups() - (uint64_t)fs.n_blocks * c.shape.lookup_cells_per_block;
         if (period.place) {                              // the run's first block cell, its digests' lookup shifts
             tbl.base = local;
-            tbl.lk_shift = tbl.cell + 2 * tbl.n + digest0;
+            tbl.lk_shift = tbl.cell + 2 * tbl.n + (c.group_m ? digest0 % c.group_m : digest0);
         } else if (frame_pack) {                         // breaks before the launch's first cell are pure offsets
             rel.n_breaks = abs.n_breaks;
             for (uint32_t k = 0; k < rel.n_breaks; k++) {
@@ -542,6 +569,32 @@ struct Launch {
         }
     }
 };
+
+// The expansion (and verify) launches of a batch of n digests from digest d0 of the pass on, as runs of `count` digests
+// `step` apart from batch index `first`: neighbours of equal size (blocks_of(i): digest i of the batch) -- or, in a
+// Context group, digest index j of every Context the batch holds it of: M launches, not K * M
+struct Run { size_t first, count, step; };
+template <class BlocksOf>
+std::vector<Run> batch_runs(const Context &c, size_t d0, size_t n, BlocksOf blocks_of) {
+    std::vector<Run> runs;
+    if (c.group_m) {
+        const size_t M = c.group_m;
+        for (size_t j = 0; j < M; j++) {
+            const size_t c_lo = d0 > j ? (d0 - j + M - 1) / M : 0;      // the first Context whose digest j the batch holds
+            const size_t first = c_lo * M + j;
+            if (first >= d0 + n) continue;
+            runs.push_back(Run{first - d0, (d0 + n - first + M - 1) / M, M});
+        }
+        return runs;
+    }
+    for (size_t i = 0; i < n;) {
+        size_t j = i + 1;
+        while (j < n && blocks_of(j) == blocks_of(i)) j++;
+        runs.push_back(Run{i, j - i, 1});
+        i = j;
+    }
+    return runs;
+}
 
 int Sha256DynamicConfig::digest(Context &ctx, const uint8_t *input, size_t input_len,
                                 size_t precomputed_input_len, AssignedHashResult *result) {
@@ -618,7 +671,9 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
     // small-batch kernel, which for a whole-digest context also writes the frames -- ONE launch, inputs read
     // in place from the pinned staging, next states written straight into pinned memory, no copy launches.
     // (whole-digest contexts: one such launch per run of equally sized digests, each with its own frames)
-    const bool small = hsw_small_eligible(ctx.engine, batch_blocks);
+    // (a Context group always takes the expansion + frame launches: its expansion launches are not contiguous runs)
+    if (ctx.group_m && !ctx.layout.max_rows) return HSW_ERR_UNSUPPORTED;        // K images: hsw_gadget_set_columns first
+    const bool small = !ctx.group_m && hsw_small_eligible(ctx.engine, batch_blocks);
     const bool zero_copy = host_chain && (ctx.whole ? small : (small || batch_blocks <= 32));
     const uint8_t *d_blk = (zero_copy ? ctx.dp_blocks : ctx.d_blocks) + 64 * b0;
     uint32_t *d_next = ctx.d_next_states + 8 * b0;
@@ -676,7 +731,13 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 d.is_input_range_check = is_input_range_check ? 1u : 0u;
                 // context images: Context h's lookup column is cells [h*Lp, (h+1)*Lp), the caller's queued cells first
                 if (ctx.context_images) lc = (uint64_t)(cur_hash_idx + i) * ctx.ctx_lookups() + ctx.layout.origin_lookups;
-                if (table) lc = ctx.layout.digest_lookup0[cur_hash_idx + i];   // after the caller's entries of the interlude
+                if (table && !ctx.group_m) lc = ctx.layout.digest_lookup0[cur_hash_idx + i];   // after the caller's entries of the interlude
+                if (ctx.group_m) {                           // digest j of Context cx: that Context's stream, image and lookup column
+                    const size_t cx = (cur_hash_idx + i) / ctx.group_m, j = (cur_hash_idx + i) % ctx.group_m;
+                    gc = cx * ctx.layout.period + ctx.layout.digest_cell0[j];
+                    lc = cx * ctx.ctx_lookups() + ctx.layout.digest_lookup0[j];
+                    zero_loaded = j != 0 || ctx.layout.origin_zero_loaded;
+                }
                 r.prologue_cell = d.prologue_cell = gc;      gc += fss[i].prologue_cells;
                 r.prologue_lookup = d.prologue_lookup = lc;  lc += fss[i].prologue_lookups;
                 d.zero_cell = ~0ull;
@@ -690,10 +751,10 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
             }
             if (rc == HSW_OK && (gc > ctx.gate_capacity || lc > ctx.lookup_capacity)) rc = HSW_ERR_INVALID_ARG;
             ob = 0;
-            for (size_t i = 0; i < n && rc == HSW_OK;) {
-                size_t j = i + 1;                            // run [i, j) of equally sized digests
-                while (j < n && frames[j].n_blocks == frames[i].n_blocks) j++;
-                L.run(cur_hash_idx + i, results[i], b0 + ob, j - i, fss[i]);
+            for (const Run &run : batch_runs(ctx, cur_hash_idx, n, [&](size_t k) { return frames[k].n_blocks; })) {
+                if (rc != HSW_OK) break;
+                const size_t i = run.first, j = i + run.count;   // (step 1: the run [i, j) of equally sized digests)
+                L.run(cur_hash_idx + i, results[i], (size_t)frames[i].first_block, run.count, fss[i]);
                 if (small) {
                     hsw_digests_args da{};
                     da.blocks = L.a;
@@ -709,7 +770,6 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                     rc = hsw_witness_blocks_impl(ctx.engine, &L.a, nullptr, nullptr, L.per);
                 }
                 ob += L.a.n_blocks;
-                i = j;
             }
             if (rc == HSW_OK && !small)
                 rc = hsw_witness_frames_impl(ctx.engine, frames.data(), n, L.in_blocks, L.in_pre, ctx.d_next_states,
@@ -813,6 +873,30 @@ int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, s
                                              is_input_range_check != 0, &g->cfg);
     if (rc == HSW_OK) rc = g->cfg.new_context(e, &g->ctx, (flags & HSW_GADGET_WHOLE_DIGEST) != 0, (flags & HSW_GADGET_INDEPENDENT) != 0,
                                               images, shared);
+    if (rc != HSW_OK) { delete g; return rc; }
+    *out = g;
+    return HSW_OK;
+} HSW_NO_UNWIND
+
+int hsw_gadget_create_contexts(hsw_engine *e, const size_t *max_variable_byte_sizes, size_t digests_per_context,
+                               size_t n_contexts, int is_input_range_check, uint32_t flags, hsw_gadget **out) try {
+    if (!e || !out || !max_variable_byte_sizes || digests_per_context == 0 || n_contexts == 0) return HSW_ERR_INVALID_ARG;
+    // (HSW_GADGET_SHARED_CONTEXT may be named: every Context of a group is one; the K-proof flags of create_ex are not this)
+    if (!(flags & HSW_GADGET_WHOLE_DIGEST) || (flags & ~(HSW_GADGET_WHOLE_DIGEST | HSW_GADGET_SHARED_CONTEXT))) return HSW_ERR_INVALID_ARG;
+    *out = nullptr;
+    hsw_shape s;
+    int rc = hsw_engine_shape(e, &s);
+    if (rc != HSW_OK) return rc;
+    if (s.mode != HSW_MODE_HALO2_INTERNALS) return HSW_ERR_INVALID_ARG;
+    if (s.num_bits_lookup != 8) return HSW_ERR_UNSUPPORTED;              // the table-path kernels: the 8-bit spread table
+    if (n_contexts > (~(size_t)0 >> 8) / digests_per_context) return HSW_ERR_TOO_LARGE;
+    hsw_gadget *g = new (std::nothrow) hsw_gadget();
+    if (!g) return HSW_ERR_NOMEM;
+    std::vector<size_t> sizes;                               // digest d of the pass: digest d % M of Context d / M
+    sizes.reserve(digests_per_context * n_contexts);
+    for (size_t c = 0; c < n_contexts; c++) sizes.insert(sizes.end(), max_variable_byte_sizes, max_variable_byte_sizes + digests_per_context);
+    rc = hsw::Sha256DynamicConfig::configure(sizes, s.num_bits_lookup, s.num_advice_columns, is_input_range_check != 0, &g->cfg);
+    if (rc == HSW_OK) rc = g->cfg.new_context(e, &g->ctx, true, false, false, true, digests_per_context);
     if (rc != HSW_OK) { delete g; return rc; }
     *out = g;
     return HSW_OK;
@@ -945,7 +1029,7 @@ int hsw_gadget_set_origin(hsw_gadget *g, uint64_t column, uint64_t row, int zero
 int hsw_gadget_set_digest_origin(hsw_gadget *g, size_t h, uint64_t column, uint64_t row, uint64_t lookups_queued) try {
     if (!g) return HSW_ERR_INVALID_ARG;
     hsw::Context &c = *g->ctx;
-    const size_t n = g->cfg.max_variable_byte_sizes.size();
+    const size_t n = c.group_m ? c.group_m : g->cfg.max_variable_byte_sizes.size();   // (a group: digest h of every Context alike)
     if (!c.shared || !c.layout.max_rows || h < 1 || h >= n || h < g->cfg.cur_hash_idx || row >= c.layout.max_rows)
         return HSW_ERR_INVALID_ARG;
     const hsw::DigestOrigin &was = c.declared[h];
@@ -1078,8 +1162,10 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
         // images: K images back to back, host layout = device layout).  Rows above the origin, the gaps at column ends
         // and the interludes' cells are the caller's or nobody's: never touched
         const hsw::Layout &l = c.layout;
-        const uint64_t end = l.period ? l.period : c.gate_cursor, K = l.period ? g->cfg.cur_hash_idx : 1;
+        // (a Context group: the Contexts begun so far, the last one up to the cursor)
+        const uint64_t K = c.group_m ? (c.gate_cursor + l.period - 1) / l.period : l.period ? g->cfg.cur_hash_idx : 1;
         for (uint64_t h = 0; h < K; h++) {
+            const uint64_t end = !l.period ? c.gate_cursor : c.group_m && c.gate_cursor < (h + 1) * l.period ? c.gate_cursor - h * l.period : l.period;
             uint64_t lo = 0;
             for (size_t k = 0; k <= l.break_cell.size() && lo < end; k++) {
                 const uint64_t hi = k < l.break_cell.size() && l.break_cell[k] < end ? l.break_cell[k] : end;
@@ -1096,10 +1182,12 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
         for (uint64_t h = 0; h < g->cfg.cur_hash_idx; h++)
             copy(dst->lookup, c.d_lookup, (size_t)(h * Lp + c.layout.origin_lookups), (size_t)c.ctx_own_lookups);
     } else if (dst->lookup && c.d_lookup && c.shared && !c.layout.digest_lookup0.empty()) {
-        for (size_t h = 0; h < g->cfg.cur_hash_idx; h++) {     // every digest's own entries; the interludes' are the caller's
-            const uint64_t end = h + 1 < c.layout.digest_entry0.size() ? c.layout.digest_entry0[h + 1]
-                                                               : c.own_lookup_capacity;
-            copy(dst->lookup, c.d_lookup, (size_t)c.layout.digest_lookup0[h], (size_t)(end - c.layout.digest_entry0[h]));
+        const size_t M = c.group_m ? c.group_m : c.layout.digest_entry0.size();
+        const uint64_t own = c.group_m ? c.ctx_own_lookups : c.own_lookup_capacity, Lp = c.group_m ? c.ctx_lookups() : 0;
+        for (size_t d = 0; d < g->cfg.cur_hash_idx; d++) {     // every digest's own entries; the interludes' are the caller's
+            const size_t h = d % M, cx = d / M;                 // (a Context group: digest h of Context cx, in its own lookup column)
+            const uint64_t end = h + 1 < c.layout.digest_entry0.size() ? c.layout.digest_entry0[h + 1] : own;
+            copy(dst->lookup, c.d_lookup, (size_t)(cx * Lp + c.layout.digest_lookup0[h]), (size_t)(end - c.layout.digest_entry0[h]));
         }
     } else if (dst->lookup && c.d_lookup) {
         copy(dst->lookup, c.d_lookup, (size_t)c.layout.origin_lookups, (size_t)(c.lookup_cursor - c.layout.origin_lookups));
@@ -1119,7 +1207,7 @@ int hsw_gadget_download_region_compact(hsw_gadget *g, hsw_region_compact *dst) t
     hsw::Context &c = *g->ctx;
     if (c.repr_flags != HSW_REPR_CANONICAL) return HSW_ERR_UNSUPPORTED;      // packs canonical 32-byte cells
     if (c.context_images) return HSW_ERR_UNSUPPORTED;                         // one image per Context: not packed here
-    if (c.shared && c.layout.max_rows) return HSW_ERR_UNSUPPORTED;                   // shared context: interludes are the caller's
+    if ((c.shared && c.layout.max_rows) || c.group_m) return HSW_ERR_UNSUPPORTED;    // shared context: interludes are the caller's
     if (!dst->wide && dst->wide_cap) return HSW_ERR_INVALID_ARG;
     hipStream_t stream = nullptr;
     int device = 0;
@@ -1260,35 +1348,31 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
             merge(r);
             continue;
         }
-        size_t fb = b.first_block;
-        for (size_t i = 0; i < b.n_digests;) {                       // runs of equally sized digests, as generated
-            const hsw::AssignedHashResult &r0 = g->results[b.first_digest + i];
-            size_t j = i + 1;
-            while (j < b.n_digests && g->results[b.first_digest + j].n_blocks == r0.n_blocks) j++;
+        // the launches of the batch as it was generated: runs of equally sized digests, or a group's digest indices
+        for (const hsw::Run &run : hsw::batch_runs(c, b.first_digest, b.n_digests, [&](size_t k) { return g->results[b.first_digest + k].n_blocks; })) {
+            const hsw::AssignedHashResult &r0 = g->results[b.first_digest + run.first];
             hsw_frame_shape fs;
             int rc = hsw_frame_query(&c.shape, r0.n_blocks * 64, g->cfg.is_input_range_check ? 1 : 0, &fs);
             if (rc != HSW_OK) return rc;
-            L.run(b.first_digest + i, r0, fb, j - i, fs);
+            L.run(b.first_digest + run.first, r0, r0.first_block, run.count, fs);
             rc = hsw_verify_blocks_impl(c.engine, &L.a, &r, L.per);
             if (rc != HSW_OK) return rc;
             merge(r);
-            std::vector<hsw_frame_desc> descs(j - i);
-            for (size_t k = i; k < j; k++) {
-                const hsw::AssignedHashResult &rk = g->results[b.first_digest + k];
-                hsw_frame_desc &d = descs[k - i];
-                d.input_len = rk.input_len; d.first_block = fb; d.n_blocks = (uint32_t)rk.n_blocks;
+            std::vector<hsw_frame_desc> descs(run.count);
+            for (size_t k = 0; k < run.count; k++) {
+                const hsw::AssignedHashResult &rk = g->results[b.first_digest + run.first + k * run.step];
+                hsw_frame_desc &d = descs[k];
+                d.input_len = rk.input_len; d.first_block = rk.first_block; d.n_blocks = (uint32_t)rk.n_blocks;
                 d.num_round = (uint32_t)rk.num_round; d.precomputed_round = (uint32_t)(rk.num_round - rk.target_round);
                 d.is_input_range_check = g->cfg.is_input_range_check ? 1u : 0u;
                 d.prologue_cell = rk.prologue_cell; d.epilogue_cell = rk.epilogue_cell;
                 d.prologue_lookup = rk.prologue_lookup; d.epilogue_lookup = rk.epilogue_lookup;
                 d.zero_cell = rk.block_cell == rk.prologue_cell + fs.prologue_cells + 1 ? rk.block_cell - 1 : ~0ull;
-                fb += rk.n_blocks;
             }
             rc = hsw_verify_frames_impl(c.engine, descs.data(), descs.size(), L.in_blocks, L.in_pre, c.d_next_states, c.gate_stream(),
                                         c.d_lookup, L.frame_pack, b.repr_flags, &r, L.per);
             if (rc != HSW_OK) return rc;
             merge(r);
-            i = j;
         }
     }
     return HSW_OK;
@@ -1297,11 +1381,12 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
 int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region *out) try {
     if (!g || !out) return HSW_ERR_INVALID_ARG;
     const hsw::Context &c = *g->ctx;
-    if (!c.context_images || h >= g->cfg.max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
+    if (!(c.context_images || c.group_m) || h >= c.contexts()) return HSW_ERR_INVALID_ARG;
     std::memset(out, 0, sizeof *out);
     const size_t cb = HSW_CELL_BYTES;                       // whole-digest contexts: 32-byte cells
     const uint32_t ncols = c.shape.num_advice_columns;
-    const uint64_t nb = g->cfg.max_variable_byte_sizes[h] / 64, C = c.ctx_stream();
+    // (a Context group: Context h holds group_m digests, ctx_blocks blocks)
+    const uint64_t nb = c.group_m ? c.ctx_blocks : g->cfg.max_variable_byte_sizes[h] / 64, C = c.ctx_stream();
     out->stream_cells = C;
     out->first_stream_cell = h * C;
     out->columns = c.layout.columns;
@@ -1324,7 +1409,7 @@ int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region 
     out->origin_column = c.layout.origin_column;
     out->origin_row = c.layout.origin_row;
     out->origin_lookups = c.layout.origin_lookups;
-    out->assigned = h < g->cfg.cur_hash_idx ? 1u : 0u;
+    out->assigned = (h + 1) * (c.group_m ? c.group_m : 1) <= g->cfg.cur_hash_idx ? 1u : 0u;   // every digest of the Context
     return HSW_OK;
 } HSW_NO_UNWIND
 

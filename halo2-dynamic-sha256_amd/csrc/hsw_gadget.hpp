@@ -75,8 +75,9 @@ class Sha256DynamicConfig {
 
     // lib.rs:351-360: a context sized for every hash this config will assign.
     // whole_digest: also lay out digest()'s own cells (HSW_GADGET_WHOLE_DIGEST)
+    // group_m: a Context group (hsw_gadget_create_contexts) -- max_variable_byte_sizes holds K Contexts' group_m sizes each
     int new_context(hsw_engine *engine, Context **out, bool whole_digest = false, bool independent = false,
-                    bool context_images = false, bool shared = false) const;
+                    bool context_images = false, bool shared = false, size_t group_m = 0) const;
 
     // lib.rs:71-349.  precomputed_input_len = 0 is the reference's None.
     int digest(Context &ctx, const uint8_t *input, size_t input_len, size_t precomputed_input_len,
@@ -130,7 +131,17 @@ class Context {
     bool context_images = false;
     uint64_t ctx_digest_cells = 0, ctx_own_lookups = 0;   // one Context's digest cells (zero cell not counted) and lookups
     uint64_t ctx_stream() const { return ctx_digest_cells + (layout.origin_zero_loaded ? 0u : 1u); }   // C: stream cells per Context
-    uint64_t ctx_lookups() const { return layout.origin_lookups + ctx_own_lookups; }             // Lp
+    uint64_t ctx_lookups() const {                                                               // Lp
+        return group_m && layout.max_rows ? layout.lookups_end : layout.origin_lookups + ctx_own_lookups;
+    }
+    // hsw_gadget_create_contexts (with shared): K Contexts of group_m digests each, every one laid out like ONE shared
+    // context (its jumps, its interludes, the jump table on the device) and repeated like context images -- Context
+    // c's image is cells [c*S, (c+1)*S) of d_gate, its lookup column cells [c*Lp, (c+1)*Lp) of d_lookup, its chip rows
+    // follow Context c-1's.  Digest d of the pass is digest d % group_m of Context d / group_m; the layout, the
+    // declarations and ctx_digest_cells / ctx_own_lookups are ONE Context's
+    size_t group_m = 0;
+    size_t ctx_blocks = 0;                                     // blocks of one Context
+    size_t contexts() const { return context_images ? init_capacity : group_m ? init_capacity / group_m : 1; }
     bool zero_loaded = false;        // Context.zero_cell (first load_zero: compression.rs:34 of the first block)
     uint64_t gate_cursor = 0, gate_capacity = 0;       // cells
     void *d_lookup = nullptr;

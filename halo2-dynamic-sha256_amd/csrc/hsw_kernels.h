@@ -101,6 +101,15 @@ struct PlaceTable {
     const uint64_t *lk_shift;   // expansion: per digest of the launch (blk / frame_every), cumulative caller lookup entries
     uint64_t n;
     uint64_t base;              // expansion: gate-stream cell that ExpandParams::gate (no gaps added) stands for
+    // Context groups (hsw_gadget_create_contexts; 0 = one Context): the table is ONE Context's and repeats with a
+    // period -- a Context's gate stream is ctx_stream cells long, its image ctx_image cells (ExpandParams /
+    // VerifyParams::ctx_cells carry ctx_image to the block kernels), and it owns ctx_blocks blocks.  An expansion or
+    // verify launch then covers ONE digest index of several Contexts: block b is block b % frame_every of that digest
+    // in Context b / frame_every, so its inputs, next states and chip cursor are those of block
+    // (b / frame_every) * ctx_blocks + b % frame_every from the launch's first, its cells go through the table at
+    // base + (b % frame_every) * G and land (b / frame_every) * ctx_image further, and its lookup entries follow the
+    // launch's first by (b / frame_every) * (frame_every * LOOKUP_CELLS + frame_lookups), lk_shift unused
+    uint64_t ctx_blocks, ctx_stream, ctx_image;
 };
 
 struct FrameDesc;   // hsw_frame.hpp

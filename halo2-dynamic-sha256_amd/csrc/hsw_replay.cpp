@@ -142,7 +142,9 @@ static int build_region_tape(const hsw_gadget *g, RegionTape **out) {
         if (!b.section(pro, g0, pro_ext)) return HSW_ERR_INVALID_ARG;
         for (int64_t src : pro.lookup_src) t->lookup_code.push_back(b.code_of(pro_ext(src)));
         gc += P;
-        if (!zero_seen || (c.independent && !c.layout.origin_zero_loaded)) {   // this digest's Context loads its zero cell (A4-iii)
+        // this digest's Context loads its zero cell (A4-iii): the first digest of the pass -- or of every Context
+        const bool ctx_first = c.independent || (c.group_m && h % c.group_m == 0);
+        if (!zero_seen || (ctx_first && !c.layout.origin_zero_loaded)) {
             zero_abs = (int64_t)gc;
             t->gate_code[(size_t)gc] = b.constant(0);
             gc += 1;
@@ -189,7 +191,7 @@ static int build_region_tape(const hsw_gadget *g, RegionTape **out) {
     }
     // (a Context that came with its zero cell leaves the one cell reserved for it unused -- one per Context when
     //  every digest is a Context of its own)
-    const uint64_t unused = c.layout.origin_zero_loaded ? (c.independent ? (uint64_t)g->cfg.max_variable_byte_sizes.size() : 1) : 0;
+    const uint64_t unused = c.layout.origin_zero_loaded ? (c.independent ? (uint64_t)g->cfg.max_variable_byte_sizes.size() : (uint64_t)c.contexts()) : 0;
     if (gc + unused != c.gate_capacity || t->lookup_code.size() != c.own_lookup_capacity) return HSW_ERR_INVALID_ARG;
     guard.p = nullptr;
     *out = t;
@@ -205,7 +207,7 @@ static int ensure_tape(hsw_gadget *g) {
 struct Extent { uint64_t cells, wit, lookups, limbs; };
 // Everything image_cell() depends on besides the stream cell
 static std::vector<uint64_t> layout_key(const Context &c) {
-    std::vector<uint64_t> k{c.layout.max_rows, c.layout.origin_row, c.context_images ? c.ctx_stream() : 0, c.layout.image_cells()};
+    std::vector<uint64_t> k{c.layout.max_rows, c.layout.origin_row, c.context_images || c.group_m ? c.ctx_stream() : 0, c.layout.image_cells()};
     k.insert(k.end(), c.layout.break_cell.begin(), c.layout.break_cell.end());
     k.insert(k.end(), c.layout.break_gap.begin(), c.layout.break_gap.end());
     return k;
@@ -268,7 +270,7 @@ int hsw_gadget_download_region_distinct(hsw_gadget *g, void *distinct, size_t ca
     if (t.d_wit_pos && key != t.pos_layout) drop_region_tape_positions(&t);
     if (!t.d_wit_pos) {                                   // first delivery with this layout: where every witness sits in the image
         // (image positions are 32-bit: every Context's image together must stay below 2^32 cells)
-        if (c.layout.max_rows && c.layout.columns * c.layout.max_rows * (c.context_images ? c.init_capacity : 1) >= (1ull << 32)) {
+        if (c.layout.max_rows && c.layout.columns * c.layout.max_rows * c.contexts() >= (1ull << 32)) {
             if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
             return HSW_ERR_TOO_LARGE;
         }
@@ -310,7 +312,7 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
     auto gate_part = [&](uint64_t lo, uint64_t hi) {
         if (!dst->gate) return;
         Cell *img = static_cast<Cell *>(dst->gate);
-        if (c.context_images && c.layout.max_rows) {                     // K images: every Context walks its own breaks
+        if ((c.context_images || c.group_m) && c.layout.max_rows) {      // K images: every Context walks its own breaks
             for (uint64_t i = lo; i < hi; i++) img[c.layout.image_cell(i)] = value(t.gate_code[i]);
             return;
         }
@@ -328,6 +330,12 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
         if (c.context_images) {                                   // entry j of Context h = j / own: its own lookup column
             const uint64_t own = c.ctx_own_lookups, Lp = c.ctx_lookups();
             for (uint64_t j = lo; j < hi; j++) lk[(j / own) * Lp + j % own] = value(t.lookup_code[j]);
+            return;
+        }
+        if (c.group_m && !c.layout.digest_entry0.empty()) {              // a Context group: both -- entry j of Context j / own
+            Cell *lk0 = static_cast<Cell *>(dst->lookup);
+            const uint64_t own = c.ctx_own_lookups, Lp = c.ctx_lookups();
+            for (uint64_t j = lo; j < hi; j++) lk0[(j / own) * Lp + c.layout.lookup_cell(j % own)] = value(t.lookup_code[j]);
             return;
         }
         if (c.shared && !c.layout.digest_entry0.empty()) {               // shared context: past the caller's entries of the interludes

@@ -10,6 +10,11 @@
         g0 = p.gate_cell0 + (blk - dg * p.frame_every) * (u64)p.gate_cells;
         gate += 2u * (size_t)(dg * p.ctx_cells);
     }
+    // Context groups (TABLE, tbl->ctx_blocks): the launch is one digest index of several Contexts -- the block's
+    // inputs, next state and chip cursor are those of the same block ctx_blocks further per Context
+    u64 in_blk = blk;
+    if constexpr (TABLE)
+        if (tbl->ctx_blocks) in_blk = dg * tbl->ctx_blocks + (blk - dg * p.frame_every);
     const bool packed = p.n_breaks != 0;
     auto gcell = [&](u64 idx) -> Cell {
         if constexpr (TABLE) {
@@ -19,8 +24,8 @@
             return load_value<MONT>(gate, packed ? place(p, idx) : idx);
         }
     };
-    const uint8_t *bytes = p.blocks + 64 * blk;
-    const u32 *pre = p.pre_states + 8 * blk;
+    const uint8_t *bytes = p.blocks + 64 * in_blk;
+    const u32 *pre = p.pre_states + 8 * in_blk;
     u32 bad = 0;
     u32 first = 0xffffffffu, first_class = 0;
 
@@ -136,7 +141,7 @@
             const u32 n = nb + (tid >> 1);
             const bool act = n < p.limb_calls;
             const u32 nn = act ? n : 0u;
-            const u64 N = p.cursor0 + blk * (u64)p.limb_calls + nn;
+            const u64 N = p.cursor0 + in_blk * (u64)p.limb_calls + nn;
             const u64 at = (N % p.ncols) * (u64)p.chip_col_stride + (N / p.ncols - row0);
             const Cell rv = load_cell(half ? csp : cd, at);
             const int64_t id = p.chip[2 * nn + half];
@@ -162,7 +167,8 @@
             bool known;
             const Cell src = cell_of(p.lookup_src[j], known);
             u64 at = p.lookup_cell0 + blk * (u64)p.lookup_cells + dg * p.frame_lookups + j;
-            if constexpr (TABLE) at += tbl->lk_shift[dg] - tbl->lk_shift[0];
+            if constexpr (TABLE)
+                if (!tbl->ctx_blocks) at += tbl->lk_shift[dg] - tbl->lk_shift[0];   // (a group's launch: one digest index, its shift is in p.lookup)
             const Cell rv = load_cell(lk, at);
             Cell v = rv;
             bool enc = true;
@@ -174,11 +180,11 @@
     if (p.next_states && tid < 8) {
         bool known;
         const Cell v = cell_of(p.next_state_cells[tid], known);
-        if (!same(v, small(p.next_states[8 * blk + tid]))) fail(VERIFY_NEXT_STATE, (u32)p.next_state_cells[tid]);
+        if (!same(v, small(p.next_states[8 * in_blk + tid]))) fail(VERIFY_NEXT_STATE, (u32)p.next_state_cells[tid]);
     }
     if (bad) {
         atomicAdd(reinterpret_cast<unsigned long long *>(&p.report->violations), (unsigned long long)bad);
         // first failing (block, cell, class): smallest packed key wins
-        const unsigned long long key = ((unsigned long long)blk << 36) | ((unsigned long long)first << 4) | first_class;
+        const unsigned long long key = ((unsigned long long)in_blk << 36) | ((unsigned long long)first << 4) | first_class;
         atomicMin(reinterpret_cast<unsigned long long *>(&p.report->first_key), key);
     }

@@ -14,6 +14,7 @@
     }
     auto gcell = [&](u64 idx) -> Cell {
         if constexpr (TABLE) {
+            idx -= at0;       // (a Context group: the table is one Context's; at0 = 0 otherwise)
             const u64 k = tbl_count(*tbl, idx);
             return load_value<MONT>(gate, idx + (k ? tbl->cum[k - 1] : 0));
         } else {

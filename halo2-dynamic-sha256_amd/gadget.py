@@ -36,7 +36,7 @@ class Sha256DynamicConfig:
     """configure (lib.rs:49-69) + new_context (lib.rs:351-360) in one object."""
 
     def __init__(self, engine, max_variable_byte_sizes, is_input_range_check=True, whole_digest=False, independent=False,
-                 context_images=False, shared_context=False):
+                 context_images=False, shared_context=False, n_contexts=None):
         """whole_digest: also emit the cells digest() itself allocates (lib.rs:122-178, 294-341;
         SURVEY 8 f4, assumption A4) -- needs an engine in HSW_MODE_HALO2_INTERNALS.
         independent: every digest is a synthesis of its own (HSW_GADGET_INDEPENDENT: K proofs in one launch).
@@ -44,20 +44,28 @@ class Sha256DynamicConfig:
         Context origin (HSW_GADGET_CONTEXT_IMAGES; all max_variable_byte_sizes equal).
         shared_context: with whole_digest, every digest works on the same Context and the circuit may assign cells
         of its own between two digests (HSW_GADGET_SHARED_CONTEXT, set_digest_origin); layouts of up to
-        HSW_GADGET_MAX_COLUMNS columns."""
+        HSW_GADGET_MAX_COLUMNS columns.
+        n_contexts: a Context group (hsw_gadget_create_contexts) -- n_contexts proofs of one circuit whose digests
+        max_variable_byte_sizes lists (ONE Context's), each laid out like a shared context, the layouts repeating
+        like context images; whole_digest is implied, digest d of the pass is digest d % M of Context d // M."""
         self.engine = engine
-        self.whole_digest = bool(whole_digest)
+        self.n_contexts = None if n_contexts is None else int(n_contexts)
+        self.whole_digest = bool(whole_digest) or n_contexts is not None
         self.context_images = bool(context_images)
         self.lib = engine.lib
         self.max_variable_byte_sizes = list(max_variable_byte_sizes)
         arr = (C.c_size_t * max(len(self.max_variable_byte_sizes), 1))(*self.max_variable_byte_sizes)
         h = C.c_void_p()
-        rc = self.lib.hsw_gadget_create_ex(engine.h, arr, len(self.max_variable_byte_sizes),
-                                           1 if is_input_range_check else 0,
-                                           (N.HSW_GADGET_WHOLE_DIGEST if whole_digest else 0) |
-                                           (N.HSW_GADGET_INDEPENDENT if independent else 0) |
-                                           (N.HSW_GADGET_CONTEXT_IMAGES if context_images else 0) |
-                                           (N.HSW_GADGET_SHARED_CONTEXT if shared_context else 0), C.byref(h))
+        flags = ((N.HSW_GADGET_WHOLE_DIGEST if self.whole_digest else 0) |
+                 (N.HSW_GADGET_INDEPENDENT if independent else 0) |
+                 (N.HSW_GADGET_CONTEXT_IMAGES if context_images else 0) |
+                 (N.HSW_GADGET_SHARED_CONTEXT if shared_context else 0))
+        if n_contexts is not None:
+            rc = self.lib.hsw_gadget_create_contexts(engine.h, arr, len(self.max_variable_byte_sizes), self.n_contexts,
+                                                     1 if is_input_range_check else 0, flags, C.byref(h))
+        else:
+            rc = self.lib.hsw_gadget_create_ex(engine.h, arr, len(self.max_variable_byte_sizes),
+                                               1 if is_input_range_check else 0, flags, C.byref(h))
         if rc != N.HSW_OK:
             raise N.HswError(rc, self.lib.hsw_last_error(engine.h).decode())
         self.h = h
@@ -139,6 +147,8 @@ class Sha256DynamicConfig:
     def _image_shape(self, v):
         """Shape of the gate image: (columns, max_rows), or (K, columns, max_rows) with context images."""
         cr = (int(v.columns), int(v.max_rows))
+        if self.n_contexts is not None:
+            return (self.n_contexts,) + cr
         return (len(self.max_variable_byte_sizes),) + cr if self.context_images else cr
 
     def download_region(self, pinned=True):
@@ -253,7 +263,7 @@ class Sha256DynamicConfig:
         self._n = hash_idx
 
     def context_region(self, h):
-        """hsw_gadget_context_region: where proof h lives on the device (context-image gadgets)."""
+        """hsw_gadget_context_region: where proof h lives on the device (context-image gadgets and Context groups)."""
         r = N.ContextRegion()
         self._ok(self.lib.hsw_gadget_context_region(self.h, h, C.byref(r)))
         return r
@@ -284,8 +294,8 @@ class Sha256DynamicConfig:
             return a
 
         rows = (int(v.num_limb_sum) + ncols - 1) // ncols
-        if self.context_images and int(v.max_rows):       # (K, columns, max_rows, 4): one image per proof
-            k = len(self.max_variable_byte_sizes)
+        if (self.context_images or self.n_contexts is not None) and int(v.max_rows):   # (K, columns, max_rows, 4): one image per proof
+            k = self.n_contexts if self.n_contexts is not None else len(self.max_variable_byte_sizes)
             gate = grab(v.d_gate, k * int(v.max_rows) * int(v.columns)).reshape(k, int(v.columns), int(v.max_rows), 4)
         elif self.whole_digest and int(v.max_rows):
             gate = grab(v.d_gate, int(v.max_rows) * int(v.columns)).reshape(int(v.columns), int(v.max_rows), 4)

@@ -361,7 +361,10 @@ typedef struct hsw_launch_info {
     uint32_t parts;        /* waves per block */
     uint32_t split;        /* 0: every wave takes a share of every phase; 1: one phase program per wave;
                               2: one sub-unit program per wave (tiny batches) */
-    uint32_t reserved_;
+    uint32_t seq;          /* expansion launches of this engine so far (wraps): the difference across a call is the
+                              number of expansion launches that call made.  Counts every launch of the streaming and
+                              of the small-batch kernel, in every mode -- a call of more than 2^20 blocks is one launch
+                              per chunk; frame, chain and verify launches are not counted.  (Was reserved_, always 0.) */
     uint64_t n_blocks;     /* blocks of that launch */
     uint64_t grid;         /* workgroups (= waves) of that launch */
 } hsw_launch_info;
@@ -584,6 +587,40 @@ int hsw_gadget_create(hsw_engine *e, const size_t *max_variable_byte_sizes, size
 #define HSW_GADGET_MAX_COLUMNS 1024u
 int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, size_t n_hashes,
                          int is_input_range_check, uint32_t flags, hsw_gadget **out);
+/* A Context group: n_contexts Contexts (proofs) of ONE circuit that makes digests_per_context digests -- the
+ * reference's Sha256DynamicConfig with max_variable_byte_sizes of that length (lib.rs:40-43,86,347), synthesized K
+ * times.  max_variable_byte_sizes lists ONE Context's M = digests_per_context sizes.  Every Context is laid out
+ * exactly like a HSW_GADGET_SHARED_CONTEXT gadget of those M sizes (one zero cell, one lookup queue, one run of chip
+ * rows, interludes between its digests, up to HSW_GADGET_MAX_COLUMNS columns), and the K layouts repeat like
+ * HSW_GADGET_CONTEXT_IMAGES: with S = columns x max_rows and Lp = one Context's whole lookup queue (the caller's
+ * queued and interlude entries included), Context c's image is cells [c*S, (c+1)*S) of d_gate, its lookup column
+ * cells [c*Lp, (c+1)*Lp) of d_lookup, and its chip rows follow Context c-1's.
+ *   flags          must contain HSW_GADGET_WHOLE_DIGEST (HSW_GADGET_SHARED_CONTEXT may be named too); any other bit,
+ *                  digests_per_context = 0, n_contexts = 0 or an engine not in HSW_MODE_HALO2_INTERNALS:
+ *                  HSW_ERR_INVALID_ARG.  Engines with the 8-bit spread table only (HSW_ERR_UNSUPPORTED), and one
+ *                  Context's blocks x limb_calls_per_block must be a multiple of num_advice_columns
+ *                  (HSW_ERR_UNSUPPORTED, as for HSW_GADGET_INDEPENDENT).
+ *   pass order     digest d = c*M + j of the pass is digest j of Context c.  hsw_gadget_digest /
+ *                  hsw_gadget_digest_batch take any n -- a batch may start or end in the middle of a Context -- and
+ *                  a pass issued digest by digest, as one batch or in any split writes the same bytes.  A batch
+ *                  costs one expansion launch per digest index it holds (M, not K*M) and one frame launch.
+ *                  hsw_gadget_set_columns must have been called (HSW_ERR_UNSUPPORTED from the digest calls before).
+ *   layout calls   hsw_gadget_set_columns, hsw_gadget_set_origin and hsw_gadget_set_digest_origin(g, j, ...) with
+ *                  1 <= j < M describe ONE Context and apply to every Context alike; a call that fails leaves layout
+ *                  and buffers as they were.  A call that changes the layout replaces the K images and lookup
+ *                  columns by zeroed ones (device pointers from earlier queries are stale); the same declaration
+ *                  again, pass after pass, keeps layout, buffers, region tape and the device's jump table.
+ *   queries        hsw_gadget_context_region(g, c, ...) describes Context c (assigned: all M digests are).
+ *                  hsw_hash_result gate cells are gadget-stream indices, the K Context streams (stream_cells each)
+ *                  back to back; its lookup indices are d_lookup cells.  hsw_gadget_cell_position /
+ *                  hsw_gadget_result_cells map into the owning Context's image, after its jumps.
+ *   deliveries     hsw_gadget_download_region (K images back to back, used cells only), hsw_gadget_region_tape,
+ *                  hsw_gadget_download_region_distinct, hsw_gadget_replay_region and hsw_gadget_verify work.  Rows
+ *                  above the origin, interlude cells and the caller's lookup entries of EVERY Context are the
+ *                  caller's: never written on the device, never touched in host buffers.
+ *   refusals       hsw_gadget_seek, hsw_gadget_download_region_compact and hsw_gadget_place: HSW_ERR_UNSUPPORTED. */
+int hsw_gadget_create_contexts(hsw_engine *e, const size_t *max_variable_byte_sizes, size_t digests_per_context,
+                               size_t n_contexts, int is_input_range_check, uint32_t flags, hsw_gadget **out);
 void hsw_gadget_destroy(hsw_gadget *g);
 /* HSW_GADGET_WHOLE_DIGEST, before the first digest: lay the gate stream out as the
  * FlexGate (Vertical) advice columns themselves -- column c = cells [c*max_rows,
@@ -749,6 +786,7 @@ typedef struct hsw_context_region {
     uint32_t assigned;                  /* 1 once proof h has been digested in this synthesis pass */
     uint32_t reserved_;
 } hsw_context_region;
+/* (hsw_gadget_create_contexts gadgets: h counts Contexts; chip_rows are the rows of its M digests, assigned = all M are) */
 int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region *out);
 /* Sha256DynamicConfig::digest (lib.rs:71-349); precomputed_input_len 0 = None.
  * Synchronous: returns once the streams of this hash are in HBM. */

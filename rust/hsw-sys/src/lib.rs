@@ -85,7 +85,8 @@ pub struct hsw_launch_info {
     pub internals: u32,
     pub parts: u32,
     pub split: u32,
-    pub reserved_: u32,
+    /// expansion launches of this engine so far (wraps)
+    pub seq: u32,
     pub n_blocks: u64,
     pub grid: u64,
 }
@@ -396,6 +397,10 @@ extern "C" {
                               init_state_out: *mut u32, info: *mut hsw_digest_info) -> c_int;
     pub fn hsw_gadget_create(e: *mut hsw_engine, max_variable_byte_sizes: *const usize, n_hashes: usize,
                              is_input_range_check: c_int, out: *mut *mut hsw_gadget) -> c_int;
+    /// K Contexts (proofs) of one circuit with M digests each (a Context group, include/hsw.h).
+    pub fn hsw_gadget_create_contexts(e: *mut hsw_engine, max_variable_byte_sizes: *const usize, digests_per_context: usize,
+                                      n_contexts: usize, is_input_range_check: c_int, flags: u32,
+                                      out: *mut *mut hsw_gadget) -> c_int;
     pub fn hsw_gadget_create_ex(e: *mut hsw_engine, max_variable_byte_sizes: *const usize, n_hashes: usize,
                                 is_input_range_check: c_int, flags: u32, out: *mut *mut hsw_gadget) -> c_int;
     pub fn hsw_gadget_destroy(g: *mut hsw_gadget);

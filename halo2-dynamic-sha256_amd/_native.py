@@ -173,6 +173,14 @@ class GadgetView(C.Structure):
                 ("origin_zero_loaded", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class RegionBinding(C.Structure):
+    """hsw_region_binding: caller-owned device columns a gadget's region is bound to, pitches in cells."""
+    _fields_ = [("d_columns", C.c_void_p), ("column_pitch", C.c_uint64), ("columns_capacity", C.c_uint64), ("context_pitch", C.c_uint64),
+                ("d_lookup", C.c_void_p), ("lookup_capacity", C.c_uint64), ("lookup_pitch", C.c_uint64),
+                ("d_chip_dense", C.c_void_p), ("d_chip_spread", C.c_void_p), ("chip_col_stride", C.c_uint64),
+                ("chip_rows_capacity", C.c_uint64), ("chip_context_pitch", C.c_uint64)]
+
+
 class ContextRegion(C.Structure):
     """hsw_context_region: where proof h of an HSW_GADGET_CONTEXT_IMAGES gadget lives on the device."""
     _fields_ = [("d_image", C.c_void_p), ("d_lookup", C.c_void_p), ("d_chip_dense", C.c_void_p), ("d_chip_spread", C.c_void_p)] + \
@@ -200,6 +208,7 @@ SYMBOLS = (
     "hsw_gadget_download_region_compact", "hsw_region_widen", "hsw_gadget_result_cells",
     "hsw_gadget_set_origin", "hsw_gadget_region_tape", "hsw_gadget_download_region_distinct", "hsw_gadget_replay_region",
     "hsw_gadget_context_region", "hsw_gadget_set_digest_origin", "hsw_gadget_create_contexts",
+    "hsw_gadget_bind_region", "hsw_gadget_region_binding",
 )
 
 
@@ -351,6 +360,10 @@ def lib():
         L.hsw_gadget_set_digest_origin.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint64]
         L.hsw_gadget_context_region.restype = C.c_int
         L.hsw_gadget_context_region.argtypes = [vp, C.c_size_t, C.POINTER(ContextRegion)]
+        L.hsw_gadget_bind_region.restype = C.c_int
+        L.hsw_gadget_bind_region.argtypes = [vp, C.POINTER(RegionBinding)]
+        L.hsw_gadget_region_binding.restype = C.c_int
+        L.hsw_gadget_region_binding.argtypes = [vp, C.POINTER(RegionBinding)]
         L.hsw_gadget_create_contexts.restype = C.c_int
         L.hsw_gadget_create_contexts.argtypes = [vp, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_int, C.c_uint32,
                                                  C.POINTER(vp)]

@@ -400,7 +400,8 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
         if (!d_chip_dense || !d_chip_spread || ((uintptr_t)d_chip_dense & 15u) ||
             ((uintptr_t)d_chip_spread & 15u))
             return set_err(e, HSW_ERR_INVALID_ARG, "chip buffers null or not 16-byte aligned");
-        if (chip_col_stride < hsw_chip_rows(&e->shape, spread_cursor0, n_blocks))
+        // (a bound region keeps every Context's chip rows in a place of its own: checked per Context when it was bound)
+        if (!(period && period->chip_rows_checked) && chip_col_stride < hsw_chip_rows(&e->shape, spread_cursor0, n_blocks))
             return set_err(e, HSW_ERR_INVALID_ARG, "chip_col_stride smaller than hsw_chip_rows()");
     }
     if (args->d_lookup && e->mode != HSW_MODE_HALO2_INTERNALS)
@@ -470,6 +471,7 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
         p.frame_cells = args->frame_cells;
         p.frame_lookups = args->frame_lookups;
         p.ctx_cells = period ? period->image_cells : 0;
+        p.chip_ctx_extra = period ? period->chip_ctx_extra : 0;
         const int tile = choose_tile(e, flags);
         p.parts = (uint32_t)choose_parts(e, n_blocks, tile, flags);
         // tiny batches are latency-bound: the small-batch kernel (37 waves per block, one sub-unit program

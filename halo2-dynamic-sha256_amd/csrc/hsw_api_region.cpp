@@ -169,7 +169,8 @@ int hsw_verify_blocks_impl(hsw_engine *e, const hsw_witness_args *args, hsw_veri
         return set_err(e, HSW_ERR_INVALID_ARG, "stream buffers must be 16-byte aligned");
     if (((uintptr_t)args->d_blocks & 3u) || ((uintptr_t)args->d_pre_states & 3u) || ((uintptr_t)args->d_next_states & 3u))
         return set_err(e, HSW_ERR_INVALID_ARG, "inputs must be 4-byte aligned");
-    if (args->d_chip_dense && args->chip_col_stride < hsw_chip_rows(&e->shape, args->spread_cursor0, args->n_blocks))
+    if (args->d_chip_dense && !(period && period->chip_rows_checked) &&
+        args->chip_col_stride < hsw_chip_rows(&e->shape, args->spread_cursor0, args->n_blocks))
         return set_err(e, HSW_ERR_INVALID_ARG, "chip_col_stride smaller than hsw_chip_rows()");
     DeviceScope ds(e->device);
     if (!ds.ok) return set_err(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
@@ -184,6 +185,7 @@ int hsw_verify_blocks_impl(hsw_engine *e, const hsw_witness_args *args, hsw_veri
     p.gate_cell0 = p.lookup_cell0 = 0;
     p.frame_every = args->frame_every; p.frame_cells = args->frame_cells; p.frame_lookups = args->frame_lookups;
     p.ctx_cells = period ? period->image_cells : 0;
+    p.chip_ctx_extra = period ? period->chip_ctx_extra : 0;
     p.n_breaks = args->pack ? args->pack->n_breaks : 0;
     for (uint32_t k = 0; k < p.n_breaks; k++) { p.break_cell[k] = args->pack->break_cell[k]; p.break_gap[k] = args->pack->break_gap[k]; }
     p.report = e->d_report;

@@ -318,6 +318,9 @@ struct Em {
     u32 lk_first;      // block-relative index of the phase-part's first lookup cell
     u32 lks;           // lookup cells staged by this phase-part
     const uint4 *tab;  // M32: ExpandParams.mont_tab
+    // bound regions (ExpandParams::chip_ctx_extra): cells from where consecutive rows would put this block's chip
+    // rows to where its Context's own chip rows lie (wave-uniform; 0 unless every Context has chip rows of its own)
+    u64 chip_off;
 };
 
 // entry idx of ExpandParams.mont_tab (M32): Montgomery form of i | spread(i) | i << 8 at 0 | 256 | 512 + i
@@ -879,7 +882,7 @@ DEV void flush_chip(const EM &em, const ExpandParams &p, u64 block_first_limb) {
         const u32 count = (u32)(row_hi - row_lo + 1);
         const u32 n0 = (u32)(row_lo * ncols + c - first);              // run-relative limb index of row_lo
         // wave-uniform column run base + 32-bit lane offsets
-        const size_t cell0 = (size_t)c * p.chip_col_stride + (size_t)(row_lo - row0);
+        const size_t cell0 = (size_t)c * p.chip_col_stride + (size_t)(row_lo - row0) + (size_t)em.chip_off;
         constexpr u32 CB = EM::COMPACT ? 8u : 32u;
         char *cdb = reinterpret_cast<char *>(p.chip_dense) + cell0 * CB;
         char *csb = reinterpret_cast<char *>(p.chip_spread) + cell0 * CB;
@@ -1473,12 +1476,14 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
     em.head = s_head;
     em.d16 = s_d16;
     em.tab = static_cast<const uint4 *>(p.mont_tab);
+    em.chip_off = 0;
     {   // FlexGate column packing: gaps of the breaks at or before this block, and the (<= 2) inside it
         u64 first = (u64)blk * (u64)LY::GATE_CELLS, ctx_base = 0;
         if constexpr (RC)          // whole-digest streams: every frame_every blocks a digest frame sits in between
             if (p.frame_every) {
                 u32 ctx;                                             // wave-uniform (blk is the workgroup's block)
                 if constexpr (TABLE) ctx = tctx; else ctx = (u32)blk / (u32)p.frame_every;
+                em.chip_off = (u64)ctx * p.chip_ctx_extra;           // every Context's chip rows in its own place (bound regions)
                 if (p.ctx_cells) {     // context images: the breaks are one context's, the image of context ctx follows ctx_cells further
                     first -= (u64)ctx * (u64)p.frame_every * (u64)LY::GATE_CELLS;
                     ctx_base = (u64)ctx * p.ctx_cells;

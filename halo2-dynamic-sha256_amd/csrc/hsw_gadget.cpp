@@ -238,9 +238,9 @@ std::vector<std::pair<uint64_t, uint64_t>> Sha256DynamicConfig::load() const {
 }
 
 Context::~Context() {
-    (void)hipFree(d_gate); (void)hipFree(d_chip_dense); (void)hipFree(d_chip_spread);
+    if (!bound) { (void)hipFree(d_gate); (void)hipFree(d_chip_dense); (void)hipFree(d_chip_spread); (void)hipFree(d_lookup); }
     (void)hipFree(d_next_states); (void)hipFree(d_blocks); (void)hipFree(d_pre_states);
-    (void)hipFree(d_init_states); (void)hipFree(d_offsets); (void)hipFree(d_lookup); (void)hipFree(d_place);
+    (void)hipFree(d_init_states); (void)hipFree(d_offsets); (void)hipFree(d_place);
     if (hp_blocks) (void)hipHostFree(hp_blocks);
     free_compact_staging();
 }
@@ -377,6 +377,13 @@ int Context::plan_layout(const std::vector<size_t> &sizes, bool rc_inputs, uint6
 int Context::adopt(Layout &nl, bool fresh_image, bool fresh_lookup, uint64_t clear_from) {
     const size_t K = contexts(), none = ~(size_t)0;
     const bool table = shared && nl.max_rows, changed = !nl.same_map(layout);
+    if (bound) {                                          // the caller's memory: it fits what was declared, or it does not
+        if (nl.columns > binding.columns_capacity || lookups_needed(nl) > binding.lookup_capacity) return HSW_ERR_TOO_LARGE;
+        layout = std::move(nl);
+        lookup_capacity = (uint64_t)(K - 1) * lookup_pitch() + binding.lookup_capacity;
+        place_dirty = place_dirty || changed;
+        return HSW_OK;
+    }
     size_t img_cells = none, img_keep = 0, lk_cells = none, lk_keep = 0;
     if (table && group_m) {
         // a Context group: K images and K lookup columns whose places follow from one Context's size -- a layout
@@ -423,6 +430,7 @@ int Context::set_columns(const std::vector<size_t> &sizes, bool rc_inputs, uint6
     const uint64_t G = shape.gate_cells_per_block;
     if (rows < G + 16) return HSW_ERR_INVALID_ARG;        // keeps a block inside <= 2 columns (kernel: <= 2 breaks per block)
     if (layout.origin_row >= rows) return HSW_ERR_INVALID_ARG;   // the Context's next free row lies inside its column
+    if (bound && rows > layout.pitch) return HSW_ERR_TOO_LARGE;  // a bound column holds column_pitch cells at most
     Layout nl = layout.origin();
     // (shared context -- a new layout: the declarations made for the old one are dropped)
     const std::vector<DigestOrigin> none(declared.size());
@@ -469,7 +477,7 @@ int Context::set_origin(const std::vector<size_t> &sizes, bool rc_inputs, uint64
     // the new layout, checked in full: nothing is touched if it cannot be had.  The column breaks follow from where
     // the stream starts: a new row, or a zero cell that comes or goes, lays the image out again (a fresh image); a
     // shared context drops its declarations and has every cell of an earlier layout zeroed
-    Layout nl;
+    Layout nl = layout.origin();                          // (in the same memory: a bound region's pitches stay)
     nl.origin_column = column; nl.origin_row = row; nl.origin_lookups = lookups_queued; nl.origin_zero_loaded = zero_cell_loaded;
     const std::vector<DigestOrigin> none(declared.size());
     const int rc = plan_layout(sizes, rc_inputs, layout.max_rows, none, &nl);
@@ -480,6 +488,81 @@ int Context::set_origin(const std::vector<size_t> &sizes, bool rc_inputs, uint64
     declared = none;
     lookup_cursor = lookups_queued;
     zero_loaded = zero_cell_loaded;                       // (without the zero cell the stream is one cell shorter)
+    return HSW_OK;
+}
+
+int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b) {
+    const uint64_t K = contexts();
+    const void *ptrs[4] = {b.d_columns, b.d_lookup, b.d_chip_dense, b.d_chip_spread};
+    // (128 bytes: a column that starts on a line boundary keeps the realigned write-out on whole lines)
+    for (const void *p : ptrs)
+        if (!p || ((uintptr_t)p & 127u)) return HSW_ERR_INVALID_ARG;
+    // (a block's cells are addressed by 32-bit byte offsets from its first, the gaps of <= 2 column breaks included)
+    if (b.column_pitch < layout.max_rows || b.column_pitch > (1ull << 24)) return HSW_ERR_INVALID_ARG;
+    if (b.chip_col_stride < b.chip_rows_capacity) return HSW_ERR_INVALID_ARG;
+    if (K > 1) {
+        if (b.columns_capacity > ~0ull / b.column_pitch || b.context_pitch < b.columns_capacity * b.column_pitch) return HSW_ERR_INVALID_ARG;
+        if (b.lookup_pitch < b.lookup_capacity) return HSW_ERR_INVALID_ARG;
+        if (b.context_pitch > ~0ull / (K * HSW_CELL_BYTES) || b.lookup_pitch > ~0ull / (K * HSW_CELL_BYTES) ||
+            b.chip_context_pitch > ~0ull / (K * HSW_CELL_BYTES))
+            return HSW_ERR_INVALID_ARG;
+    }
+    Layout nl = layout.origin();
+    nl.pitch = b.column_pitch;
+    nl.image_pitch = K > 1 ? b.context_pitch : 0;
+    const int rc = plan_layout(sizes, rc_inputs, layout.max_rows, declared, &nl);
+    if (rc != HSW_OK) return rc;
+    if (nl.columns > b.columns_capacity || lookups_needed(nl) > b.lookup_capacity || ctx_chip_rows() > b.chip_rows_capacity) return HSW_ERR_TOO_LARGE;
+    // (the caller ran on a drained engine: nothing still writes the buffers given up here)
+    if (!bound) {
+        int device = 0;
+        hsw_engine_stream(engine, nullptr, &device);
+        DeviceScope ds(device);
+        if (!ds.ok) return HSW_ERR_NO_DEVICE;
+        (void)hipFree(d_gate); (void)hipFree(d_lookup); (void)hipFree(d_chip_dense); (void)hipFree(d_chip_spread);
+    }
+    free_compact_staging();
+    bound = true;
+    binding = b;
+    d_gate = b.d_columns; d_lookup = b.d_lookup; d_chip_dense = b.d_chip_dense; d_chip_spread = b.d_chip_spread;
+    chip_col_stride = (size_t)b.chip_col_stride;
+    image_columns = b.columns_capacity;
+    layout = std::move(nl);
+    lookup_capacity = (K - 1) * lookup_pitch() + b.lookup_capacity;
+    place_dirty = true;
+    return HSW_OK;
+}
+
+int Context::unbind(const std::vector<size_t> &sizes, bool rc_inputs) {
+    if (!bound) return HSW_OK;
+    const size_t K = contexts();
+    Layout nl = layout.origin();
+    nl.pitch = nl.image_pitch = 0;
+    const int rc = plan_layout(sizes, rc_inputs, layout.max_rows, declared, &nl);
+    if (rc != HSW_OK) return rc;
+    int device = 0;
+    hsw_engine_stream(engine, nullptr, &device);
+    DeviceScope ds(device);
+    if (!ds.ok) return HSW_ERR_NO_DEVICE;
+    // what a fresh gadget with this layout owns (new_context, adopt)
+    const size_t stride = (size_t)hsw_chip_rows(&shape, 0, capacity_blocks);
+    const size_t col_bytes = (size_t)shape.num_advice_columns * (stride ? stride : 1) * HSW_CELL_BYTES;
+    const size_t lk_cells = shared && group_m ? K * (size_t)nl.lookups_end : shared ? (size_t)std::max(nl.lookups_end, own_lookup_capacity)
+                                                                                   : (size_t)own_lookup_capacity + K * (size_t)nl.origin_lookups;
+    void *img = nullptr, *lk = nullptr, *cd = nullptr, *cs = nullptr;
+    hipError_t he = fresh_zeroed(&img, K * (size_t)nl.image_cells() * HSW_CELL_BYTES);
+    if (he == hipSuccess) he = fresh_zeroed(&lk, lk_cells * HSW_CELL_BYTES);
+    if (he == hipSuccess) he = fresh_zeroed(&cd, col_bytes);
+    if (he == hipSuccess) he = fresh_zeroed(&cs, col_bytes);
+    if (he != hipSuccess) { (void)hipFree(img); (void)hipFree(lk); (void)hipFree(cd); (void)hipFree(cs); return hip_status(he); }
+    bound = false;
+    binding = hsw_region_binding{};
+    d_gate = img; d_lookup = lk; d_chip_dense = cd; d_chip_spread = cs;
+    chip_col_stride = stride;
+    image_columns = nl.columns;
+    lookup_capacity = lk_cells;
+    layout = std::move(nl);
+    place_dirty = true;
     return HSW_OK;
 }
 
@@ -513,11 +596,13 @@ struct Launch {
                 tbl.ctx_blocks = c.ctx_blocks; tbl.ctx_stream = l.period; tbl.ctx_image = l.image_cells();
                 period.stream_cells = l.period; period.image_cells = l.image_cells();
             }
+            period.chip_ctx_extra = c.chip_ctx_extra(); period.chip_rows_checked = c.bound;
         } else if (l.max_rows) {
             abs.n_breaks = (uint32_t)l.break_cell.size();
             for (size_t k = 0; k < abs.n_breaks; k++) { abs.break_cell[k] = l.break_cell[k]; abs.break_gap[k] = l.break_gap[k]; }
             frame_pack = &abs;
             if (l.period) { period = ContextPeriod{l.period, l.image_cells()}; per = &period; }
+            period.chip_ctx_extra = c.chip_ctx_extra(); period.chip_rows_checked = c.bound;
         }
     }
     Launch(const Launch &) = delete;
@@ -529,7 +614,8 @@ struct Launch {
         a = hsw_witness_args{};
         a.d_blocks = in_blocks + 64 * first_block; a.d_pre_states = in_pre + 8 * first_block; a.n_blocks = n_blocks;
         a.spread_cursor0 = (uint64_t)first_block * c.shape.limb_calls_per_block;
-        const size_t row_shift = (size_t)(a.spread_cursor0 / c.shape.num_advice_columns);
+        // (a bound region: the chip rows of the launch's first Context, where the caller keeps that Context's)
+        const size_t row_shift = (size_t)c.chip_cell(a.spread_cursor0 - a.spread_cursor0 % c.shape.num_advice_columns);
         a.d_gate = static_cast<uint8_t *>(c.d_gate) + first_block * (size_t)c.shape.gate_cells_per_block * cb;
         a.d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + row_shift * cb;
         a.d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + row_shift * cb;
@@ -552,10 +638,10 @@ struct Launch {
         // between the block streams of two digests: one epilogue, the next prologue -- and the next Context's zero cell
         // when every digest is a Context of its own, and (context images) its caller-owned lookup cells
         a.frame_cells = fs.epilogue_cells + fs.prologue_cells + (c.independent && !l.origin_zero_loaded ? 1u : 0u);
-        a.frame_lookups = fs.epilogue_lookups + fs.prologue_lookups + (c.context_images ? l.origin_lookups : 0u);
+        a.frame_lookups = fs.epilogue_lookups + fs.prologue_lookups + (c.context_images ? l.origin_lookups + (c.lookup_pitch() - c.ctx_lookups()) : 0u);
         // (a Context group: the "digests" of the run are the SAME digest index of consecutive Contexts, whose lookup
         //  columns lie ctx_lookups() apart and whose blocks ctx_blocks apart -- PlaceTable::ctx_blocks)
-        if (c.group_m) a.frame_lookups = c.ctx_lookups() - (uint64_t)fs.n_blocks * c.shape.lookup_cells_per_block;
+        if (c.group_m) a.frame_lookups = c.lookup_pitch() - (uint64_t)fs.n_blocks * c.shape.lookup_cells_per_block;
         if (period.place) {                              // the run's first block cell, its digests' lookup shifts
             tbl.base = local;
             tbl.lk_shift = tbl.cell + 2 * tbl.n + (c.group_m ? digest0 % c.group_m : digest0);
@@ -730,12 +816,13 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 d.precomputed_round = (uint32_t)plans[i].precomputed_round;
                 d.is_input_range_check = is_input_range_check ? 1u : 0u;
                 // context images: Context h's lookup column is cells [h*Lp, (h+1)*Lp), the caller's queued cells first
-                if (ctx.context_images) lc = (uint64_t)(cur_hash_idx + i) * ctx.ctx_lookups() + ctx.layout.origin_lookups;
+                // (lookup_pitch() apart: Lp, or what the caller bound)
+                if (ctx.context_images) lc = (uint64_t)(cur_hash_idx + i) * ctx.lookup_pitch() + ctx.layout.origin_lookups;
                 if (table && !ctx.group_m) lc = ctx.layout.digest_lookup0[cur_hash_idx + i];   // after the caller's entries of the interlude
                 if (ctx.group_m) {                           // digest j of Context cx: that Context's stream, image and lookup column
                     const size_t cx = (cur_hash_idx + i) / ctx.group_m, j = (cur_hash_idx + i) % ctx.group_m;
                     gc = cx * ctx.layout.period + ctx.layout.digest_cell0[j];
-                    lc = cx * ctx.ctx_lookups() + ctx.layout.digest_lookup0[j];
+                    lc = cx * ctx.lookup_pitch() + ctx.layout.digest_lookup0[j];
                     zero_loaded = j != 0 || ctx.layout.origin_zero_loaded;
                 }
                 r.prologue_cell = d.prologue_cell = gc;      gc += fss[i].prologue_cells;
@@ -1053,6 +1140,40 @@ int hsw_gadget_set_digest_origin(hsw_gadget *g, size_t h, uint64_t column, uint6
     return HSW_OK;
 } HSW_NO_UNWIND
 
+int hsw_gadget_bind_region(hsw_gadget *g, const hsw_region_binding *b) try {
+    if (!g) return HSW_ERR_INVALID_ARG;
+    hsw::Context &c = *g->ctx;
+    // a whole-digest gadget with a column image (K linear regions in one stream, block streams: nothing to bind)
+    if (!c.whole || !c.layout.max_rows) return HSW_ERR_UNSUPPORTED;
+    if (g->cfg.cur_hash_idx != 0 || c.blocks_done != 0 || c.gate_cursor != 0) return HSW_ERR_INVALID_ARG;   // a fresh or reset gadget
+    int rc = hsw_engine_synchronize(c.engine);           // buffers change hands: nothing may still write the old ones
+    if (rc != HSW_OK) return rc;
+    rc = b ? c.bind(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, *b)
+           : c.unbind(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check);
+    if (rc == HSW_OK) hsw::drop_region_tape_positions(g->tape);     // image positions follow the pitches
+    return rc;
+} HSW_NO_UNWIND
+
+int hsw_gadget_region_binding(const hsw_gadget *g, hsw_region_binding *out) try {
+    if (!g || !out) return HSW_ERR_INVALID_ARG;
+    const hsw::Context &c = *g->ctx;
+    if (c.bound) { *out = c.binding; return HSW_OK; }
+    const bool many = c.contexts() > 1;
+    std::memset(out, 0, sizeof *out);
+    out->d_columns = c.d_gate;
+    out->column_pitch = c.layout.column_pitch();
+    out->columns_capacity = c.shared && !c.group_m && c.image_columns ? c.image_columns : c.layout.columns;
+    out->context_pitch = c.layout.image_cells();
+    out->d_lookup = c.d_lookup;
+    out->lookup_capacity = many ? c.ctx_lookups() : c.lookup_capacity;
+    out->lookup_pitch = c.lookup_pitch();
+    out->d_chip_dense = c.d_chip_dense; out->d_chip_spread = c.d_chip_spread;
+    out->chip_col_stride = c.chip_col_stride;
+    out->chip_rows_capacity = many ? c.ctx_chip_rows() : c.chip_col_stride;
+    out->chip_context_pitch = c.ctx_chip_rows();         // consecutive rows of the same columns
+    return HSW_OK;
+} HSW_NO_UNWIND
+
 int hsw_gadget_reset(hsw_gadget *g) try {
     if (!g) return HSW_ERR_INVALID_ARG;
     const int rc = hsw_engine_synchronize(g->ctx->engine);
@@ -1076,6 +1197,7 @@ int hsw_gadget_place(hsw_gadget *g, unsigned candidates, float *ms_each, unsigne
     if (!g || candidates == 0 || candidates > 16) return HSW_ERR_INVALID_ARG;
     hsw::Context &c = *g->ctx;
     if (c.shared) return HSW_ERR_UNSUPPORTED;                     // (its trial batch would run over the declared interludes)
+    if (c.bound) return HSW_ERR_UNSUPPORTED;                      // (the chip columns are the caller's: nothing to place)
     if (g->cfg.cur_hash_idx != 0 || c.blocks_done != 0) return HSW_ERR_INVALID_ARG;      // a fresh or reset gadget
     const size_t n = g->cfg.max_variable_byte_sizes.size();
     if (n == 0) return HSW_ERR_INVALID_ARG;
@@ -1178,12 +1300,12 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
         copy(dst->gate, c.d_gate, 0, cells);
     }
     if (dst->lookup && c.d_lookup && c.context_images) {
-        const uint64_t Lp = c.ctx_lookups();               // Context h: its own entries after the caller's queued cells
+        const uint64_t Lp = c.lookup_pitch();              // Context h: its own entries after the caller's queued cells
         for (uint64_t h = 0; h < g->cfg.cur_hash_idx; h++)
             copy(dst->lookup, c.d_lookup, (size_t)(h * Lp + c.layout.origin_lookups), (size_t)c.ctx_own_lookups);
     } else if (dst->lookup && c.d_lookup && c.shared && !c.layout.digest_lookup0.empty()) {
         const size_t M = c.group_m ? c.group_m : c.layout.digest_entry0.size();
-        const uint64_t own = c.group_m ? c.ctx_own_lookups : c.own_lookup_capacity, Lp = c.group_m ? c.ctx_lookups() : 0;
+        const uint64_t own = c.group_m ? c.ctx_own_lookups : c.own_lookup_capacity, Lp = c.group_m ? c.lookup_pitch() : 0;
         for (size_t d = 0; d < g->cfg.cur_hash_idx; d++) {     // every digest's own entries; the interludes' are the caller's
             const size_t h = d % M, cx = d / M;                 // (a Context group: digest h of Context cx, in its own lookup column)
             const uint64_t end = h + 1 < c.layout.digest_entry0.size() ? c.layout.digest_entry0[h + 1] : own;
@@ -1193,10 +1315,15 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
         copy(dst->lookup, c.d_lookup, (size_t)c.layout.origin_lookups, (size_t)(c.lookup_cursor - c.layout.origin_lookups));
     }
     const uint32_t ncols = c.shape.num_advice_columns;
-    const size_t rows = (size_t)((c.num_limb_sum + ncols - 1) / ncols);
-    for (uint32_t k = 0; k < ncols; k++) {
-        if (dst->chip_dense) copy(dst->chip_dense, c.d_chip_dense, k * c.chip_col_stride, rows);
-        if (dst->chip_spread) copy(dst->chip_spread, c.d_chip_spread, k * c.chip_col_stride, rows);
+    // the used rows of every chip column -- of every Context begun, where each has chip rows of its own (a bound region)
+    const uint64_t per = c.chip_ctx_extra() ? c.ctx_limb_calls() : c.num_limb_sum ? c.num_limb_sum : 1;
+    for (uint64_t n0 = 0; n0 < c.num_limb_sum; n0 += per) {
+        const uint64_t n1 = n0 + per < c.num_limb_sum ? n0 + per : c.num_limb_sum;
+        const size_t rows = (size_t)((n1 - n0 + ncols - 1) / ncols), row0 = (size_t)c.chip_cell(n0);
+        for (uint32_t k = 0; k < ncols; k++) {
+            if (dst->chip_dense) copy(dst->chip_dense, c.d_chip_dense, k * c.chip_col_stride + row0, rows);
+            if (dst->chip_spread) copy(dst->chip_spread, c.d_chip_spread, k * c.chip_col_stride + row0, rows);
+        }
     }
     if (he == hipSuccess) he = hipStreamSynchronize(stream);
     return he == hipSuccess ? HSW_OK : HSW_ERR_HIP;
@@ -1208,6 +1335,7 @@ int hsw_gadget_download_region_compact(hsw_gadget *g, hsw_region_compact *dst) t
     if (c.repr_flags != HSW_REPR_CANONICAL) return HSW_ERR_UNSUPPORTED;      // packs canonical 32-byte cells
     if (c.context_images) return HSW_ERR_UNSUPPORTED;                         // one image per Context: not packed here
     if ((c.shared && c.layout.max_rows) || c.group_m) return HSW_ERR_UNSUPPORTED;    // shared context: interludes are the caller's
+    if (c.bound) return HSW_ERR_UNSUPPORTED;                                  // a bound region: the cells between columns are the caller's
     if (!dst->wide && dst->wide_cap) return HSW_ERR_INVALID_ARG;
     hipStream_t stream = nullptr;
     int device = 0;
@@ -1294,6 +1422,7 @@ int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx) try {
     if (!g || hash_idx > g->cfg.max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
     if (g->ctx->context_images) return HSW_ERR_UNSUPPORTED;       // K proofs of one circuit: nothing to deal out
     if (g->ctx->shared) return HSW_ERR_UNSUPPORTED;               // shared context: the layout follows the declared origins
+    if (g->ctx->bound) return HSW_ERR_UNSUPPORTED;                // a bound region is one prover's own slabs
     int rc = hsw_engine_synchronize(g->ctx->engine);
     if (rc != HSW_OK) return rc;
     hsw::Context &c = *g->ctx;
@@ -1400,10 +1529,10 @@ int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region 
         out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * C) * cb;   // linear: the Context's stream
     }
     out->lookup_cells = c.ctx_lookups();
-    out->d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)(h * c.ctx_lookups()) * cb;
+    out->d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)(h * c.lookup_pitch()) * cb;
     out->chip_rows = nb * c.shape.limb_calls_per_block / ncols;
     out->chip_col_stride = c.chip_col_stride;
-    const size_t chip_row0 = (size_t)(h * nb * c.shape.limb_calls_per_block / ncols);
+    const size_t chip_row0 = (size_t)c.chip_cell(h * nb * c.shape.limb_calls_per_block);   // (a whole number of rows per Context)
     out->d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + chip_row0 * cb;
     out->d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + chip_row0 * cb;
     out->origin_column = c.layout.origin_column;

@@ -142,6 +142,33 @@ class Context {
     size_t group_m = 0;
     size_t ctx_blocks = 0;                                     // blocks of one Context
     size_t contexts() const { return context_images ? init_capacity : group_m ? init_capacity / group_m : 1; }
+    // hsw_gadget_bind_region: d_gate, d_lookup and the chip columns are the CALLER's memory -- never freed, grown,
+    // zeroed or filled here -- at the caller's pitches: the image columns layout.pitch cells apart, and (K Contexts)
+    // every Context's image, lookup column and chip rows in a place of its own: layout.image_pitch,
+    // binding.lookup_pitch and binding.chip_context_pitch cells after the previous Context's.  Library-owned, these
+    // three are columns x max_rows, Lp and "consecutive rows of the same columns".  `binding` is what the caller
+    // declared; the layout calls check what they need against its capacities (adopt)
+    bool bound = false;
+    hsw_region_binding binding{};
+    uint64_t lookup_pitch() const { return bound && contexts() > 1 ? binding.lookup_pitch : ctx_lookups(); }
+    size_t blocks_per_context() const { return context_images ? capacity_blocks / init_capacity : group_m ? ctx_blocks : capacity_blocks; }
+    uint64_t ctx_limb_calls() const { return (uint64_t)blocks_per_context() * shape.limb_calls_per_block; }
+    uint64_t ctx_chip_rows() const { return (ctx_limb_calls() + shape.num_advice_columns - 1) / shape.num_advice_columns; }
+    // cells from where consecutive rows would put a Context's chip rows to where they lie, per Context (modulo 2^64;
+    // ExpandParams::chip_ctx_extra)
+    uint64_t chip_ctx_extra() const { return bound && contexts() > 1 ? binding.chip_context_pitch - ctx_chip_rows() : 0; }
+    // chip cell of limb call n (counted from the pass's first), from d_chip_dense / d_chip_spread
+    uint64_t chip_cell(uint64_t n) const {
+        const uint64_t ncols = shape.num_advice_columns, extra = chip_ctx_extra();
+        return (n % ncols) * chip_col_stride + n / ncols + (extra ? n / ctx_limb_calls() * extra : 0);
+    }
+    // d_lookup cells ONE Context needs with layout l (Lp; one Context: the whole column)
+    uint64_t lookups_needed(const Layout &l) const {
+        return context_images ? l.origin_lookups + ctx_own_lookups : shared && l.max_rows ? l.lookups_end : l.origin_lookups + own_lookup_capacity;
+    }
+    // the library's own zeroed buffers again, sized for the layout without pitches (sizes / rc_inputs: the gadget's)
+    int unbind(const std::vector<size_t> &sizes, bool rc_inputs);
+    int bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b);
     bool zero_loaded = false;        // Context.zero_cell (first load_zero: compression.rs:34 of the first block)
     uint64_t gate_cursor = 0, gate_capacity = 0;       // cells
     void *d_lookup = nullptr;
@@ -171,7 +198,9 @@ class Context {
     // Makes `nl` the layout.  fresh_image / fresh_lookup: the image / the lookup column is replaced by a zeroed
     // one sized for nl; a shared context's buffers grow instead, keeping what they hold, and if the map changed its
     // image cells [clear_from, end) -- what an earlier layout may have written there -- are zeroed again (unassigned
-    // advice cells are 0).  Nothing is touched unless every allocation succeeded.
+    // advice cells are 0).  Nothing is touched unless every allocation succeeded.  A bound region is the caller's:
+    // nothing is allocated, grown or zeroed, and a layout that needs more columns or lookup cells than the binding
+    // declares is HSW_ERR_TOO_LARGE.
     int adopt(Layout &nl, bool fresh_image, bool fresh_lookup, uint64_t clear_from);
     // hsw_gadget_set_origin: validated in full (layout included) before anything is freed or reallocated
     int set_origin(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t column, uint64_t row, bool zero_cell_loaded,

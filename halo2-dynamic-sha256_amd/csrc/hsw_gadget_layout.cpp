@@ -9,7 +9,7 @@ void ColumnWalk::calls(const uint8_t *lens, size_t n) {
     for (size_t i = 0; i < n; i++) {
         const uint8_t len = lens[i];
         if (row + len >= rows) {                          // halo2-lib v0.2.x assign_region: next column (A3-iii)
-            bc.push_back(cell); bg.push_back(rows - row);
+            bc.push_back(cell); bg.push_back((pitch ? pitch : rows) - row);
             row = 0; col++;
         }
         row += len; cell += len;
@@ -29,14 +29,16 @@ int layout_walk(const hsw_shape &shape, const size_t *sizes, size_t n, bool rc_i
     hsw_gate_tape(&shape, block_tape.data(), m, nullptr);
     std::vector<uint64_t> bc, bg;
     out->digest_cell0.clear(); out->digest_entry0.clear(); out->digest_lookup0.clear();
-    ColumnWalk w{rows, 0, out->origin_row, 0, bc, bg};    // the Context's next free row (hsw_gadget_set_origin)
+    const uint64_t pitch = out->pitch ? out->pitch : rows;
+    ColumnWalk w{rows, 0, out->origin_row, 0, bc, bg, pitch};   // the Context's next free row (hsw_gadget_set_origin)
     uint64_t lk = out->origin_lookups, own = 0;
     bool zero = out->origin_zero_loaded;                  // a Context that already caches its zero cell assigns none
     for (size_t h = 0; h < n; h++) {
         if (decl && h < decl->size() && (*decl)[h].set) { // the caller's interlude ends at (column, row)
             const DigestOrigin &d = (*decl)[h];
             if (d.column < out->origin_column || d.row >= rows) return HSW_ERR_INVALID_ARG;
-            const uint64_t want = (d.column - out->origin_column) * rows + d.row, here = w.col * rows + w.row;
+            // (in image cells: a gap that spans columns takes the cells between them along)
+            const uint64_t want = (d.column - out->origin_column) * pitch + d.row, here = w.col * pitch + w.row;
             if (want < here || d.lookups < lk) return HSW_ERR_INVALID_ARG;
             if (want > here) { bc.push_back(w.cell); bg.push_back(want - here); }
             w.col = d.column - out->origin_column; w.row = d.row; lk = d.lookups;
@@ -85,7 +87,7 @@ uint64_t Layout::gap_at(uint64_t cell) const {           // breaks are ascending
 void Layout::position(uint64_t cell, uint64_t *column, uint64_t *row) const {
     if (period) cell %= period;                          // the owning Context's own stream cell
     const uint64_t at = cell + origin_row + gap_at(cell);
-    if (max_rows) { if (column) *column = origin_column + at / max_rows; if (row) *row = at % max_rows; }
+    if (max_rows) { if (column) *column = origin_column + at / column_pitch(); if (row) *row = at % column_pitch(); }
     else { if (column) *column = origin_column; if (row) *row = at; }
 }
 

@@ -62,6 +62,10 @@ struct ExpandParams {
     uint64_t ctx_cells;
     uint32_t *next_states_host;   // small-batch kernel only: a second copy of next_states, in pinned host memory (may be null)
     const void *mont_tab;         // HSW_K_M32 only: 3 x 256 Montgomery-form cells -- i, spread(i), i << 8 for i < 256 (hsw_api.cpp)
+    // bound regions (hsw_gadget_bind_region) with a Context per frame_every blocks: the chip rows of Context
+    // b / frame_every start chip_ctx_extra cells further per Context than consecutive rows would put them
+    // (= chip_context_pitch - rows of one Context, modulo 2^64).  0 = consecutive rows of the same columns
+    uint64_t chip_ctx_extra;
 };
 
 // limbs = 16 / num_bits_lookup.  Returns hipErrorInvalidValue for a limb count
@@ -88,6 +92,8 @@ struct PlaceTable;
 struct ContextPeriod {
     uint64_t stream_cells, image_cells;
     const PlaceTable *place = nullptr;   // shared context (HSW_GADGET_SHARED_CONTEXT): the table path; stream_cells = image_cells = 0
+    uint64_t chip_ctx_extra = 0;         // bound regions: ExpandParams / VerifyParams::chip_ctx_extra
+    bool chip_rows_checked = false;      // bound regions: the gadget checked the chip capacities per Context itself
 };
 
 // Shared-context placement (HSW_GADGET_SHARED_CONTEXT, library-internal): the map from gate-stream cell to image

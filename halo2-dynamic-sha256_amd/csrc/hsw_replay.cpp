@@ -207,7 +207,8 @@ static int ensure_tape(hsw_gadget *g) {
 struct Extent { uint64_t cells, wit, lookups, limbs; };
 // Everything image_cell() depends on besides the stream cell
 static std::vector<uint64_t> layout_key(const Context &c) {
-    std::vector<uint64_t> k{c.layout.max_rows, c.layout.origin_row, c.context_images || c.group_m ? c.ctx_stream() : 0, c.layout.image_cells()};
+    std::vector<uint64_t> k{c.layout.max_rows, c.layout.origin_row, c.context_images || c.group_m ? c.ctx_stream() : 0, c.layout.image_cells(),
+                            c.layout.column_pitch()};
     k.insert(k.end(), c.layout.break_cell.begin(), c.layout.break_cell.end());
     k.insert(k.end(), c.layout.break_gap.begin(), c.layout.break_gap.end());
     return k;
@@ -269,8 +270,8 @@ int hsw_gadget_download_region_distinct(hsw_gadget *g, void *distinct, size_t ca
     const std::vector<uint64_t> key = layout_key(c);
     if (t.d_wit_pos && key != t.pos_layout) drop_region_tape_positions(&t);
     if (!t.d_wit_pos) {                                   // first delivery with this layout: where every witness sits in the image
-        // (image positions are 32-bit: every Context's image together must stay below 2^32 cells)
-        if (c.layout.max_rows && c.layout.columns * c.layout.max_rows * c.contexts() >= (1ull << 32)) {
+        // (image positions are 32-bit: every Context's image together -- a bound region: context_pitch x K -- must stay below 2^32 cells)
+        if (c.layout.max_rows && c.layout.image_cells() * c.contexts() >= (1ull << 32)) {
             if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
             return HSW_ERR_TOO_LARGE;
         }
@@ -305,7 +306,6 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
     const Cell *val = static_cast<const Cell *>(distinct);
     const Cell *consts = reinterpret_cast<const Cell *>((c.repr_flags & HSW_REPR_MONTGOMERY) ? t.const_mont.data() : t.const_canon.data());
     auto value = [&](uint32_t code) -> const Cell & { return (code & TAPE_CONST) ? consts[code & ~TAPE_CONST] : val[code]; };
-    const uint32_t ncols = c.shape.num_advice_columns;
     if (threads == 0) threads = 1;
     if (threads > 64) threads = 64;
     // gate stream -> image: thread k takes cells [lo, hi); the breaks it passes are walked once
@@ -328,13 +328,13 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
         if (!dst->lookup) return;
         Cell *lk = static_cast<Cell *>(dst->lookup) + c.layout.origin_lookups;
         if (c.context_images) {                                   // entry j of Context h = j / own: its own lookup column
-            const uint64_t own = c.ctx_own_lookups, Lp = c.ctx_lookups();
+            const uint64_t own = c.ctx_own_lookups, Lp = c.lookup_pitch();
             for (uint64_t j = lo; j < hi; j++) lk[(j / own) * Lp + j % own] = value(t.lookup_code[j]);
             return;
         }
         if (c.group_m && !c.layout.digest_entry0.empty()) {              // a Context group: both -- entry j of Context j / own
             Cell *lk0 = static_cast<Cell *>(dst->lookup);
-            const uint64_t own = c.ctx_own_lookups, Lp = c.ctx_lookups();
+            const uint64_t own = c.ctx_own_lookups, Lp = c.lookup_pitch();
             for (uint64_t j = lo; j < hi; j++) lk0[(j / own) * Lp + c.layout.lookup_cell(j % own)] = value(t.lookup_code[j]);
             return;
         }
@@ -348,7 +348,7 @@ int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_regi
     auto chip_part = [&](uint64_t lo, uint64_t hi) {              // limb call n: column n % ncols, row n / ncols
         Cell *cd = static_cast<Cell *>(dst->chip_dense), *cs = static_cast<Cell *>(dst->chip_spread);
         for (uint64_t n = lo; n < hi; n++) {
-            const size_t at = (size_t)(n % ncols) * c.chip_col_stride + (size_t)(n / ncols);
+            const size_t at = (size_t)c.chip_cell(n);
             if (cd) cd[at] = value(t.chip_dense_code[n]);
             if (cs) cs[at] = value(t.chip_spread_code[n]);
         }

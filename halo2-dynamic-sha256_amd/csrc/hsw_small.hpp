@@ -138,7 +138,7 @@ DEV void scatter_chip(const EM &em, const ExpandParams &p, u64 block_first_limb,
     const u64 n0 = block_first_limb + (u64)call0 * L;
     const u64 r0 = n0 / p.ncols;
     const u32 c0 = (u32)(n0 - r0 * p.ncols), ncols = p.ncols;
-    const size_t rbase = (size_t)(r0 - p.cursor0 / p.ncols);
+    const size_t rbase = (size_t)(r0 - p.cursor0 / p.ncols) + (size_t)em.chip_off;
     constexpr u32 CB = EM::COMPACT ? 8u : 32u;
     const u32 hs = em.hsel, hn = em.hcnt;             // all waves of the workgroup, the emitter included
     for (u32 k = lane + 64u * hs; k < total; k += 64u * hn) {
@@ -229,6 +229,7 @@ DEV void small_role(const ExpandParams &p, const u32 *bw, const u32 (&ps)[8], si
     em.head = nullptr;
     em.d16 = s_d16;
     em.tab = nullptr;
+    em.chip_off = 0;
     em.hsel = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform (the flush loops stay scalar); blockDim.x / 64 waves share the role
     em.hcnt = blockDim.x >> 6;
 
@@ -237,6 +238,7 @@ DEV void small_role(const ExpandParams &p, const u32 *bw, const u32 (&ps)[8], si
         if constexpr (RC)
             if (p.frame_every) {
                 const u32 ctx = (u32)blk / (u32)p.frame_every;       // wave-uniform
+                em.chip_off = (u64)ctx * p.chip_ctx_extra;           // (as in hsw_expand.hpp)
                 if (p.ctx_cells) {     // context images (as in hsw_expand.hpp)
                     first -= (u64)ctx * (u64)p.frame_every * (u64)LY::GATE_CELLS;
                     ctx_base = (u64)ctx * p.ctx_cells;

@@ -50,6 +50,7 @@ struct VerifyParams {
     const uint32_t *gate_rows;
     const int64_t *assert_eq, *range, *chip, *lookup_src, *next_state_cells;
     VerifyReport *report;
+    uint64_t chip_ctx_extra;       // bound regions: as ExpandParams::chip_ctx_extra (0 = consecutive rows)
 };
 
 hipError_t launch_verify(const VerifyParams &p, size_t n_blocks, hipStream_t stream);

@@ -134,7 +134,7 @@
     //    to load (compared as stored); the table relation takes the partner's low limb by a DPP swap.
     if (p.chip_dense) {
         const uint4 *cd = reinterpret_cast<const uint4 *>(p.chip_dense), *csp = reinterpret_cast<const uint4 *>(p.chip_spread);
-        const u64 row0 = p.cursor0 / p.ncols;
+        const u64 row0 = p.cursor0 / p.ncols - dg * p.chip_ctx_extra;       // (bound regions: the Context's own chip rows)
         const u32 half = threadIdx.x & 1u;                                    // 0: dense, 1: spread
         auto swap32 = [](u32 v) -> u32 { return (u32)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); };   // quad_perm [1,0,3,2]
         for (u32 nb = 0; nb < p.limb_calls; nb += nt >> 1) {                  // the same trip count in every lane

@@ -137,6 +137,37 @@ class Sha256DynamicConfig:
         (column, row) and ctx.cells_to_lookup.len() after the circuit's own cells since digest h-1."""
         self._ok(self.lib.hsw_gadget_set_digest_origin(self.h, h, column, row, lookups_queued))
 
+    def bind_region(self, columns, column_pitch=0, columns_capacity=0, lookup=None, lookup_capacity=0, chip_dense=None,
+                    chip_spread=None, chip_col_stride=0, chip_rows_capacity=0, context_pitch=0, lookup_pitch=0,
+                    chip_context_pitch=0):
+        """hsw_gadget_bind_region: write the region straight into device columns the caller owns.  columns, lookup,
+        chip_dense, chip_spread: torch tensors (their data_ptr is taken; the caller keeps them alive and disjoint) or
+        raw device pointers; pitches and capacities in cells.  bind_region(None): back to library-owned buffers."""
+        if columns is None:
+            self._ok(self.lib.hsw_gadget_bind_region(self.h, None))
+            self._bound = None
+            return
+
+        def ptr(x):
+            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x or 0)
+        b = N.RegionBinding(ptr(columns), column_pitch, columns_capacity, context_pitch, ptr(lookup), lookup_capacity, lookup_pitch,
+                            ptr(chip_dense), ptr(chip_spread), chip_col_stride, chip_rows_capacity, chip_context_pitch)
+        self._ok(self.lib.hsw_gadget_bind_region(self.h, C.byref(b)))
+        self._bound = (columns, lookup, chip_dense, chip_spread)      # keeps tensors alive while they are bound
+
+    def _unbound_only(self, what):
+        """The numpy conveniences size their host buffers for library-owned geometry; a bound gadget's host layout
+        follows the caller's pitches: call hsw_gadget_download_region / hsw_gadget_replay_region with buffers of
+        that geometry (region_binding())."""
+        if getattr(self, "_bound", None) is not None:
+            raise N.HswError(N.HSW_ERR_UNSUPPORTED, what + "(): bound region -- pass host buffers laid out like the binding to the C call")
+
+    def region_binding(self):
+        """hsw_gadget_region_binding: the geometry in force (also when library-owned)."""
+        b = N.RegionBinding()
+        self._ok(self.lib.hsw_gadget_region_binding(self.h, C.byref(b)))
+        return b
+
     def reset(self):
         """Next synthesis pass: all cursors back to their start, buffers and layout kept
         (the reference clones the config per synthesis, lib.rs:440)."""
@@ -155,6 +186,7 @@ class Sha256DynamicConfig:
         """hsw_gadget_download_region into (pinned) host arrays: dict of numpy uint64 arrays shaped like
         streams() -- gate (columns, max_rows, 4) or (cells, 4); lookup; dense / spread (ncols, stride, 4)."""
         import numpy as np
+        self._unbound_only("download_region")
         v = self.view()
         ncols = self.engine.ncols
         img = self.whole_digest and int(v.max_rows)
@@ -194,6 +226,7 @@ class Sha256DynamicConfig:
         pinned memory), the image is rebuilt on the host (hsw_gadget_replay_region).  Returns the same dict as
         download_region plus "distinct" (n, 4) and "bufs" (pass back in to reuse the host buffers)."""
         import numpy as np
+        self._unbound_only("download_region_distinct")
         tape = N.RegionTape()
         self._ok(self.lib.hsw_gadget_region_tape(self.h, C.byref(tape)))
         v = self.view()
@@ -294,6 +327,8 @@ class Sha256DynamicConfig:
             return a
 
         rows = (int(v.num_limb_sum) + ncols - 1) // ncols
+        if getattr(self, "_bound", None) is not None:
+            return self._bound_streams(v, grab, rows)
         if (self.context_images or self.n_contexts is not None) and int(v.max_rows):   # (K, columns, max_rows, 4): one image per proof
             k = self.n_contexts if self.n_contexts is not None else len(self.max_variable_byte_sizes)
             gate = grab(v.d_gate, k * int(v.max_rows) * int(v.columns)).reshape(k, int(v.columns), int(v.max_rows), 4)
@@ -307,3 +342,24 @@ class Sha256DynamicConfig:
         if self.whole_digest:
             out["lookup"] = grab(v.d_lookup, int(v.lookup_cells))
         return out
+
+    def _bound_streams(self, v, grab, rows):
+        """streams() of a bound gadget: the same shapes as unbound, gathered from the caller's memory at the bound
+        pitches -- the rows [0, max_rows) of every image column, Lp cells of every proof's lookup column and every
+        proof's chip rows (one after the other along the row axis, as the library-owned columns hold them)."""
+        import numpy as np
+        b = self.region_binding()
+        multi = self.context_images or self.n_contexts is not None
+        k = 1 if not multi else self.n_contexts if self.n_contexts is not None else len(self.max_variable_byte_sizes)
+        ncols, cols, mr = self.engine.ncols, int(v.columns), int(v.max_rows)
+        gate = np.stack([np.stack([grab(b.d_columns + (c * int(b.context_pitch) + j * int(b.column_pitch)) * 32, mr)
+                                   for j in range(cols)]) for c in range(k)])
+        lp = int(self.context_region(0).lookup_cells) if multi else int(v.lookup_cells)
+        lookup = np.concatenate([grab(b.d_lookup + c * int(b.lookup_pitch) * 32, lp) for c in range(k)])
+        per = rows // k if multi else rows             # chip rows of one proof (a whole number of rows each)
+
+        def chip(base):
+            return np.stack([np.concatenate([grab(base + (c * int(b.chip_context_pitch) + j * int(b.chip_col_stride)) * 32, per)
+                                             for c in range(k)]) for j in range(ncols)])
+        return dict(gate=gate if multi else gate[0], dense=chip(b.d_chip_dense), spread=chip(b.d_chip_spread), rows=rows,
+                    lookup=lookup)

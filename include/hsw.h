@@ -608,7 +608,8 @@ int hsw_gadget_create_ex(hsw_engine *e, const size_t *max_variable_byte_sizes, s
  *   layout calls   hsw_gadget_set_columns, hsw_gadget_set_origin and hsw_gadget_set_digest_origin(g, j, ...) with
  *                  1 <= j < M describe ONE Context and apply to every Context alike; a call that fails leaves layout
  *                  and buffers as they were.  A call that changes the layout replaces the K images and lookup
- *                  columns by zeroed ones (device pointers from earlier queries are stale); the same declaration
+ *                  columns by zeroed ones (device pointers from earlier queries are stale; a bound region,
+ *                  hsw_gadget_bind_region, is neither replaced nor zeroed); the same declaration
  *                  again, pass after pass, keeps layout, buffers, region tape and the device's jump table.
  *   queries        hsw_gadget_context_region(g, c, ...) describes Context c (assigned: all M digests are).
  *                  hsw_hash_result gate cells are gadget-stream indices, the K Context streams (stream_cells each)
@@ -625,7 +626,8 @@ void hsw_gadget_destroy(hsw_gadget *g);
 /* HSW_GADGET_WHOLE_DIGEST, before the first digest: lay the gate stream out as the
  * FlexGate (Vertical) advice columns themselves -- column c = cells [c*max_rows,
  * (c+1)*max_rows) of d_gate, every assign_region call placed by the v0.2.x rule
- * `row + len >= max_rows -> next column` (assumption A3-iii), unassigned tail rows 0.
+ * `row + len >= max_rows -> next column` (assumption A3-iii), unassigned tail rows 0 (a bound
+ * region, hsw_gadget_bind_region: columns column_pitch cells apart, unassigned cells the caller's, never zeroed).
  * max_rows = the gate's usable rows (RangeConfig.gate.max_rows, lib.rs:355).  The
  * layout depends only on max_variable_byte_sizes, never on the messages.
  * HSW_ERR_TOO_LARGE: more than HSW_MAX_BREAKS + 1 columns (HSW_GADGET_MAX_COLUMNS with HSW_GADGET_SHARED_CONTEXT). */
@@ -647,7 +649,8 @@ int hsw_gadget_set_columns(hsw_gadget *g, uint64_t max_rows, uint64_t *n_columns
  *   lookups_already_queued   ctx.cells_to_lookup.len(): RangeConfig::finalize (lib.rs:469) copies the queue
  *                            into the lookup-advice column in order, so the gadget's entries start at that
  *                            index: d_lookup is reallocated with that many leading cells (zero, the
- *                            caller's), every *_lookup index of hsw_hash_result counts from cell 0.
+ *                            caller's; a bound region is never reallocated or zeroed, hsw_gadget_bind_region),
+ *                            every *_lookup index of hsw_hash_result counts from cell 0.
  * The origin survives hsw_gadget_reset (the next synthesis of the same circuit starts at the same place).
  * HSW_ERR_INVALID_ARG: not a whole-digest context, digests already assigned in this pass, or row >= max_rows;
  * HSW_ERR_TOO_LARGE: the layout from that row needs more than HSW_MAX_BREAKS + 1 columns (the previous
@@ -661,11 +664,66 @@ int hsw_gadget_set_origin(hsw_gadget *g, uint64_t column, uint64_t row, int zero
  * every origin first and run the pass as one hsw_gadget_digest_batch.  Declaring h drops the declarations of every
  * later digest -- unless it repeats h's current declaration, which changes nothing (a prover that declares the same
  * interludes pass after pass keeps its layout, its device table and its tape positions).  A declaration that changes
- * the layout zeroes the image cells past digest h-1's end again (what an earlier layout wrote there).  HSW_ERR_INVALID_ARG, with the layout unchanged: not a shared context or no column image, h = 0 or
+ * the layout zeroes the image cells past digest h-1's end again (what an earlier layout wrote there; not in a bound
+ * region, hsw_gadget_bind_region: its cells are the caller's, and a layout past its capacities is HSW_ERR_TOO_LARGE).  HSW_ERR_INVALID_ARG, with the layout unchanged: not a shared context or no column image, h = 0 or
  * h >= n_hashes, digest h already assigned in this pass, row >= max_rows, (column, row) before the next free cell
  * after digest h-1's layout (in (column, row) order), or lookups_queued below the queue length after digest h-1.
  * HSW_ERR_TOO_LARGE: the layout would need more than HSW_GADGET_MAX_COLUMNS columns. */
 int hsw_gadget_set_digest_origin(hsw_gadget *g, size_t h, uint64_t column, uint64_t row, uint64_t lookups_queued);
+/* Bind the gadget's region to device memory the CALLER owns -- a prover that keeps every advice column as a polynomial
+ * of n = 2^k cells in HBM gets the cells written straight into its own columns, no copy afterwards.  For
+ * HSW_GADGET_WHOLE_DIGEST gadgets with a column image (hsw_gadget_set_columns first: HSW_ERR_UNSUPPORTED without it,
+ * and for linear or block-stream gadgets): the plain single image, HSW_GADGET_SHARED_CONTEXT,
+ * HSW_GADGET_CONTEXT_IMAGES and hsw_gadget_create_contexts; 32-byte cells, canonical or Montgomery.
+ * Cells, not bytes, throughout; image column k is FlexGate column origin_column + k as before.
+ *   d_columns, column_pitch      image column k of proof c starts at cell c * context_pitch + k * column_pitch;
+ *                                max_rows <= column_pitch <= 2^24, odd values included.  Rows [max_rows,
+ *                                column_pitch) of a column (a prover's blinding rows) are never written.
+ *   columns_capacity             image columns reserved per proof: the layout's `columns` must fit
+ *   context_pitch                K > 1 proofs: >= columns_capacity * column_pitch
+ *   d_lookup, lookup_capacity    the lookup-advice column of proof c starts at cell c * lookup_pitch and holds
+ *   lookup_pitch                 lookup_capacity cells (>= Lp, the cells the layout needs); lookup_pitch >= lookup_capacity
+ *   d_chip_dense, d_chip_spread  chip column k of proof c starts at cell c * chip_context_pitch + k * chip_col_stride and
+ *   chip_col_stride              holds chip_rows_capacity rows (>= one proof's chip rows; chip_col_stride >=
+ *   chip_rows_capacity           chip_rows_capacity).  Library-owned, proof c's rows follow proof c-1's in the same
+ *   chip_context_pitch           columns; bound, every proof has chip rows of its own
+ * A single-proof gadget ignores context_pitch, lookup_pitch and chip_context_pitch.  b = NULL: back to library-owned,
+ * zeroed buffers (nothing to do on an unbound gadget).
+ * When: on a fresh or reset gadget only (HSW_ERR_INVALID_ARG after the first digest of a pass).  The binding survives
+ * hsw_gadget_reset and every layout call whose result still fits the declared capacities (hsw_gadget_set_columns with
+ * max_rows <= column_pitch, hsw_gadget_set_origin, hsw_gadget_set_digest_origin); one that does not fit returns
+ * HSW_ERR_TOO_LARGE and leaves layout and binding as they were -- a bound shared context never grows its image.
+ * Checks, each leaving the previous binding or the library's buffers in place: a null pointer or one that is not
+ * 128-byte aligned (whole lines for the realigned write-out), or a pitch below its minimum: HSW_ERR_INVALID_ARG; a
+ * capacity below what the layout needs (columns, Lp, one proof's chip rows): HSW_ERR_TOO_LARGE.  The four areas must
+ * be disjoint and live on the engine's device: the library does NOT check that.
+ * Ownership: binding drains the engine and frees the library's own image, lookup and chip buffers.  Caller memory is
+ * never freed, grown, zeroed or filled: cells the layout does not assign keep whatever the caller put there (a prover
+ * zeroes its polynomials once) -- on a bound gadget this replaces every "zeroed" / "zeroed again" clause of
+ * hsw_gadget_set_columns, hsw_gadget_set_origin, hsw_gadget_set_digest_origin and hsw_gadget_create_contexts.
+ * What follows the binding with unchanged meaning: hsw_gadget_streams and hsw_gadget_context_region report the bound
+ * pointers (chip_col_stride the bound one); hsw_gadget_cell_position / hsw_gadget_result_cells return the same
+ * (FlexGate column, row) as an unbound gadget -- binding changes addresses, never positions; hsw_gadget_verify;
+ * hsw_gadget_download_region / hsw_gadget_replay_region with host buffers laid out like the device (pitches included,
+ * used rows only); the distinct delivery, whose 32-bit image positions now bound context_pitch x K (columns x
+ * column_pitch for one proof): HSW_ERR_TOO_LARGE at 2^32 cells.  hsw_gadget_place, hsw_gadget_download_region_compact
+ * and hsw_gadget_seek return HSW_ERR_UNSUPPORTED on a bound gadget. */
+typedef struct hsw_region_binding {
+    void    *d_columns;          /* image column 0 of proof 0 */
+    uint64_t column_pitch;       /* cells from image column k to k+1;          >= max_rows */
+    uint64_t columns_capacity;   /* image columns the caller reserved per proof */
+    uint64_t context_pitch;      /* cells from proof c to c+1 (K > 1);         >= columns_capacity * column_pitch */
+    void    *d_lookup;           /* lookup-advice column of proof 0 */
+    uint64_t lookup_capacity;    /* cells per proof */
+    uint64_t lookup_pitch;       /* cells from proof c to c+1;                 >= lookup_capacity */
+    void    *d_chip_dense, *d_chip_spread;   /* chip row 0 of chip column 0 of proof 0 */
+    uint64_t chip_col_stride;    /* cells from chip column k to k+1 */
+    uint64_t chip_rows_capacity; /* rows per chip column per proof */
+    uint64_t chip_context_pitch; /* cells from proof c to c+1 */
+} hsw_region_binding;
+int hsw_gadget_bind_region(hsw_gadget *g, const hsw_region_binding *b);   /* b = NULL: back to library-owned, zeroed buffers */
+/* The geometry in force, also when library-owned (then: d_gate / max_rows / columns x max_rows, Lp, consecutive chip rows). */
+int hsw_gadget_region_binding(const hsw_gadget *g, hsw_region_binding *out);
 /* Start the next synthesis pass with the same buffers and layout: every cursor back to
  * its initial value (cur_hash_idx, num_limb_sum, the stream cursors, the Context's zero
  * cell).  What the reference's harnesses do by cloning the config per synthesis

@@ -345,6 +345,23 @@ pub struct hsw_context_region {
     pub reserved_: u32,
 }
 
+/// hsw_region_binding: caller-owned device columns a gadget's region is bound to (include/hsw.h).
+#[repr(C)]
+pub struct hsw_region_binding {
+    pub d_columns: *mut c_void,
+    pub column_pitch: u64,
+    pub columns_capacity: u64,
+    pub context_pitch: u64,
+    pub d_lookup: *mut c_void,
+    pub lookup_capacity: u64,
+    pub lookup_pitch: u64,
+    pub d_chip_dense: *mut c_void,
+    pub d_chip_spread: *mut c_void,
+    pub chip_col_stride: u64,
+    pub chip_rows_capacity: u64,
+    pub chip_context_pitch: u64,
+}
+
 extern "C" {
     pub fn hsw_abi_version() -> u32;
     pub fn hsw_strerror(status: c_int) -> *const c_char;
@@ -436,6 +453,8 @@ extern "C" {
     pub fn hsw_gadget_download_region(g: *mut hsw_gadget, dst: *const hsw_region_host) -> c_int;
     pub fn hsw_gadget_cell_position(g: *const hsw_gadget, cell: u64, column: *mut u64, row: *mut u64) -> c_int;
     pub fn hsw_gadget_context_region(g: *const hsw_gadget, h: usize, out: *mut hsw_context_region) -> c_int;
+    pub fn hsw_gadget_bind_region(g: *mut hsw_gadget, b: *const hsw_region_binding) -> c_int;
+    pub fn hsw_gadget_region_binding(g: *const hsw_gadget, out: *mut hsw_region_binding) -> c_int;
     pub fn hsw_frame_query(shape: *const hsw_shape, max_variable_byte_size: usize, is_input_range_check: c_int,
                            out: *mut hsw_frame_shape) -> c_int;
     pub fn hsw_frame_tape(shape: *const hsw_shape, max_variable_byte_size: usize, is_input_range_check: c_int,

@@ -76,6 +76,10 @@ class LaunchInfo(C.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
     def kernel_name(self):
+        if self.split & 4:      # a gadget bound by hsw_gadget_bind_columns: the wide table-path instantiations
+            if self.split & 2:
+                return "hsw::hsw_small_table_kernel<%d, %d, true>" % (self.limbs, self.repr)
+            return "hsw::hsw_expand_table_kernel<%d, %d, %d, %d, true>" % (self.limbs, self.tile_cells, self.tile_rows, self.repr)
         if self.split == 2:
             return "hsw::hsw_small_kernel<%d, %d, %s>" % (self.limbs, self.repr, "true" if self.internals else "false")
         return "hsw::hsw_expand_kernel<%d, %d, %d, %d, %s>" % (self.limbs, self.tile_cells, self.tile_rows, self.repr,
@@ -208,7 +212,7 @@ SYMBOLS = (
     "hsw_gadget_download_region_compact", "hsw_region_widen", "hsw_gadget_result_cells",
     "hsw_gadget_set_origin", "hsw_gadget_region_tape", "hsw_gadget_download_region_distinct", "hsw_gadget_replay_region",
     "hsw_gadget_context_region", "hsw_gadget_set_digest_origin", "hsw_gadget_create_contexts",
-    "hsw_gadget_bind_region", "hsw_gadget_region_binding",
+    "hsw_gadget_bind_region", "hsw_gadget_region_binding", "hsw_gadget_bind_columns",
 )
 
 
@@ -362,6 +366,8 @@ def lib():
         L.hsw_gadget_context_region.argtypes = [vp, C.c_size_t, C.POINTER(ContextRegion)]
         L.hsw_gadget_bind_region.restype = C.c_int
         L.hsw_gadget_bind_region.argtypes = [vp, C.POINTER(RegionBinding)]
+        L.hsw_gadget_bind_columns.restype = C.c_int
+        L.hsw_gadget_bind_columns.argtypes = [vp, C.POINTER(RegionBinding), C.POINTER(C.c_void_p), C.c_size_t]
         L.hsw_gadget_region_binding.restype = C.c_int
         L.hsw_gadget_region_binding.argtypes = [vp, C.POINTER(RegionBinding)]
         L.hsw_gadget_create_contexts.restype = C.c_int

@@ -477,7 +477,9 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
         // tiny batches are latency-bound: the small-batch kernel (37 waves per block, one sub-unit program
         // each; hsw_small.hpp).  "split" = 1 keeps the older one-phase-per-wave mode of hsw_expand_kernel.
         // (a Context group's launch -- one digest index of several Contexts -- is the streaming table kernel's at any size)
-        const bool small = hsw_small_eligible(e, n_blocks) && !(table && table->ctx_blocks);
+        // (... except K proofs by pointer table with one digest each: their blocks are consecutive, as the small-batch kernel reads them)
+        const bool small = hsw_small_eligible(e, n_blocks) &&
+                           !(table && table->ctx_blocks && !(table->cum_stride && table->ctx_blocks == args->frame_every));
         if (!small && e->limbs == 2 && e->split == 1) {
             p.parts = 32;
             p.flags |= hsw::HSW_K_SPLIT;
@@ -535,7 +537,7 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
             li.limbs = 2; li.tile_cells = 128; li.tile_rows = 16;
             li.repr = (flags & HSW_REPR_MONTGOMERY) ? 1u : (flags & HSW_REPR_COMPACT64) ? 2u : 0u;
             li.internals = e->mode == HSW_MODE_HALO2_INTERNALS ? 1u : 0u;
-            li.parts = hsw::HSW_SMALL_WAVES_PER_BLOCK * helpers; li.split = 2; li.n_blocks = n; li.seq++;
+            li.parts = hsw::HSW_SMALL_WAVES_PER_BLOCK * helpers; li.split = 2u | (table && table->cum_stride ? 4u : 0u); li.n_blocks = n; li.seq++;
             li.grid = (uint64_t)n * hsw::HSW_SMALL_WAVES_PER_BLOCK + ((done == 0 && frames) ? (uint64_t)frames->n_frames * (frames->state_waves + frames->byte_waves) : 0);
             continue;
         }
@@ -550,7 +552,7 @@ int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const h
             li.repr = m32 ? 3u : (flags & HSW_REPR_MONTGOMERY) ? 1u : (flags & HSW_REPR_COMPACT64) ? 2u : 0u;
             li.internals = e->mode == HSW_MODE_HALO2_INTERNALS ? 1u : 0u;
             li.parts = p.parts;
-            li.split = (p.flags & hsw::HSW_K_SPLIT) ? 1u : 0u;
+            li.split = ((p.flags & hsw::HSW_K_SPLIT) ? 1u : 0u) | (table && table->cum_stride ? 4u : 0u);
             li.n_blocks = n;
             li.seq++;
             li.grid = (uint64_t)n * p.parts;

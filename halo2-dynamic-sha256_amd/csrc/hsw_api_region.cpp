@@ -479,7 +479,8 @@ static int check_frame_args(hsw_engine *e, const hsw_frame_desc *descs, const ui
         for (uint32_t k = 0; k < pack->n_breaks; k++) { brk->cell[k] = pack->break_cell[k]; brk->gap[k] = pack->break_gap[k]; }
     }
     if (period && period->stream_cells) {     // context images: the break table is one Context's
-        if (!period->image_cells) return set_err(e, HSW_ERR_INVALID_ARG, "context images: image_cells = 0");
+        // (columns by pointer table: the Contexts' images are where their cum rows say, image_cells = 0)
+        if (!period->image_cells && !(period->place && period->place->cum_stride)) return set_err(e, HSW_ERR_INVALID_ARG, "context images: image_cells = 0");
         brk->ctx_stream = period->stream_cells;
         brk->ctx_image = period->image_cells;
     }

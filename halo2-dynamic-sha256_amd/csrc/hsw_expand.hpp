@@ -256,8 +256,18 @@ DEV void em_sync() {
 // 32-byte cells, every distinct value of a unit is converted once by the lane that owns the unit, copies and
 // constants cost no arithmetic (hsw_mont.hpp), and the write-out is the plain transposing copy of the canonical
 // form.  Same bytes in HBM as REPR 1.
-template <int T, int R, int REPR_, bool RC_, bool NO_REALIGN_ = false, bool EMITS_ = true>
-struct Em {
+// Columns by pointer table (PlaceTable::cum_stride, WIDE emitters only): the (<= 2) column breaks inside a block are
+// jumps of any 64-bit distance.  The block-local placement stays 32-bit: brk1 / brk2 carry VIRTUAL gaps of 4..7 cells
+// (congruent to the real ones modulo a 128-byte line, so skew and realignment see the real alignment), and a store
+// picks the segment base its virtual byte offset belongs to -- seg1 / seg2 = the block's base + 32 x (real - virtual
+// gaps so far), thr1 / thr2 = the virtual byte offset the segment after brk1 / brk2 starts at.  A store is one
+// 16-byte piece of one cell: it never spans two segments.
+template <bool WIDE_> struct EmSegs {};
+template <> struct EmSegs<true> { u64 seg1, seg2; u32 thr1, thr2; };
+
+template <int T, int R, int REPR_, bool RC_, bool NO_REALIGN_ = false, bool EMITS_ = true, bool WIDE_ = false>
+struct Em : EmSegs<WIDE_> {
+    static constexpr bool WIDE = WIDE_;
     static constexpr int TILE = T, ROWS = R;
     static constexpr int REPR = REPR_;
     static constexpr bool MONT = REPR_ == 1;
@@ -355,6 +365,16 @@ DEV u32 packed_cell(const EM &em, u32 cl) {       // FlexGate column packing: ad
 }
 DEV void store16(char *base, u32 byte_off, uint4 v) { *reinterpret_cast<uint4 *>(base + (size_t)byte_off) = v; }
 DEV void store8(char *base, u32 byte_off, u64 v) { *reinterpret_cast<u64 *>(base + (size_t)byte_off) = v; }
+// the gate stream's stores: WIDE emitters choose the segment base by the (virtual) byte offset (EmSegs)
+template <class EM>
+DEV char *seg_base(const EM &em, char *base, u32 byte_off) {
+    if constexpr (EM::WIDE)
+        return byte_off >= em.thr2 ? reinterpret_cast<char *>(em.seg2) : byte_off >= em.thr1 ? reinterpret_cast<char *>(em.seg1) : base;
+    else
+        return base;
+}
+template <class EM> DEV void store16g(const EM &em, char *base, u32 byte_off, uint4 v) { store16(seg_base(em, base, byte_off), byte_off, v); }
+template <class EM> DEV void store8g(const EM &em, char *base, u32 byte_off, u64 v) { store8(seg_base(em, base, byte_off), byte_off, v); }
 
 // Gate cell -> Montgomery form.  8 % of a block's cells hold a value of 2^32 or more, and half of the 64-cell runs
 // a wave converts at a time hold none: those take the one-multiplicand conversion (wave-uniform choice, 70 instead
@@ -444,7 +464,7 @@ DEV void flush_tile(EM &em, u32 ncells, int fl, int na, int nb, int nc, int nd, 
                 u32 cl0 = em.cell_base + seg + lane + hs * em.unit_cells;
                 for (u32 r = hs; r < em.nrows; r += hn, src += hn * S, cl0 += hn * em.unit_cells)
                     for (u32 q = 0; lane + q < ncells; q += 64)
-                        store8(base, (packed ? packed_cell(em, cl0 + q) : cl0 + q + shift) * 8u, src[q]);
+                        store8g(em, base, (packed ? packed_cell(em, cl0 + q) : cl0 + q + shift) * 8u, src[q]);
             } else if constexpr (EM::MONT) {
                 const u64 *src = tile + lane + hs * S;
                 u32 cl0 = em.cell_base + seg + lane + hs * em.unit_cells;
@@ -456,8 +476,8 @@ DEV void flush_tile(EM &em, u32 ncells, int fl, int na, int nb, int nc, int nd, 
                         if (any_neg) {
                             if (is_neg(lane + q) && v != 0ull) m = fe_neg_nonzero(m);
                         }
-                        store16(base, off + q * 32u, make_uint4(m.l[0], m.l[1], m.l[2], m.l[3]));
-                        store16(base, off + q * 32u + 16u, make_uint4(m.l[4], m.l[5], m.l[6], m.l[7]));
+                        store16g(em, base, off + q * 32u, make_uint4(m.l[0], m.l[1], m.l[2], m.l[3]));
+                        store16g(em, base, off + q * 32u + 16u, make_uint4(m.l[4], m.l[5], m.l[6], m.l[7]));
                     }
             } else {
                 // like the full-tile path below: all T / 32 LDS reads of a row first (columns past ncells hold
@@ -485,7 +505,7 @@ DEV void flush_tile(EM &em, u32 ncells, int fl, int na, int nb, int nc, int nd, 
                         }
                         u32 o_off = offr + 1024u * (u32)k;
                         if (strad) o_off = (packed_cell(em, cell0 + r * em.unit_cells + 32u * (u32)k) * 2u + h) * 16u;
-                        if (p0 + 32u * (u32)k < ncells) store16(base, o_off, o);
+                        if (p0 + 32u * (u32)k < ncells) store16g(em, base, o_off, o);
                     }
                 }
             }
@@ -498,7 +518,7 @@ DEV void flush_tile(EM &em, u32 ncells, int fl, int na, int nb, int nc, int nd, 
                 const u32 p = lo0 + i - r * ncols;
                 u32 cl = cell_sh + r * em.unit_cells + p;
                 if (packed) cl = packed_cell(em, cl);
-                store8(base, cl * 8u, tile[r * S + p]);
+                store8g(em, base, cl * 8u, tile[r * S + p]);
             }
         } else if constexpr (EM::MONT) {
             // full tiles index by the compile-time T (a shift) and skip the < 4 empty / held-back columns
@@ -515,8 +535,8 @@ DEV void flush_tile(EM &em, u32 ncells, int fl, int na, int nb, int nc, int nd, 
                 }
                 u32 cl = cell_sh + r * em.unit_cells + p;
                 if (packed) cl = packed_cell(em, cl);
-                store16(base, cl * 32u, make_uint4(m.l[0], m.l[1], m.l[2], m.l[3]));
-                store16(base, cl * 32u + 16u, make_uint4(m.l[4], m.l[5], m.l[6], m.l[7]));
+                store16g(em, base, cl * 32u, make_uint4(m.l[0], m.l[1], m.l[2], m.l[3]));
+                store16g(em, base, cl * 32u + 16u, make_uint4(m.l[4], m.l[5], m.l[6], m.l[7]));
             }
         } else if (FULL) {
             // the common case: a full tile.  Lane l owns the 16-byte piece (l & 1) of LDS column
@@ -544,7 +564,7 @@ DEV void flush_tile(EM &em, u32 ncells, int fl, int na, int nb, int nc, int nd, 
                     }
                     u32 o_off = offr + 1024u * (u32)k;
                     if (strad) o_off = (packed_cell(em, cell0 + r * em.unit_cells + 32u * (u32)k) * 2u + h) * 16u;
-                    if (k != 0 || !skip0) store16(base, o_off, o);
+                    if (k != 0 || !skip0) store16g(em, base, o_off, o);
                 }
             }
         } else {
@@ -566,7 +586,7 @@ DEV void flush_tile(EM &em, u32 ncells, int fl, int na, int nb, int nc, int nd, 
                 }
                 u32 cl = cell_sh + r * em.unit_cells + p;
                 if (packed) cl = packed_cell(em, cl);
-                store16(base, cl * 32u + h * 16u, o);
+                store16g(em, base, cl * 32u + h * 16u, o);
             }
         }
     }
@@ -644,7 +664,7 @@ DEV void flush_tile32(EM &em, u32 ncells, int fl) {
                         const bool skip0 = first_skewed && p0 < (rr == 0u ? lo0 : lo);
 #pragma unroll
                         for (u32 k = 0; k < K; k++)
-                            if (rr < em.nrows && (k != 0u || !skip0)) store16(base, off + u * hn * row_bytes + 1024u * k, v[u * K + k]);
+                            if (rr < em.nrows && (k != 0u || !skip0)) store16g(em, base, off + u * hn * row_bytes + 1024u * k, v[u * K + k]);
                     }
                 }
             } else {
@@ -662,7 +682,7 @@ DEV void flush_tile32(EM &em, u32 ncells, int fl) {
                     for (u32 u = 0; u < UR; u++) {
                         const u32 r = r0 + u * hn * RPI + dr;
                         if (r < em.nrows && !(first_skewed && p < (r == 0u ? lo0 : lo)))
-                            store16(base, off + u * hn * RPI * row_bytes, v[u]);
+                            store16g(em, base, off + u * hn * RPI * row_bytes, v[u]);
                     }
                 }
             }
@@ -686,7 +706,7 @@ DEV void flush_tile32(EM &em, u32 ncells, int fl) {
                 }
                 u32 cl = em.cell_base + seg + r * em.unit_cells + p;
                 cl = packed ? packed_cell(em, cl) : cl + shift;
-                store16(base, cl * 32u + h * 16u, *reinterpret_cast<const uint4 *>(tile + r * SW + p * 4u + h * 2u));
+                store16g(em, base, cl * 32u + h * 16u, *reinterpret_cast<const uint4 *>(tile + r * SW + p * 4u + h * 2u));
             }
         }
     }
@@ -1359,8 +1379,30 @@ DEV bool phase_window(bool split, int phase, u32 part, u32 parts, u32 &wpart, u3
 // Shared context: gap0 = the gaps of the jumps at or before the block's first stream cell `at`, and the (<= 2)
 // column breaks inside its G cells (an interlude jump falls on a digest's prologue, never inside a block).
 template <class EM>
-DEV void table_block_jumps(EM &em, const PlaceTable &t, u64 at, u64 G, u64 &gap0) {
+DEV void table_block_jumps(EM &em, const PlaceTable &t, u64 at, u64 G, u64 &gap0, u32 ctx = 0) {
     const u64 k = tbl_count_uniform(t, at);
+    if constexpr (EM::WIDE) {
+        // columns by pointer table: this Context's cum row (wave-uniform: scalar loads); jump 0 sits at stream cell 0,
+        // so k >= 1.  seg1 / seg2 hold cells relative to the block's base until wide_segments() knows em.out
+        ctx = (u32)__builtin_amdgcn_readfirstlane((int)ctx);
+        const uint64_t *cum_row = t.cum + (t.ctx0 + (u64)ctx) * t.cum_stride;
+        u64 prev = tbl_uniform(cum_row, k - 1);
+        gap0 = prev;
+        u32 virt = 0;
+        em.seg1 = em.seg2 = 0;
+        em.thr1 = em.thr2 = 0xffffffffu;
+        for (u64 j = k; j < k + 2 && j < t.n; j++) {
+            const u64 bc = tbl_uniform(t.cell, j);
+            if (bc >= at + G) break;
+            const u64 cum = tbl_uniform(cum_row, j);
+            const u32 vgap = 4u + ((u32)(cum - prev) & 3u);
+            virt += vgap;
+            if (em.brk1 == 0xffffffffu) { em.brk1 = (u32)(bc - at); em.gap1 = vgap; em.thr1 = (em.brk1 + virt) * 32u; em.seg1 = cum - gap0 - virt; }
+            else { em.brk2 = (u32)(bc - at); em.gap2 = vgap; em.thr2 = (em.brk2 + virt) * 32u; em.seg2 = cum - gap0 - virt; }
+            prev = cum;
+        }
+        return;
+    }
     u64 prev = k ? tbl_uniform(t.cum, k - 1) : 0;
     gap0 = prev;
     for (u64 j = k; j < k + 2 && j < t.n; j++) {
@@ -1372,16 +1414,25 @@ DEV void table_block_jumps(EM &em, const PlaceTable &t, u64 at, u64 G, u64 &gap0
         prev = cum;
     }
 }
+// WIDE emitters, once em.out is known: the segment bases as addresses
+template <class EM>
+DEV void wide_segments(EM &em) {
+    if constexpr (EM::WIDE) {
+        const u64 out = reinterpret_cast<u64>(em.out);
+        em.seg1 = out + em.seg1 * 32u;
+        em.seg2 = out + em.seg2 * 32u;
+    }
+}
 
 // --------------------------------------------------------------- the kernel
 // T = tile width in cells (contiguous run per row = 32*T bytes), R = tile rows =
 // units one wave expands per phase; a block needs parts >= 64/R waves.
 // One wave's program for its block (or its share of one).
-template <int L, int T, int R, int REPR, bool RC, bool EMITS, bool TABLE = false>
+template <int L, int T, int R, int REPR, bool RC, bool EMITS, bool TABLE = false, bool WIDE = false>
 DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d16, u16 *s_lk16,
                       const PlaceTable *tbl = nullptr) {
     using LY = Lay<L, RC>;
-    using EM = Em<T, R, REPR, RC, false, EMITS>;
+    using EM = Em<T, R, REPR, RC, false, EMITS, WIDE>;
     static_assert(R * EM::STRIDE_W * 8 >= 800, "tile must be able to hold the chain seeds");
     u32 *sW = reinterpret_cast<u32 *>(s_tile);   // [64]
     u32 *sA = sW + 64;         // [68] sA[k] = a-value A[k-3]: A[-3..0] = d,c,b,a of the pre-state
@@ -1495,7 +1546,7 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
         em.brk1 = em.brk2 = 0xffffffffu;
         em.gap1 = em.gap2 = 0;
         if constexpr (TABLE) {     // shared context: search the jump table, then the (<= 2) jumps inside the block
-            table_block_jumps(em, *tbl, tbl->base + first, (u64)LY::GATE_CELLS, gap0);
+            table_block_jumps(em, *tbl, tbl->base + first, (u64)LY::GATE_CELLS, gap0, tbl->ctx_blocks ? tctx : 0u);
         } else {
         for (u32 k = 0; k < p.n_breaks; k++) {
             const u64 bc = p.break_cell[k];
@@ -1510,6 +1561,7 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
             em.out = reinterpret_cast<uint4 *>(reinterpret_cast<u64 *>(p.gate) + (size_t)(ctx_base + first + gap0));
         else
             em.out = reinterpret_cast<uint4 *>(p.gate) + (size_t)(ctx_base + first + gap0) * 2u;
+        wide_segments(em);
     }
     size_t lk_blk = (size_t)blk * (size_t)LY::LOOKUP_CELLS;
     if constexpr (TABLE) {         // shared context: the caller's lookup entries queued before this block's digest
@@ -1617,6 +1669,19 @@ __global__ __launch_bounds__(64) void hsw_expand_table_kernel(ExpandParams p, Pl
     __shared__ u16 s_lk16[R * LY::LK_ROUND];
     expand_block<L, T, R, REPR, true, true, true>(p, s_tile, s_head, s_d16, s_lk16, &t);
 }
+// Columns by pointer table (hsw_gadget_bind_columns, PlaceTable::cum_stride != 0): the same, with 64-bit jumps
+// inside a block and a cum row per Context (an overload, so that the kernels above keep their names and code).
+template <int L, int T, int R, int REPR, bool WIDE>
+__global__ __launch_bounds__(64) void hsw_expand_table_kernel(ExpandParams p, PlaceTable t) {
+    static_assert(WIDE, "the wide instantiation only");
+    using LY = Lay<L, true>;
+    using EM = Em<T, R, REPR, true>;
+    __shared__ __attribute__((aligned(16))) u64 s_tile[(R + (R < 64 ? 1 : 0)) * EM::STRIDE_W];
+    __shared__ __attribute__((aligned(16))) u64 s_head[EM::REALIGN ? R * EM::HEAD_W : 2];
+    __shared__ u16 s_d16[R * LY::CALLS_ROUND];
+    __shared__ u16 s_lk16[R * LY::LK_ROUND];
+    expand_block<L, T, R, REPR, true, true, true, true>(p, s_tile, s_head, s_d16, s_lk16, &t);
+}
 
 // ------------------------------------------------------------------ launch
 template <int L, int T, int R>
@@ -1625,7 +1690,12 @@ static hipError_t launch_expand_table_LTR(const ExpandParams &p, const PlaceTabl
         return hipErrorInvalidValue;
     if ((p.flags & (HSW_K_COMPACT | HSW_K_M32)) || !(p.flags & HSW_K_INTERNALS) || !p.frame_every) return hipErrorInvalidValue;
     const dim3 grid((unsigned)(p.n_blocks * p.parts)), block(64);
-    if (p.flags & HSW_K_MONTGOMERY)
+    if (t.cum_stride) {          // columns by pointer table: the wide instantiations
+        if (p.flags & HSW_K_MONTGOMERY)
+            hipLaunchKernelGGL((hsw_expand_table_kernel<L, T, R, 1, true>), grid, block, 0, stream, p, t);
+        else
+            hipLaunchKernelGGL((hsw_expand_table_kernel<L, T, R, 0, true>), grid, block, 0, stream, p, t);
+    } else if (p.flags & HSW_K_MONTGOMERY)
         hipLaunchKernelGGL((hsw_expand_table_kernel<L, T, R, 1>), grid, block, 0, stream, p, t);
     else
         hipLaunchKernelGGL((hsw_expand_table_kernel<L, T, R, 0>), grid, block, 0, stream, p, t);

@@ -376,7 +376,7 @@ int Context::plan_layout(const std::vector<size_t> &sizes, bool rc_inputs, uint6
 
 int Context::adopt(Layout &nl, bool fresh_image, bool fresh_lookup, uint64_t clear_from) {
     const size_t K = contexts(), none = ~(size_t)0;
-    const bool table = shared && nl.max_rows, changed = !nl.same_map(layout);
+    const bool table = (shared || by_pointer) && nl.max_rows, changed = !nl.same_map(layout);
     if (bound) {                                          // the caller's memory: it fits what was declared, or it does not
         if (nl.columns > binding.columns_capacity || lookups_needed(nl) > binding.lookup_capacity) return HSW_ERR_TOO_LARGE;
         layout = std::move(nl);
@@ -444,10 +444,30 @@ int Context::upload_place() {
     if (!place_dirty && d_place) return HSW_OK;
     // [jump cells n][cumulative gaps n][per digest: the caller's lookup entries before it, cumulative]
     const Layout &l = layout;
-    const size_t n = l.break_cell.size(), H = l.digest_lookup0.size();
-    std::vector<uint64_t> h(2 * n + (H ? H : 1), 0);
-    for (size_t k = 0; k < n; k++) { h[k] = l.break_cell[k]; h[n + k] = l.break_cum[k]; }
-    for (size_t d = 0; d < H; d++) h[2 * n + d] = l.digest_lookup0[d] - l.origin_lookups - l.digest_entry0[d];
+    const size_t nb = l.break_cell.size(), H = shared ? l.digest_lookup0.size() : by_pointer ? init_capacity : 0;
+    std::vector<uint64_t> h;
+    if (by_pointer) {
+        // columns by pointer table: [jump cells n = breaks + 1][K cum rows of n][per digest], jump 0 at stream cell 0.
+        // A jump into image column k of Context c lands break_cum (columns one pitch apart) + what column k really
+        // lies from there: col_off - k * pitch, modulo 2^64 (PlaceTable::cum_stride)
+        const size_t n = nb + 1, K = contexts();
+        h.assign(n + K * n + (H ? H : 1), 0);
+        std::vector<uint64_t> col(n, 0);
+        for (size_t k = 0; k < nb; k++) {
+            h[1 + k] = l.break_cell[k];
+            uint64_t c = 0;
+            l.position(l.break_cell[k], &c, nullptr);
+            col[1 + k] = c - l.origin_column;
+        }
+        for (size_t c = 0; c < K; c++)
+            for (size_t k = 0; k < n; k++)
+                h[n + c * n + k] = (k ? l.break_cum[k - 1] : 0) + column_cell(c, col[k]) - col[k] * l.column_pitch();
+        for (size_t d = 0; d < H && shared; d++) h[n + K * n + d] = l.digest_lookup0[d] - l.origin_lookups - l.digest_entry0[d];
+    } else {
+        h.assign(2 * nb + (H ? H : 1), 0);
+        for (size_t k = 0; k < nb; k++) { h[k] = l.break_cell[k]; h[nb + k] = l.break_cum[k]; }
+        for (size_t d = 0; d < H; d++) h[2 * nb + d] = l.digest_lookup0[d] - l.origin_lookups - l.digest_entry0[d];
+    }
     if (d_place && h == place_host) { place_dirty = false; return HSW_OK; }   // the device already holds this table
     int device = 0;
     hsw_engine_stream(engine, nullptr, &device);
@@ -491,8 +511,16 @@ int Context::set_origin(const std::vector<size_t> &sizes, bool rc_inputs, uint64
     return HSW_OK;
 }
 
-int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b) {
+int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b_in, void *const *col_ptrs, size_t n_ptrs) {
     const uint64_t K = contexts();
+    hsw_region_binding b = b_in;
+    if (col_ptrs) {                                       // columns by pointer table: one pointer per column per proof
+        if (b.columns_capacity == 0 || b.columns_capacity > ~(size_t)0 / (size_t)K || n_ptrs != (size_t)K * (size_t)b.columns_capacity) return HSW_ERR_INVALID_ARG;
+        for (size_t i = 0; i < n_ptrs; i++)
+            if (!col_ptrs[i] || ((uintptr_t)col_ptrs[i] & 127u)) return HSW_ERR_INVALID_ARG;
+        b.d_columns = col_ptrs[0];
+        b.context_pitch = 0;
+    }
     const void *ptrs[4] = {b.d_columns, b.d_lookup, b.d_chip_dense, b.d_chip_spread};
     // (128 bytes: a column that starts on a line boundary keeps the realigned write-out on whole lines)
     for (const void *p : ptrs)
@@ -501,7 +529,7 @@ int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_re
     if (b.column_pitch < layout.max_rows || b.column_pitch > (1ull << 24)) return HSW_ERR_INVALID_ARG;
     if (b.chip_col_stride < b.chip_rows_capacity) return HSW_ERR_INVALID_ARG;
     if (K > 1) {
-        if (b.columns_capacity > ~0ull / b.column_pitch || b.context_pitch < b.columns_capacity * b.column_pitch) return HSW_ERR_INVALID_ARG;
+        if (!col_ptrs && (b.columns_capacity > ~0ull / b.column_pitch || b.context_pitch < b.columns_capacity * b.column_pitch)) return HSW_ERR_INVALID_ARG;
         if (b.lookup_pitch < b.lookup_capacity) return HSW_ERR_INVALID_ARG;
         if (b.context_pitch > ~0ull / (K * HSW_CELL_BYTES) || b.lookup_pitch > ~0ull / (K * HSW_CELL_BYTES) ||
             b.chip_context_pitch > ~0ull / (K * HSW_CELL_BYTES))
@@ -512,6 +540,11 @@ int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_re
     nl.image_pitch = K > 1 ? b.context_pitch : 0;
     const int rc = plan_layout(sizes, rc_inputs, layout.max_rows, declared, &nl);
     if (rc != HSW_OK) return rc;
+    std::vector<uint64_t> off;
+    if (col_ptrs) {
+        off.resize(n_ptrs);
+        for (size_t i = 0; i < n_ptrs; i++) off[i] = (uint64_t)((uintptr_t)col_ptrs[i] - (uintptr_t)col_ptrs[0]) / HSW_CELL_BYTES;
+    }
     if (nl.columns > b.columns_capacity || lookups_needed(nl) > b.lookup_capacity || ctx_chip_rows() > b.chip_rows_capacity) return HSW_ERR_TOO_LARGE;
     // (the caller ran on a drained engine: nothing still writes the buffers given up here)
     if (!bound) {
@@ -524,6 +557,8 @@ int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_re
     free_compact_staging();
     bound = true;
     binding = b;
+    by_pointer = col_ptrs != nullptr;
+    col_off.swap(off);
     d_gate = b.d_columns; d_lookup = b.d_lookup; d_chip_dense = b.d_chip_dense; d_chip_spread = b.d_chip_spread;
     chip_col_stride = (size_t)b.chip_col_stride;
     image_columns = b.columns_capacity;
@@ -556,6 +591,8 @@ int Context::unbind(const std::vector<size_t> &sizes, bool rc_inputs) {
     if (he == hipSuccess) he = fresh_zeroed(&cs, col_bytes);
     if (he != hipSuccess) { (void)hipFree(img); (void)hipFree(lk); (void)hipFree(cd); (void)hipFree(cs); return hip_status(he); }
     bound = false;
+    by_pointer = false;
+    col_off.clear();
     binding = hsw_region_binding{};
     d_gate = img; d_lookup = lk; d_chip_dense = cd; d_chip_spread = cs;
     chip_col_stride = stride;
@@ -586,15 +623,21 @@ struct Launch {
         : c(ctx), in_blocks(inputs_in_pinned ? ctx.dp_blocks : ctx.d_blocks), in_pre(inputs_in_pinned ? ctx.dp_pre : ctx.d_pre_states),
           flags(repr_flags) {
         const Layout &l = c.layout;
-        if (c.shared && l.max_rows) {
+        if (c.table_path()) {
             const uint64_t *d_place = static_cast<const uint64_t *>(c.d_place);
-            const size_t n = l.break_cell.size();
+            size_t n = l.break_cell.size();
             tbl = PlaceTable{d_place, d_place + n, d_place + 2 * n, n, 0};
+            if (c.by_pointer) {                          // jump 0 at cell 0, a cum row per Context (upload_place)
+                n += 1;
+                tbl = PlaceTable{d_place, d_place + n, d_place + n + c.contexts() * n, n, 0};
+                tbl.cum_stride = n;
+            }
             period.place = &tbl;
             per = &period;
-            if (c.group_m) {                             // the periodic table: one Context's, every l.period stream cells
-                tbl.ctx_blocks = c.ctx_blocks; tbl.ctx_stream = l.period; tbl.ctx_image = l.image_cells();
-                period.stream_cells = l.period; period.image_cells = l.image_cells();
+            if (l.period) {                              // the periodic table: one Context's, every l.period stream cells
+                const uint64_t image = c.by_pointer ? 0 : l.image_cells();      // (by pointer: the Context's cum row says where)
+                tbl.ctx_blocks = c.blocks_per_context(); tbl.ctx_stream = l.period; tbl.ctx_image = image;
+                period.stream_cells = l.period; period.image_cells = image;
             }
             period.chip_ctx_extra = c.chip_ctx_extra(); period.chip_rows_checked = c.bound;
         } else if (l.max_rows) {
@@ -632,7 +675,7 @@ struct Launch {
         const Layout &l = c.layout;
         // (context images: the run's first block in ITS Context's image; the breaks are that Context's)
         const uint64_t ctx0 = l.period ? r0.block_cell / l.period : 0, local = r0.block_cell - ctx0 * l.period;
-        a.d_gate = static_cast<uint8_t *>(c.gate_stream()) + (size_t)(ctx0 * l.image_cells() + local) * cb;
+        a.d_gate = static_cast<uint8_t *>(c.gate_stream()) + (size_t)((c.by_pointer ? 0 : ctx0 * l.image_cells()) + local) * cb;
         a.d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)r0.block_lookup * cb;
         a.frame_every = fs.n_blocks;
         // between the block streams of two digests: one epilogue, the next prologue -- and the next Context's zero cell
@@ -644,7 +687,15 @@ struct Launch {
         if (c.group_m) a.frame_lookups = c.lookup_pitch() - (uint64_t)fs.n_blocks * c.shape.lookup_cells_per_block;
         if (period.place) {                              // the run's first block cell, its digests' lookup shifts
             tbl.base = local;
-            tbl.lk_shift = tbl.cell + 2 * tbl.n + (c.group_m ? digest0 % c.group_m : digest0);
+            const uint64_t *shifts = c.by_pointer ? tbl.cum + c.contexts() * tbl.n : tbl.cell + 2 * tbl.n;
+            tbl.lk_shift = shifts + (c.group_m ? digest0 % c.group_m : c.context_images ? 0 : digest0);
+            if (c.by_pointer && l.period) {
+                // a pointer table's Contexts: block b of the launch is block b % frame_every of Context ctx0 + b / frame_every,
+                // whose cells go through ITS cum row from the Context's own stream cell on -- no image offset (ctx_cells = 0),
+                // and stepping a Context steps the stream back by the Context's blocks: frame_cells = -(frame_every * G), mod 2^64
+                tbl.ctx0 = ctx0;
+                a.frame_cells = 0 - (uint64_t)fs.n_blocks * c.shape.gate_cells_per_block;
+            }
         } else if (frame_pack) {                         // breaks before the launch's first cell are pure offsets
             rel.n_breaks = abs.n_breaks;
             for (uint32_t k = 0; k < rel.n_breaks; k++) {
@@ -784,7 +835,7 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
         }
         const size_t G = ctx.shape.gate_cells_per_block;
         // shared context: every launch placed by the jump table (uploaded when the layout changed)
-        if (ctx.shared && ctx.layout.max_rows && (rc = ctx.upload_place()) != HSW_OK) break;
+        if (ctx.table_path() && (rc = ctx.upload_place()) != HSW_OK) break;
         Launch L(ctx, zero_copy, ctx.repr_flags);
         if (!ctx.whole) {
             // one call covers every block of the batch
@@ -818,7 +869,7 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                 // context images: Context h's lookup column is cells [h*Lp, (h+1)*Lp), the caller's queued cells first
                 // (lookup_pitch() apart: Lp, or what the caller bound)
                 if (ctx.context_images) lc = (uint64_t)(cur_hash_idx + i) * ctx.lookup_pitch() + ctx.layout.origin_lookups;
-                if (table && !ctx.group_m) lc = ctx.layout.digest_lookup0[cur_hash_idx + i];   // after the caller's entries of the interlude
+                if (table && ctx.shared && !ctx.group_m) lc = ctx.layout.digest_lookup0[cur_hash_idx + i];   // after the caller's entries of the interlude
                 if (ctx.group_m) {                           // digest j of Context cx: that Context's stream, image and lookup column
                     const size_t cx = (cur_hash_idx + i) / ctx.group_m, j = (cur_hash_idx + i) % ctx.group_m;
                     gc = cx * ctx.layout.period + ctx.layout.digest_cell0[j];
@@ -1154,6 +1205,20 @@ int hsw_gadget_bind_region(hsw_gadget *g, const hsw_region_binding *b) try {
     return rc;
 } HSW_NO_UNWIND
 
+int hsw_gadget_bind_columns(hsw_gadget *g, const hsw_region_binding *b, void *const *d_column_ptrs, size_t n_ptrs) try {
+    if (!g || !b || !d_column_ptrs) return HSW_ERR_INVALID_ARG;
+    hsw::Context &c = *g->ctx;
+    if (!c.whole || !c.layout.max_rows) return HSW_ERR_UNSUPPORTED;
+    if (g->cfg.cur_hash_idx != 0 || c.blocks_done != 0 || c.gate_cursor != 0) return HSW_ERR_INVALID_ARG;   // a fresh or reset gadget
+    // (the table-path kernels: the 8-bit spread table, as for shared contexts)
+    if (c.shape.num_bits_lookup != 8) return HSW_ERR_UNSUPPORTED;
+    int rc = hsw_engine_synchronize(c.engine);
+    if (rc != HSW_OK) return rc;
+    rc = c.bind(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, *b, d_column_ptrs, n_ptrs);
+    if (rc == HSW_OK) hsw::drop_region_tape_positions(g->tape);
+    return rc;
+} HSW_NO_UNWIND
+
 int hsw_gadget_region_binding(const hsw_gadget *g, hsw_region_binding *out) try {
     if (!g || !out) return HSW_ERR_INVALID_ARG;
     const hsw::Context &c = *g->ctx;
@@ -1279,7 +1344,26 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
             he = hipMemcpyAsync(static_cast<uint8_t *>(h) + cell0 * cb, static_cast<const uint8_t *>(d) + cell0 * cb,
                                 cells * cb, hipMemcpyDeviceToHost, stream);
     };
-    if (dst->gate && c.whole && c.layout.max_rows) {
+    if (dst->gate && c.by_pointer) {
+        // columns by pointer table: the host buffer is an UNBOUND gadget's (K images of columns x max_rows cells back to
+        // back); every run of the stream between two jumps lies in one column and is one copy from that column's allocation
+        const hsw::Layout &l = c.layout;
+        const uint64_t K = l.period ? (c.gate_cursor + l.period - 1) / l.period : 1, R = l.max_rows, P = l.column_pitch();
+        for (uint64_t h = 0; h < K; h++) {
+            const uint64_t end = !l.period ? c.gate_cursor : c.gate_cursor < (h + 1) * l.period ? c.gate_cursor - h * l.period : l.period;
+            uint64_t lo = 0;
+            for (size_t k = 0; k <= l.break_cell.size() && lo < end; k++) {
+                const uint64_t hi = k < l.break_cell.size() && l.break_cell[k] < end ? l.break_cell[k] : end;
+                if (hi > lo && he == hipSuccess) {
+                    const uint64_t at = lo + l.origin_row + l.gap_at(lo), col = at / P, row = at % P;   // (the run's first cell)
+                    he = hipMemcpyAsync(static_cast<uint8_t *>(dst->gate) + (size_t)((h * l.columns + col) * R + row) * cb,
+                                        static_cast<const uint8_t *>(c.d_gate) + (size_t)(c.column_cell(h, col) + row) * cb,
+                                        (size_t)(hi - lo) * cb, hipMemcpyDeviceToHost, stream);
+                }
+                lo = hi > lo ? hi : lo;
+            }
+        }
+    } else if (dst->gate && c.whole && c.layout.max_rows) {
         // the runs of the stream between two jumps up to the cursor, for every assigned Context (one, unless context
         // images: K images back to back, host layout = device layout).  Rows above the origin, the gaps at column ends
         // and the interludes' cells are the caller's or nobody's: never touched
@@ -1457,7 +1541,7 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
     hsw::Context &c = *g->ctx;
     if (c.repr_flags & HSW_REPR_COMPACT64) return HSW_ERR_UNSUPPORTED;         // 32-byte cells only
     // shared context: every launch checks through the jump table (the layout of the digests so far is final)
-    if (c.shared && c.layout.max_rows) {
+    if (c.table_path()) {
         const int rc0 = c.upload_place();
         if (rc0 != HSW_OK) return rc0;
     }
@@ -1524,7 +1608,7 @@ int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region 
         uint64_t col = 0, row = 0;
         c.layout.position(C - 1, &col, &row);
         out->last_column_rows = row + 1;
-        out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * c.layout.image_cells()) * cb;
+        out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)c.column_cell(h, 0) * cb;   // (by pointer table: proof h's column 0)
     } else {
         out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * C) * cb;   // linear: the Context's stream
     }

@@ -150,6 +150,18 @@ class Context {
     // declared; the layout calls check what they need against its capacities (adopt)
     bool bound = false;
     hsw_region_binding binding{};
+    // hsw_gadget_bind_columns: a bound region whose image columns are one allocation each -- col_off[c *
+    // binding.columns_capacity + k] = cells from proof 0's column 0 (d_gate) to column k of proof c, modulo 2^64.  Every
+    // launch then goes through the table path (the jumps of a plain image, a Context per proof of context images) with a
+    // cum row per Context (PlaceTable::cum_stride, upload_place); layout.pitch = binding.column_pitch keeps positions
+    // and break gaps those of a pitch-bound region, layout.image_pitch is 0 and no code adds h * image_cells()
+    bool by_pointer = false;
+    std::vector<uint64_t> col_off;
+    bool table_path() const { return (shared || by_pointer) && layout.max_rows != 0; }
+    // cells from d_gate to row 0 of image column k of Context c
+    uint64_t column_cell(uint64_t c, uint64_t k) const {
+        return by_pointer ? col_off[(size_t)(c * binding.columns_capacity + k)] : c * layout.image_cells() + k * layout.column_pitch();
+    }
     uint64_t lookup_pitch() const { return bound && contexts() > 1 ? binding.lookup_pitch : ctx_lookups(); }
     size_t blocks_per_context() const { return context_images ? capacity_blocks / init_capacity : group_m ? ctx_blocks : capacity_blocks; }
     uint64_t ctx_limb_calls() const { return (uint64_t)blocks_per_context() * shape.limb_calls_per_block; }
@@ -168,7 +180,8 @@ class Context {
     }
     // the library's own zeroed buffers again, sized for the layout without pitches (sizes / rc_inputs: the gadget's)
     int unbind(const std::vector<size_t> &sizes, bool rc_inputs);
-    int bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b);
+    // ptrs: NULL = hsw_gadget_bind_region; else hsw_gadget_bind_columns' table of contexts() * b.columns_capacity pointers
+    int bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b, void *const *ptrs = nullptr, size_t n_ptrs = 0);
     bool zero_loaded = false;        // Context.zero_cell (first load_zero: compression.rs:34 of the first block)
     uint64_t gate_cursor = 0, gate_capacity = 0;       // cells
     void *d_lookup = nullptr;

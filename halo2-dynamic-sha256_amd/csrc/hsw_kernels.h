@@ -116,6 +116,14 @@ struct PlaceTable {
     // base + (b % frame_every) * G and land (b / frame_every) * ctx_image further, and its lookup entries follow the
     // launch's first by (b / frame_every) * (frame_every * LOOKUP_CELLS + frame_lookups), lk_shift unused
     uint64_t ctx_blocks, ctx_stream, ctx_image;
+    // Columns by pointer table (hsw_gadget_bind_columns; 0 = the periodic case above): every image column is an
+    // allocation of its own, so a jump lands at an arbitrary 64-bit distance and every Context has a cum row of its
+    // own, cum_stride words after the previous one's -- Context c reads cum[c * cum_stride + k].  Jump 0 is then a
+    // jump at stream cell 0 whose "gap" is the distance of the Context's column 0 from PlaceTable-less `gate`
+    // (modulo 2^64, in cells), so every cell has a jump at or before it, and ctx_image is 0.  The wide
+    // instantiations of the table-path kernels (template parameter WIDE) are launched for such a table.
+    // ctx0: the Context of the launch's block 0 (block kernels; the frame kernels take the Context from the digest)
+    uint64_t cum_stride, ctx0;
 };
 
 struct FrameDesc;   // hsw_frame.hpp

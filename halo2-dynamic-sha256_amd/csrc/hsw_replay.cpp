@@ -249,6 +249,8 @@ int hsw_gadget_region_tape(hsw_gadget *g, hsw_region_tape *out) try {
 } HSW_NO_UNWIND
 
 int hsw_gadget_download_region_distinct(hsw_gadget *g, void *distinct, size_t cap_cells, size_t *n_cells) try {
+    if (g && g->ctx->by_pointer) return HSW_ERR_UNSUPPORTED;   // columns by pointer table: no 32-bit image positions, no host mirror
+
     if (!g || (!distinct && cap_cells)) return HSW_ERR_INVALID_ARG;
     Context &c = *g->ctx;
     if (c.repr_flags & HSW_REPR_COMPACT64) return HSW_ERR_UNSUPPORTED;
@@ -295,6 +297,8 @@ int hsw_gadget_download_region_distinct(hsw_gadget *g, void *distinct, size_t ca
 } HSW_NO_UNWIND
 
 int hsw_gadget_replay_region(hsw_gadget *g, const void *distinct, const hsw_region_host *dst, unsigned threads) try {
+    if (g && g->ctx->by_pointer) return HSW_ERR_UNSUPPORTED;   // columns by pointer table: no 32-bit image positions, no host mirror
+
     if (!g || !distinct || !dst) return HSW_ERR_INVALID_ARG;
     Context &c = *g->ctx;
     if (c.repr_flags & HSW_REPR_COMPACT64) return HSW_ERR_UNSUPPORTED;

@@ -178,8 +178,33 @@ __global__ __launch_bounds__(256) void hsw_verify_frame_table_kernel(FrameVerify
 #include "hsw_verify_frame_body.inc"
 }
 
+// Columns by pointer table (PlaceTable::cum_stride != 0): every Context is checked through its own cum row (overloads,
+// so that the kernels above keep their names and code).
+template <bool MONT, bool WIDE>
+__global__ __launch_bounds__(256) void hsw_verify_table_kernel(VerifyParams p, PlaceTable t) {
+    static_assert(WIDE, "the wide instantiation only");
+    constexpr bool TABLE = true;
+    // the block's Context (a launch over several Contexts: one per frame_every blocks), workgroup-uniform
+    if (t.ctx_blocks) t.cum += (t.ctx0 + (blockIdx.x / p.slices) / p.frame_every) * t.cum_stride;
+    const PlaceTable *tbl = &t;
+#include "hsw_verify_block_body.inc"
+}
+template <bool MONT, bool WIDE>
+__global__ __launch_bounds__(256) void hsw_verify_frame_table_kernel(FrameVerifyParams p, PlaceTable t) {
+    static_assert(WIDE, "the wide instantiation only");
+    constexpr bool TABLE = true;
+    if (p.ctx_stream) t.cum += (p.descs[blockIdx.x].prologue_cell / p.ctx_stream) * t.cum_stride;
+    const PlaceTable *tbl = &t;
+#include "hsw_verify_frame_body.inc"
+}
+
 hipError_t launch_verify_frames_table(const FrameVerifyParams &p, const PlaceTable &t, size_t n_digests, hipStream_t stream) {
     if (n_digests == 0) return hipSuccess;
+    if (t.cum_stride) {
+        if (p.montgomery) hipLaunchKernelGGL((hsw_verify_frame_table_kernel<true, true>), dim3((unsigned)n_digests), dim3(256), 0, stream, p, t);
+        else hipLaunchKernelGGL((hsw_verify_frame_table_kernel<false, true>), dim3((unsigned)n_digests), dim3(256), 0, stream, p, t);
+        return hipGetLastError();
+    }
     if (p.montgomery) hipLaunchKernelGGL(hsw_verify_frame_table_kernel<true>, dim3((unsigned)n_digests), dim3(256), 0, stream, p, t);
     else hipLaunchKernelGGL(hsw_verify_frame_table_kernel<false>, dim3((unsigned)n_digests), dim3(256), 0, stream, p, t);
     return hipGetLastError();
@@ -187,6 +212,11 @@ hipError_t launch_verify_frames_table(const FrameVerifyParams &p, const PlaceTab
 
 hipError_t launch_verify_table(const VerifyParams &p, const PlaceTable &t, size_t n_blocks, hipStream_t stream) {
     if (n_blocks == 0) return hipSuccess;
+    if (t.cum_stride) {
+        if (p.montgomery) hipLaunchKernelGGL((hsw_verify_table_kernel<true, true>), dim3((unsigned)(n_blocks * p.slices)), dim3(256), 0, stream, p, t);
+        else hipLaunchKernelGGL((hsw_verify_table_kernel<false, true>), dim3((unsigned)(n_blocks * p.slices)), dim3(256), 0, stream, p, t);
+        return hipGetLastError();
+    }
     if (p.montgomery) hipLaunchKernelGGL(hsw_verify_table_kernel<true>, dim3((unsigned)(n_blocks * p.slices)), dim3(256), 0, stream, p, t);
     else hipLaunchKernelGGL(hsw_verify_table_kernel<false>, dim3((unsigned)(n_blocks * p.slices)), dim3(256), 0, stream, p, t);
     return hipGetLastError();

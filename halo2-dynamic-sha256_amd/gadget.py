@@ -146,6 +146,7 @@ class Sha256DynamicConfig:
         if columns is None:
             self._ok(self.lib.hsw_gadget_bind_region(self.h, None))
             self._bound = None
+            self._column_ptrs = None
             return
 
         def ptr(x):
@@ -154,6 +155,23 @@ class Sha256DynamicConfig:
                             ptr(chip_dense), ptr(chip_spread), chip_col_stride, chip_rows_capacity, chip_context_pitch)
         self._ok(self.lib.hsw_gadget_bind_region(self.h, C.byref(b)))
         self._bound = (columns, lookup, chip_dense, chip_spread)      # keeps tensors alive while they are bound
+        self._column_ptrs = None
+
+    def bind_columns(self, column_ptrs, column_pitch, columns_capacity, lookup=None, lookup_capacity=0, chip_dense=None,
+                     chip_spread=None, chip_col_stride=0, chip_rows_capacity=0, lookup_pitch=0, chip_context_pitch=0):
+        """hsw_gadget_bind_columns: like bind_region, but every FlexGate image column is an allocation of its own.
+        column_ptrs[c * columns_capacity + k]: torch tensor or raw device pointer of row 0 of image column k of proof c
+        (K * columns_capacity entries; the caller keeps them alive); column_pitch: cells each column holds.  Lookup and
+        chip areas as in bind_region.  bind_region(None) unbinds."""
+        def ptr(x):
+            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x or 0)
+        ptrs = [ptr(x) for x in column_ptrs]
+        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+        b = N.RegionBinding(None, column_pitch, columns_capacity, 0, ptr(lookup), lookup_capacity, lookup_pitch,
+                            ptr(chip_dense), ptr(chip_spread), chip_col_stride, chip_rows_capacity, chip_context_pitch)
+        self._ok(self.lib.hsw_gadget_bind_columns(self.h, C.byref(b), arr, len(ptrs)))
+        self._bound = (list(column_ptrs), lookup, chip_dense, chip_spread)
+        self._column_ptrs = ptrs
 
     def _unbound_only(self, what):
         """The numpy conveniences size their host buffers for library-owned geometry; a bound gadget's host layout
@@ -352,8 +370,11 @@ class Sha256DynamicConfig:
         multi = self.context_images or self.n_contexts is not None
         k = 1 if not multi else self.n_contexts if self.n_contexts is not None else len(self.max_variable_byte_sizes)
         ncols, cols, mr = self.engine.ncols, int(v.columns), int(v.max_rows)
-        gate = np.stack([np.stack([grab(b.d_columns + (c * int(b.context_pitch) + j * int(b.column_pitch)) * 32, mr)
-                                   for j in range(cols)]) for c in range(k)])
+        cp, cap = getattr(self, "_column_ptrs", None), int(b.columns_capacity)
+
+        def column(c, j):            # columns by pointer table: the caller's own pointer of (proof c, column j)
+            return cp[c * cap + j] if cp else b.d_columns + (c * int(b.context_pitch) + j * int(b.column_pitch)) * 32
+        gate = np.stack([np.stack([grab(column(c, j), mr) for j in range(cols)]) for c in range(k)])
         lp = int(self.context_region(0).lookup_cells) if multi else int(v.lookup_cells)
         lookup = np.concatenate([grab(b.d_lookup + c * int(b.lookup_pitch) * 32, lp) for c in range(k)])
         per = rows // k if multi else rows             # chip rows of one proof (a whole number of rows each)

@@ -360,7 +360,8 @@ typedef struct hsw_launch_info {
     uint32_t internals;    /* engine mode HSW_MODE_HALO2_INTERNALS */
     uint32_t parts;        /* waves per block */
     uint32_t split;        /* 0: every wave takes a share of every phase; 1: one phase program per wave;
-                              2: one sub-unit program per wave (tiny batches) */
+                              2: one sub-unit program per wave (tiny batches); + 4: the wide table-path
+                              instantiation of a gadget bound by hsw_gadget_bind_columns */
     uint32_t seq;          /* expansion launches of this engine so far (wraps): the difference across a call is the
                               number of expansion launches that call made.  Counts every launch of the streaming and
                               of the small-batch kernel, in every mode -- a call of more than 2^20 blocks is one launch
@@ -722,8 +723,35 @@ typedef struct hsw_region_binding {
     uint64_t chip_context_pitch; /* cells from proof c to c+1 */
 } hsw_region_binding;
 int hsw_gadget_bind_region(hsw_gadget *g, const hsw_region_binding *b);   /* b = NULL: back to library-owned, zeroed buffers */
-/* The geometry in force, also when library-owned (then: d_gate / max_rows / columns x max_rows, Lp, consecutive chip rows). */
+/* The geometry in force, also when library-owned (then: d_gate / max_rows / columns x max_rows, Lp, consecutive chip rows).
+ * Columns by pointer table (hsw_gadget_bind_columns): d_columns = image column 0 of proof 0 and context_pitch = 0 --
+ * "columns by pointer table": the other columns are wherever the caller's table said, no pitch describes them. */
 int hsw_gadget_region_binding(const hsw_gadget *g, hsw_region_binding *out);
+/* Like hsw_gadget_bind_region, but the FlexGate image columns are given one pointer each -- a prover that holds its
+ * advice as one allocation per column per proof (halo2_proofs' Vec<Polynomial<F>>), in no address order:
+ *   d_column_ptrs[c * b->columns_capacity + k] = device address of row 0 of image column k of proof c
+ * (host array of n_ptrs = K * columns_capacity pointers, copied by the call; K = 1 for single-proof gadgets).
+ * b->d_columns and b->context_pitch are ignored; b->column_pitch = cells each column allocation holds
+ * (max_rows <= column_pitch <= 2^24; rows [max_rows, column_pitch) are never written); the lookup and chip areas
+ * exactly as in hsw_gadget_bind_region (they keep the pitch model).  Same gadget kinds, same "fresh or reset gadget
+ * only", same ownership rules, 32-byte cells, canonical or Montgomery; hsw_gadget_bind_region(g, NULL) unbinds.
+ * HSW_ERR_INVALID_ARG: a null pointer or one not 128-byte aligned (table entries included), n_ptrs != K *
+ * columns_capacity, a pitch out of range; HSW_ERR_TOO_LARGE: columns_capacity below the layout's columns, or a lookup /
+ * chip capacity below what the layout needs; HSW_ERR_UNSUPPORTED without a column image.  A failing call leaves the
+ * previous binding or the library's buffers in place.  Disjointness and device residency are NOT checked.
+ * The binding survives hsw_gadget_reset and every layout call whose result still fits; a layout that needs more
+ * columns than columns_capacity returns HSW_ERR_TOO_LARGE and changes nothing.
+ * Binding changes addresses, never positions: hsw_gadget_cell_position, hsw_gadget_result_cells and hsw_hash_result
+ * are those of an unbound gadget.  hsw_gadget_streams reports proof 0's column-0 pointer as d_gate and
+ * hsw_gadget_context_region(g, c) proof c's column-0 pointer as d_image -- the further columns are the caller's
+ * table's, not d_gate + a pitch.  hsw_gadget_verify works.  hsw_gadget_download_region works: its `gate` host buffer
+ * is laid out as an UNBOUND gadget's (K images of columns x max_rows cells back to back, used rows only -- a host
+ * buffer cannot mirror scattered device allocations), its lookup and chip buffers as for a pitch-bound gadget.
+ * hsw_gadget_region_tape works (host only).  hsw_gadget_download_region_distinct, hsw_gadget_replay_region,
+ * hsw_gadget_download_region_compact, hsw_gadget_seek and hsw_gadget_place return HSW_ERR_UNSUPPORTED.
+ * hsw_last_launch reports such a gadget's expansion launches with bit 2 of `split` set (split = 4 or 6): the wide
+ * instantiations hsw_expand_table_kernel<.., true> / hsw_small_table_kernel<.., true>. */
+int hsw_gadget_bind_columns(hsw_gadget *g, const hsw_region_binding *b, void *const *d_column_ptrs, size_t n_ptrs);
 /* Start the next synthesis pass with the same buffers and layout: every cursor back to
  * its initial value (cur_hash_idx, num_limb_sum, the stream cursors, the Context's zero
  * cell).  What the reference's harnesses do by cloning the config per synthesis

@@ -455,6 +455,13 @@ extern "C" {
     pub fn hsw_gadget_context_region(g: *const hsw_gadget, h: usize, out: *mut hsw_context_region) -> c_int;
     pub fn hsw_gadget_bind_region(g: *mut hsw_gadget, b: *const hsw_region_binding) -> c_int;
     pub fn hsw_gadget_region_binding(g: *const hsw_gadget, out: *mut hsw_region_binding) -> c_int;
+    /// Like hsw_gadget_bind_region with one device pointer per image column per proof (include/hsw.h).
+    pub fn hsw_gadget_bind_columns(
+        g: *mut hsw_gadget,
+        b: *const hsw_region_binding,
+        d_column_ptrs: *const *mut c_void,
+        n_ptrs: usize,
+    ) -> c_int;
     pub fn hsw_frame_query(shape: *const hsw_shape, max_variable_byte_size: usize, is_input_range_check: c_int,
                            out: *mut hsw_frame_shape) -> c_int;
     pub fn hsw_frame_tape(shape: *const hsw_shape, max_variable_byte_size: usize, is_input_range_check: c_int,

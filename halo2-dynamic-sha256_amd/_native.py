@@ -185,6 +185,14 @@ class RegionBinding(C.Structure):
                 ("chip_rows_capacity", C.c_uint64), ("chip_context_pitch", C.c_uint64)]
 
 
+class ColumnTables(C.Structure):
+    """hsw_column_tables: host arrays of device pointers, one per column per proof (hsw_gadget_bind_column_tables)."""
+    _fields_ = [("d_column_ptrs", C.POINTER(C.c_void_p)), ("n_column_ptrs", C.c_size_t),
+                ("d_lookup_ptrs", C.POINTER(C.c_void_p)), ("n_lookup_ptrs", C.c_size_t),
+                ("d_chip_dense_ptrs", C.POINTER(C.c_void_p)), ("d_chip_spread_ptrs", C.POINTER(C.c_void_p)),
+                ("n_chip_ptrs", C.c_size_t)]
+
+
 class ContextRegion(C.Structure):
     """hsw_context_region: where proof h of an HSW_GADGET_CONTEXT_IMAGES gadget lives on the device."""
     _fields_ = [("d_image", C.c_void_p), ("d_lookup", C.c_void_p), ("d_chip_dense", C.c_void_p), ("d_chip_spread", C.c_void_p)] + \
@@ -212,7 +220,7 @@ SYMBOLS = (
     "hsw_gadget_download_region_compact", "hsw_region_widen", "hsw_gadget_result_cells",
     "hsw_gadget_set_origin", "hsw_gadget_region_tape", "hsw_gadget_download_region_distinct", "hsw_gadget_replay_region",
     "hsw_gadget_context_region", "hsw_gadget_set_digest_origin", "hsw_gadget_create_contexts",
-    "hsw_gadget_bind_region", "hsw_gadget_region_binding", "hsw_gadget_bind_columns",
+    "hsw_gadget_bind_region", "hsw_gadget_region_binding", "hsw_gadget_bind_columns", "hsw_gadget_bind_column_tables",
 )
 
 
@@ -368,6 +376,8 @@ def lib():
         L.hsw_gadget_bind_region.argtypes = [vp, C.POINTER(RegionBinding)]
         L.hsw_gadget_bind_columns.restype = C.c_int
         L.hsw_gadget_bind_columns.argtypes = [vp, C.POINTER(RegionBinding), C.POINTER(C.c_void_p), C.c_size_t]
+        L.hsw_gadget_bind_column_tables.restype = C.c_int
+        L.hsw_gadget_bind_column_tables.argtypes = [vp, C.POINTER(RegionBinding), C.POINTER(ColumnTables)]
         L.hsw_gadget_region_binding.restype = C.c_int
         L.hsw_gadget_region_binding.argtypes = [vp, C.POINTER(RegionBinding)]
         L.hsw_gadget_create_contexts.restype = C.c_int

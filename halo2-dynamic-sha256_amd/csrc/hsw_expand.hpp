@@ -263,7 +263,12 @@ DEV void em_sync() {
 // gaps so far), thr1 / thr2 = the virtual byte offset the segment after brk1 / brk2 starts at.  A store is one
 // 16-byte piece of one cell: it never spans two segments.
 template <bool WIDE_> struct EmSegs {};
-template <> struct EmSegs<true> { u64 seg1, seg2; u32 thr1, thr2; };
+template <> struct EmSegs<true> {
+    u64 seg1, seg2; u32 thr1, thr2;
+    // lookup and chip columns by pointer table (PlaceTable::chip_row): this block's Context's row -- [2 k] dense,
+    // [2 k + 1] spread offset of chip column k -- or null (the pitch model)
+    const uint64_t *chip_row;
+};
 
 template <int T, int R, int REPR_, bool RC_, bool NO_REALIGN_ = false, bool EMITS_ = true, bool WIDE_ = false>
 struct Em : EmSegs<WIDE_> {
@@ -906,6 +911,14 @@ DEV void flush_chip(const EM &em, const ExpandParams &p, u64 block_first_limb) {
         constexpr u32 CB = EM::COMPACT ? 8u : 32u;
         char *cdb = reinterpret_cast<char *>(p.chip_dense) + cell0 * CB;
         char *csb = reinterpret_cast<char *>(p.chip_spread) + cell0 * CB;
+        if constexpr (EM::WIDE) {
+            // chip columns by pointer table: the column's own two offsets (scalar loads: em.chip_row is wave-uniform),
+            // dense and spread each from its own pointer; the lane offsets below stay 32-bit
+            if (em.chip_row) {
+                cdb = reinterpret_cast<char *>(p.chip_dense) + (size_t)(tbl_uniform(em.chip_row, 2 * c) + (row_lo - row0)) * CB;
+                csb = reinterpret_cast<char *>(p.chip_spread) + (size_t)(tbl_uniform(em.chip_row, 2 * c + 1) + (row_lo - row0)) * CB;
+            }
+        }
         if constexpr (EM::COMPACT) {
             for (u32 k = lane; k < count; k += 64) {
                 const u32 n = n0 + k * (u32)ncols;
@@ -1414,6 +1427,17 @@ DEV void table_block_jumps(EM &em, const PlaceTable &t, u64 at, u64 G, u64 &gap0
         prev = cum;
     }
 }
+// WIDE emitters: the chip row and the lookup offset of the block's Context (ctx: counted from the launch's first,
+// 0 for a single Context).  lk: what the Context's lookup column lies further from the launch's first Context's
+// than the launch's frame_lookups steps (PlaceTable::lk_row)
+template <class EM>
+DEV void wide_context_rows(EM &em, const PlaceTable &t, u32 ncols, u32 ctx, size_t &lk) {
+    if constexpr (EM::WIDE) {
+        const u64 c = t.ctx0 + (u64)(u32)__builtin_amdgcn_readfirstlane((int)ctx);
+        em.chip_row = t.chip_row ? t.chip_row + c * 2u * ncols : nullptr;
+        if (t.lk_row) lk += (size_t)(tbl_uniform(t.lk_row, c) - tbl_uniform(t.lk_row, t.ctx0));
+    }
+}
 // WIDE emitters, once em.out is known: the segment bases as addresses
 template <class EM>
 DEV void wide_segments(EM &em) {
@@ -1568,6 +1592,7 @@ DEV void expand_block(const ExpandParams &p, u64 *s_tile, u64 *s_head, u16 *s_d1
         lk_blk += (size_t)tctx * (size_t)p.frame_lookups;
         if (!tbl->ctx_blocks)      // (a Context group's launch is ONE digest index: its shift is in p.lookup, frame_lookups steps a Context)
             lk_blk += (size_t)(tbl_uniform(tbl->lk_shift, (u64)tctx) - tbl_uniform(tbl->lk_shift, 0));
+        wide_context_rows(em, *tbl, p.ncols, tbl->ctx_blocks ? tctx : 0u, lk_blk);
     } else if constexpr (RC) {
         if (p.frame_every) lk_blk += (size_t)(blk / p.frame_every) * (size_t)p.frame_lookups;
     }

@@ -381,7 +381,7 @@ int Context::adopt(Layout &nl, bool fresh_image, bool fresh_lookup, uint64_t cle
         if (nl.columns > binding.columns_capacity || lookups_needed(nl) > binding.lookup_capacity) return HSW_ERR_TOO_LARGE;
         layout = std::move(nl);
         lookup_capacity = (uint64_t)(K - 1) * lookup_pitch() + binding.lookup_capacity;
-        place_dirty = place_dirty || changed;
+        place_dirty = place_dirty || changed || lookup_by_table();      // (the table's lookup rows count from Lp, the layout's)
         return HSW_OK;
     }
     size_t img_cells = none, img_keep = 0, lk_cells = none, lk_keep = 0;
@@ -450,8 +450,17 @@ int Context::upload_place() {
         // columns by pointer table: [jump cells n = breaks + 1][K cum rows of n][per digest], jump 0 at stream cell 0.
         // A jump into image column k of Context c lands break_cum (columns one pitch apart) + what column k really
         // lies from there: col_off - k * pitch, modulo 2^64 (PlaceTable::cum_stride)
-        const size_t n = nb + 1, K = contexts();
-        h.assign(n + K * n + (H ? H : 1), 0);
+        // then, by pointer table too (PlaceTable::lk_row / chip_row): [K lookup rows][K * ncols * 2 chip rows]
+        const size_t n = nb + 1, K = contexts(), ncols = shape.num_advice_columns;
+        const size_t rows0 = n + K * n + (H ? H : 1);
+        h.assign(rows0 + (lookup_by_table() ? K : 0) + (chips_by_table() ? K * ncols * 2 : 0), 0);
+        size_t at = rows0;
+        for (size_t c = 0; c < K && lookup_by_table(); c++) h[at++] = lookup_extra(c);
+        for (size_t c = 0; c < K && chips_by_table(); c++)
+            for (size_t k = 0; k < ncols; k++) {
+                h[at++] = chip_column_cell(c, k, false) - c * ctx_chip_rows();
+                h[at++] = chip_column_cell(c, k, true) - c * ctx_chip_rows();
+            }
         std::vector<uint64_t> col(n, 0);
         for (size_t k = 0; k < nb; k++) {
             h[1 + k] = l.break_cell[k];
@@ -511,15 +520,37 @@ int Context::set_origin(const std::vector<size_t> &sizes, bool rc_inputs, uint64
     return HSW_OK;
 }
 
-int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b_in, void *const *col_ptrs, size_t n_ptrs) {
+int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b_in, const hsw_column_tables *t) {
     const uint64_t K = contexts();
+    const size_t ncols = shape.num_advice_columns;
     hsw_region_binding b = b_in;
+    void *const *col_ptrs = t ? t->d_column_ptrs : nullptr;
+    const size_t n_ptrs = t ? t->n_column_ptrs : 0;
+    const bool lk_tab = t && t->d_lookup_ptrs, chip_tab = t && (t->d_chip_dense_ptrs || t->d_chip_spread_ptrs);
+    auto entries_ok = [](void *const *p, size_t n) {
+        for (size_t i = 0; i < n; i++)
+            if (!p[i] || ((uintptr_t)p[i] & 127u)) return false;
+        return true;
+    };
+    if (t && !col_ptrs) return HSW_ERR_INVALID_ARG;       // (without an image table: hsw_gadget_bind_region)
     if (col_ptrs) {                                       // columns by pointer table: one pointer per column per proof
         if (b.columns_capacity == 0 || b.columns_capacity > ~(size_t)0 / (size_t)K || n_ptrs != (size_t)K * (size_t)b.columns_capacity) return HSW_ERR_INVALID_ARG;
-        for (size_t i = 0; i < n_ptrs; i++)
-            if (!col_ptrs[i] || ((uintptr_t)col_ptrs[i] & 127u)) return HSW_ERR_INVALID_ARG;
+        if (!entries_ok(col_ptrs, n_ptrs)) return HSW_ERR_INVALID_ARG;
         b.d_columns = col_ptrs[0];
         b.context_pitch = 0;
+    }
+    if (t && t->n_lookup_ptrs != (lk_tab ? (size_t)K : 0)) return HSW_ERR_INVALID_ARG;
+    if (lk_tab) {                                         // ... and one per lookup-advice column
+        if (!entries_ok(t->d_lookup_ptrs, (size_t)K)) return HSW_ERR_INVALID_ARG;
+        b.d_lookup = t->d_lookup_ptrs[0];
+        b.lookup_pitch = 0;
+    }
+    if (chip_tab && (!t->d_chip_dense_ptrs || !t->d_chip_spread_ptrs)) return HSW_ERR_INVALID_ARG;   // both families or neither
+    if (t && t->n_chip_ptrs != (chip_tab ? (size_t)K * ncols : 0)) return HSW_ERR_INVALID_ARG;
+    if (chip_tab) {                                       // ... and two per chip column
+        if (!entries_ok(t->d_chip_dense_ptrs, (size_t)K * ncols) || !entries_ok(t->d_chip_spread_ptrs, (size_t)K * ncols)) return HSW_ERR_INVALID_ARG;
+        b.d_chip_dense = t->d_chip_dense_ptrs[0]; b.d_chip_spread = t->d_chip_spread_ptrs[0];
+        b.chip_col_stride = b.chip_context_pitch = 0;
     }
     const void *ptrs[4] = {b.d_columns, b.d_lookup, b.d_chip_dense, b.d_chip_spread};
     // (128 bytes: a column that starts on a line boundary keeps the realigned write-out on whole lines)
@@ -527,10 +558,10 @@ int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_re
         if (!p || ((uintptr_t)p & 127u)) return HSW_ERR_INVALID_ARG;
     // (a block's cells are addressed by 32-bit byte offsets from its first, the gaps of <= 2 column breaks included)
     if (b.column_pitch < layout.max_rows || b.column_pitch > (1ull << 24)) return HSW_ERR_INVALID_ARG;
-    if (b.chip_col_stride < b.chip_rows_capacity) return HSW_ERR_INVALID_ARG;
+    if (!chip_tab && b.chip_col_stride < b.chip_rows_capacity) return HSW_ERR_INVALID_ARG;
     if (K > 1) {
         if (!col_ptrs && (b.columns_capacity > ~0ull / b.column_pitch || b.context_pitch < b.columns_capacity * b.column_pitch)) return HSW_ERR_INVALID_ARG;
-        if (b.lookup_pitch < b.lookup_capacity) return HSW_ERR_INVALID_ARG;
+        if (!lk_tab && b.lookup_pitch < b.lookup_capacity) return HSW_ERR_INVALID_ARG;
         if (b.context_pitch > ~0ull / (K * HSW_CELL_BYTES) || b.lookup_pitch > ~0ull / (K * HSW_CELL_BYTES) ||
             b.chip_context_pitch > ~0ull / (K * HSW_CELL_BYTES))
             return HSW_ERR_INVALID_ARG;
@@ -540,11 +571,16 @@ int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_re
     nl.image_pitch = K > 1 ? b.context_pitch : 0;
     const int rc = plan_layout(sizes, rc_inputs, layout.max_rows, declared, &nl);
     if (rc != HSW_OK) return rc;
-    std::vector<uint64_t> off;
-    if (col_ptrs) {
-        off.resize(n_ptrs);
-        for (size_t i = 0; i < n_ptrs; i++) off[i] = (uint64_t)((uintptr_t)col_ptrs[i] - (uintptr_t)col_ptrs[0]) / HSW_CELL_BYTES;
-    }
+    // (cells from entry 0, modulo 2^64: an entry below entry 0 wraps, and wraps back when the kernels scale by the cell size)
+    auto offsets = [](void *const *p, size_t n) {
+        std::vector<uint64_t> o(n);
+        for (size_t i = 0; i < n; i++) o[i] = (uint64_t)((uintptr_t)p[i] - (uintptr_t)p[0]) / HSW_CELL_BYTES;
+        return o;
+    };
+    std::vector<uint64_t> off, lko, cdo, cso;
+    if (col_ptrs) off = offsets(col_ptrs, n_ptrs);
+    if (lk_tab) lko = offsets(t->d_lookup_ptrs, (size_t)K);
+    if (chip_tab) { cdo = offsets(t->d_chip_dense_ptrs, (size_t)K * ncols); cso = offsets(t->d_chip_spread_ptrs, (size_t)K * ncols); }
     if (nl.columns > b.columns_capacity || lookups_needed(nl) > b.lookup_capacity || ctx_chip_rows() > b.chip_rows_capacity) return HSW_ERR_TOO_LARGE;
     // (the caller ran on a drained engine: nothing still writes the buffers given up here)
     if (!bound) {
@@ -559,6 +595,7 @@ int Context::bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_re
     binding = b;
     by_pointer = col_ptrs != nullptr;
     col_off.swap(off);
+    lk_off.swap(lko); chip_dense_off.swap(cdo); chip_spread_off.swap(cso);
     d_gate = b.d_columns; d_lookup = b.d_lookup; d_chip_dense = b.d_chip_dense; d_chip_spread = b.d_chip_spread;
     chip_col_stride = (size_t)b.chip_col_stride;
     image_columns = b.columns_capacity;
@@ -593,6 +630,7 @@ int Context::unbind(const std::vector<size_t> &sizes, bool rc_inputs) {
     bound = false;
     by_pointer = false;
     col_off.clear();
+    lk_off.clear(); chip_dense_off.clear(); chip_spread_off.clear();
     binding = hsw_region_binding{};
     d_gate = img; d_lookup = lk; d_chip_dense = cd; d_chip_spread = cs;
     chip_col_stride = stride;
@@ -631,6 +669,10 @@ struct Launch {
                 n += 1;
                 tbl = PlaceTable{d_place, d_place + n, d_place + n + c.contexts() * n, n, 0};
                 tbl.cum_stride = n;
+                // the lookup and chip rows after the per-digest shifts (upload_place)
+                const uint64_t *rows = tbl.lk_shift + (c.shared ? l.digest_lookup0.size() ? l.digest_lookup0.size() : 1 : c.init_capacity ? c.init_capacity : 1);
+                if (c.lookup_by_table()) { tbl.lk_row = rows; rows += c.contexts(); }
+                if (c.chips_by_table()) tbl.chip_row = rows;
             }
             period.place = &tbl;
             per = &period;
@@ -658,7 +700,7 @@ struct Launch {
         a.d_blocks = in_blocks + 64 * first_block; a.d_pre_states = in_pre + 8 * first_block; a.n_blocks = n_blocks;
         a.spread_cursor0 = (uint64_t)first_block * c.shape.limb_calls_per_block;
         // (a bound region: the chip rows of the launch's first Context, where the caller keeps that Context's)
-        const size_t row_shift = (size_t)c.chip_cell(a.spread_cursor0 - a.spread_cursor0 % c.shape.num_advice_columns);
+        const size_t row_shift = (size_t)c.chip_launch_cell(a.spread_cursor0 - a.spread_cursor0 % c.shape.num_advice_columns);
         a.d_gate = static_cast<uint8_t *>(c.d_gate) + first_block * (size_t)c.shape.gate_cells_per_block * cb;
         a.d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + row_shift * cb;
         a.d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + row_shift * cb;
@@ -676,7 +718,7 @@ struct Launch {
         // (context images: the run's first block in ITS Context's image; the breaks are that Context's)
         const uint64_t ctx0 = l.period ? r0.block_cell / l.period : 0, local = r0.block_cell - ctx0 * l.period;
         a.d_gate = static_cast<uint8_t *>(c.gate_stream()) + (size_t)((c.by_pointer ? 0 : ctx0 * l.image_cells()) + local) * cb;
-        a.d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)r0.block_lookup * cb;
+        a.d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)(r0.block_lookup + c.lookup_extra(ctx0)) * cb;   // (by table: the Context's own column)
         a.frame_every = fs.n_blocks;
         // between the block streams of two digests: one epilogue, the next prologue -- and the next Context's zero cell
         // when every digest is a Context of its own, and (context images) its caller-owned lookup cells
@@ -876,14 +918,16 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
                     lc = cx * ctx.lookup_pitch() + ctx.layout.digest_lookup0[j];
                     zero_loaded = j != 0 || ctx.layout.origin_zero_loaded;
                 }
+                // (lookup columns by pointer table: the frame kernels address through the Context's offset, positions stay)
+                const uint64_t lx = ctx.lookup_extra(ctx.context_images ? cur_hash_idx + i : ctx.group_m ? (cur_hash_idx + i) / ctx.group_m : 0);
                 r.prologue_cell = d.prologue_cell = gc;      gc += fss[i].prologue_cells;
-                r.prologue_lookup = d.prologue_lookup = lc;  lc += fss[i].prologue_lookups;
+                r.prologue_lookup = lc; d.prologue_lookup = lc + lx;  lc += fss[i].prologue_lookups;
                 d.zero_cell = ~0ull;
                 if (!zero_loaded || own_zero) { d.zero_cell = gc++; zero_loaded = true; }   // compression.rs:34 of the first block of a Context
                 r.block_cell = gc;                           gc += (uint64_t)d.n_blocks * G;
                 r.block_lookup = lc;                         lc += (uint64_t)d.n_blocks * LK;
                 r.epilogue_cell = d.epilogue_cell = gc;      gc += fss[i].epilogue_cells;
-                r.epilogue_lookup = d.epilogue_lookup = lc;  lc += fss[i].epilogue_lookups;
+                r.epilogue_lookup = lc; d.epilogue_lookup = lc + lx;  lc += fss[i].epilogue_lookups;
                 r.end_cell = gc;
                 ob += d.n_blocks;
             }
@@ -1214,7 +1258,22 @@ int hsw_gadget_bind_columns(hsw_gadget *g, const hsw_region_binding *b, void *co
     if (c.shape.num_bits_lookup != 8) return HSW_ERR_UNSUPPORTED;
     int rc = hsw_engine_synchronize(c.engine);
     if (rc != HSW_OK) return rc;
-    rc = c.bind(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, *b, d_column_ptrs, n_ptrs);
+    hsw_column_tables t{};
+    t.d_column_ptrs = d_column_ptrs; t.n_column_ptrs = n_ptrs;
+    rc = c.bind(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, *b, &t);
+    if (rc == HSW_OK) hsw::drop_region_tape_positions(g->tape);
+    return rc;
+} HSW_NO_UNWIND
+
+int hsw_gadget_bind_column_tables(hsw_gadget *g, const hsw_region_binding *b, const hsw_column_tables *t) try {
+    if (!g || !b || !t || !t->d_column_ptrs) return HSW_ERR_INVALID_ARG;
+    hsw::Context &c = *g->ctx;
+    if (!c.whole || !c.layout.max_rows) return HSW_ERR_UNSUPPORTED;
+    if (g->cfg.cur_hash_idx != 0 || c.blocks_done != 0 || c.gate_cursor != 0) return HSW_ERR_INVALID_ARG;   // a fresh or reset gadget
+    if (c.shape.num_bits_lookup != 8) return HSW_ERR_UNSUPPORTED;        // (the table-path kernels, as hsw_gadget_bind_columns)
+    int rc = hsw_engine_synchronize(c.engine);
+    if (rc != HSW_OK) return rc;
+    rc = c.bind(g->cfg.max_variable_byte_sizes, g->cfg.is_input_range_check, *b, t);
     if (rc == HSW_OK) hsw::drop_region_tape_positions(g->tape);
     return rc;
 } HSW_NO_UNWIND
@@ -1383,30 +1442,46 @@ int hsw_gadget_download_region(hsw_gadget *g, const hsw_region_host *dst) try {
         const size_t cells = c.whole ? (size_t)c.gate_cursor : c.blocks_done * (size_t)c.shape.gate_cells_per_block;
         copy(dst->gate, c.d_gate, 0, cells);
     }
+    // (lookup columns by pointer table: the host buffer is an unbound gadget's, Context cx's device cells lookup_extra(cx) further)
+    auto copy_lookup = [&](uint64_t cx, uint64_t cell0, uint64_t cells) {
+        if (he == hipSuccess && cells)
+            he = hipMemcpyAsync(static_cast<uint8_t *>(dst->lookup) + (size_t)cell0 * cb,
+                                static_cast<const uint8_t *>(c.d_lookup) + (size_t)(cell0 + c.lookup_extra(cx)) * cb,
+                                (size_t)cells * cb, hipMemcpyDeviceToHost, stream);
+    };
     if (dst->lookup && c.d_lookup && c.context_images) {
         const uint64_t Lp = c.lookup_pitch();              // Context h: its own entries after the caller's queued cells
         for (uint64_t h = 0; h < g->cfg.cur_hash_idx; h++)
-            copy(dst->lookup, c.d_lookup, (size_t)(h * Lp + c.layout.origin_lookups), (size_t)c.ctx_own_lookups);
+            copy_lookup(h, h * Lp + c.layout.origin_lookups, c.ctx_own_lookups);
     } else if (dst->lookup && c.d_lookup && c.shared && !c.layout.digest_lookup0.empty()) {
         const size_t M = c.group_m ? c.group_m : c.layout.digest_entry0.size();
         const uint64_t own = c.group_m ? c.ctx_own_lookups : c.own_lookup_capacity, Lp = c.group_m ? c.lookup_pitch() : 0;
         for (size_t d = 0; d < g->cfg.cur_hash_idx; d++) {     // every digest's own entries; the interludes' are the caller's
             const size_t h = d % M, cx = d / M;                 // (a Context group: digest h of Context cx, in its own lookup column)
             const uint64_t end = h + 1 < c.layout.digest_entry0.size() ? c.layout.digest_entry0[h + 1] : own;
-            copy(dst->lookup, c.d_lookup, (size_t)(cx * Lp + c.layout.digest_lookup0[h]), (size_t)(end - c.layout.digest_entry0[h]));
+            copy_lookup(cx, cx * Lp + c.layout.digest_lookup0[h], end - c.layout.digest_entry0[h]);
         }
     } else if (dst->lookup && c.d_lookup) {
         copy(dst->lookup, c.d_lookup, (size_t)c.layout.origin_lookups, (size_t)(c.lookup_cursor - c.layout.origin_lookups));
     }
     const uint32_t ncols = c.shape.num_advice_columns;
     // the used rows of every chip column -- of every Context begun, where each has chip rows of its own (a bound region)
-    const uint64_t per = c.chip_ctx_extra() ? c.ctx_limb_calls() : c.num_limb_sum ? c.num_limb_sum : 1;
+    // (chip columns by pointer table: the host buffers are an unbound gadget's -- ncols columns of all Contexts' rows,
+    //  Context cx's after Context cx-1's -- and every column of every Context is one copy from its own allocation)
+    const uint64_t per = c.chip_rows_per_context() ? c.ctx_limb_calls() : c.num_limb_sum ? c.num_limb_sum : 1;
+    const size_t host_stride = c.chips_by_table() ? (size_t)hsw_chip_rows(&c.shape, 0, c.capacity_blocks) : c.chip_col_stride;
+    auto copy_chip = [&](void *h, const void *d, size_t hcell, size_t dcell, size_t cells) {
+        if (h && he == hipSuccess && cells)
+            he = hipMemcpyAsync(static_cast<uint8_t *>(h) + hcell * cb, static_cast<const uint8_t *>(d) + dcell * cb, cells * cb,
+                                hipMemcpyDeviceToHost, stream);
+    };
     for (uint64_t n0 = 0; n0 < c.num_limb_sum; n0 += per) {
-        const uint64_t n1 = n0 + per < c.num_limb_sum ? n0 + per : c.num_limb_sum;
-        const size_t rows = (size_t)((n1 - n0 + ncols - 1) / ncols), row0 = (size_t)c.chip_cell(n0);
+        const uint64_t n1 = n0 + per < c.num_limb_sum ? n0 + per : c.num_limb_sum, cx = n0 / per;
+        const size_t rows = (size_t)((n1 - n0 + ncols - 1) / ncols);
         for (uint32_t k = 0; k < ncols; k++) {
-            if (dst->chip_dense) copy(dst->chip_dense, c.d_chip_dense, k * c.chip_col_stride + row0, rows);
-            if (dst->chip_spread) copy(dst->chip_spread, c.d_chip_spread, k * c.chip_col_stride + row0, rows);
+            const size_t hcell = c.chips_by_table() ? k * host_stride + (size_t)(n0 / ncols) : (size_t)c.chip_column_cell(cx, k, false);
+            copy_chip(dst->chip_dense, c.d_chip_dense, hcell, (size_t)c.chip_column_cell(cx, k, false), rows);
+            copy_chip(dst->chip_spread, c.d_chip_spread, hcell, (size_t)c.chip_column_cell(cx, k, true), rows);
         }
     }
     if (he == hipSuccess) he = hipStreamSynchronize(stream);
@@ -1579,7 +1654,9 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
                 d.num_round = (uint32_t)rk.num_round; d.precomputed_round = (uint32_t)(rk.num_round - rk.target_round);
                 d.is_input_range_check = g->cfg.is_input_range_check ? 1u : 0u;
                 d.prologue_cell = rk.prologue_cell; d.epilogue_cell = rk.epilogue_cell;
-                d.prologue_lookup = rk.prologue_lookup; d.epilogue_lookup = rk.epilogue_lookup;
+                const size_t dk = b.first_digest + run.first + k * run.step;
+                const uint64_t lx = c.lookup_extra(c.context_images ? dk : c.group_m ? dk / c.group_m : 0);
+                d.prologue_lookup = rk.prologue_lookup + lx; d.epilogue_lookup = rk.epilogue_lookup + lx;
                 d.zero_cell = rk.block_cell == rk.prologue_cell + fs.prologue_cells + 1 ? rk.block_cell - 1 : ~0ull;
             }
             rc = hsw_verify_frames_impl(c.engine, descs.data(), descs.size(), L.in_blocks, L.in_pre, c.d_next_states, c.gate_stream(),
@@ -1613,12 +1690,12 @@ int hsw_gadget_context_region(const hsw_gadget *g, size_t h, hsw_context_region 
         out->d_image = static_cast<uint8_t *>(c.d_gate) + (size_t)(h * C) * cb;   // linear: the Context's stream
     }
     out->lookup_cells = c.ctx_lookups();
-    out->d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)(h * c.lookup_pitch()) * cb;
+    out->d_lookup = static_cast<uint8_t *>(c.d_lookup) + (size_t)c.lookup_cell(h) * cb;   // (by pointer table: proof h's own column)
     out->chip_rows = nb * c.shape.limb_calls_per_block / ncols;
     out->chip_col_stride = c.chip_col_stride;
-    const size_t chip_row0 = (size_t)c.chip_cell(h * nb * c.shape.limb_calls_per_block);   // (a whole number of rows per Context)
-    out->d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + chip_row0 * cb;
-    out->d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + chip_row0 * cb;
+    // (a whole number of rows per Context; by pointer table: proof h's chip column 0 of each family)
+    out->d_chip_dense = static_cast<uint8_t *>(c.d_chip_dense) + (size_t)c.chip_column_cell(h, 0, false) * cb;
+    out->d_chip_spread = static_cast<uint8_t *>(c.d_chip_spread) + (size_t)c.chip_column_cell(h, 0, true) * cb;
     out->origin_column = c.layout.origin_column;
     out->origin_row = c.layout.origin_row;
     out->origin_lookups = c.layout.origin_lookups;

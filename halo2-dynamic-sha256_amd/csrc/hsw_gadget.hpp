@@ -162,26 +162,49 @@ class Context {
     uint64_t column_cell(uint64_t c, uint64_t k) const {
         return by_pointer ? col_off[(size_t)(c * binding.columns_capacity + k)] : c * layout.image_cells() + k * layout.column_pitch();
     }
-    uint64_t lookup_pitch() const { return bound && contexts() > 1 ? binding.lookup_pitch : ctx_lookups(); }
+    // hsw_gadget_bind_column_tables: the lookup-advice column and / or the chip columns one allocation each as well (an
+    // empty vector: that family keeps the pitch model).  lk_off[c] = cells from d_lookup (proof 0's column) to row 0
+    // of proof c's; chip_dense_off / chip_spread_off[c * ncols + k] = cells from d_chip_dense / d_chip_spread (proof
+    // 0's chip column 0) to row 0 of chip column k of proof c -- all modulo 2^64.  Positions (hsw_hash_result's
+    // lookup cells, the cursors) stay an unbound gadget's: lookup_pitch() is Lp, and lookup_extra(c) is what the
+    // addresses of Context c lie further (PlaceTable::lk_row; folded into the frames' lookup cells and Launch::run)
+    std::vector<uint64_t> lk_off, chip_dense_off, chip_spread_off;
+    bool lookup_by_table() const { return !lk_off.empty(); }
+    bool chips_by_table() const { return !chip_dense_off.empty(); }
+    uint64_t lookup_pitch() const { return bound && contexts() > 1 && !lookup_by_table() ? binding.lookup_pitch : ctx_lookups(); }
+    uint64_t lookup_extra(uint64_t c) const { return lookup_by_table() ? lk_off[(size_t)c] - c * ctx_lookups() : 0; }
+    // cells from d_lookup to row 0 of Context c's lookup column
+    uint64_t lookup_cell(uint64_t c) const { return c * lookup_pitch() + lookup_extra(c); }
     size_t blocks_per_context() const { return context_images ? capacity_blocks / init_capacity : group_m ? ctx_blocks : capacity_blocks; }
     uint64_t ctx_limb_calls() const { return (uint64_t)blocks_per_context() * shape.limb_calls_per_block; }
     uint64_t ctx_chip_rows() const { return (ctx_limb_calls() + shape.num_advice_columns - 1) / shape.num_advice_columns; }
     // cells from where consecutive rows would put a Context's chip rows to where they lie, per Context (modulo 2^64;
     // ExpandParams::chip_ctx_extra)
-    uint64_t chip_ctx_extra() const { return bound && contexts() > 1 ? binding.chip_context_pitch - ctx_chip_rows() : 0; }
-    // chip cell of limb call n (counted from the pass's first), from d_chip_dense / d_chip_spread
+    uint64_t chip_ctx_extra() const { return bound && contexts() > 1 && !chips_by_table() ? binding.chip_context_pitch - ctx_chip_rows() : 0; }
+    // chip cell of limb call n (counted from the pass's first), from d_chip_dense / d_chip_spread: the pitch model
     uint64_t chip_cell(uint64_t n) const {
         const uint64_t ncols = shape.num_advice_columns, extra = chip_ctx_extra();
         return (n % ncols) * chip_col_stride + n / ncols + (extra ? n / ctx_limb_calls() * extra : 0);
     }
+    // what a launch whose first limb call is n (a multiple of ncols) adds to d_chip_dense / d_chip_spread: the place
+    // of n's row in column 0 -- by table, the columns' absolute row, which the Context's chip_row entries count from
+    uint64_t chip_launch_cell(uint64_t n) const { return chips_by_table() ? n / shape.num_advice_columns : chip_cell(n); }
+    // cells from d_chip_dense (spread: d_chip_spread) to the first chip row of Context c in chip column k
+    uint64_t chip_column_cell(uint64_t c, uint64_t k, bool spread) const {
+        if (chips_by_table()) return (spread ? chip_spread_off : chip_dense_off)[(size_t)(c * shape.num_advice_columns + k)];
+        return k * chip_col_stride + c * (ctx_chip_rows() + chip_ctx_extra());
+    }
+    // the Contexts whose chip rows are counted apart (download_region): one run of rows per column otherwise
+    bool chip_rows_per_context() const { return chip_ctx_extra() != 0 || (chips_by_table() && contexts() > 1); }
     // d_lookup cells ONE Context needs with layout l (Lp; one Context: the whole column)
     uint64_t lookups_needed(const Layout &l) const {
         return context_images ? l.origin_lookups + ctx_own_lookups : shared && l.max_rows ? l.lookups_end : l.origin_lookups + own_lookup_capacity;
     }
     // the library's own zeroed buffers again, sized for the layout without pitches (sizes / rc_inputs: the gadget's)
     int unbind(const std::vector<size_t> &sizes, bool rc_inputs);
-    // ptrs: NULL = hsw_gadget_bind_region; else hsw_gadget_bind_columns' table of contexts() * b.columns_capacity pointers
-    int bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b, void *const *ptrs = nullptr, size_t n_ptrs = 0);
+    // t: NULL = hsw_gadget_bind_region; else the pointer tables of hsw_gadget_bind_columns (the image's only) or
+    // hsw_gadget_bind_column_tables.  Validated in full before anything changes
+    int bind(const std::vector<size_t> &sizes, bool rc_inputs, const hsw_region_binding &b, const hsw_column_tables *t = nullptr);
     bool zero_loaded = false;        // Context.zero_cell (first load_zero: compression.rs:34 of the first block)
     uint64_t gate_cursor = 0, gate_capacity = 0;       // cells
     void *d_lookup = nullptr;

@@ -124,6 +124,16 @@ struct PlaceTable {
     // instantiations of the table-path kernels (template parameter WIDE) are launched for such a table.
     // ctx0: the Context of the launch's block 0 (block kernels; the frame kernels take the Context from the digest)
     uint64_t cum_stride, ctx0;
+    // Lookup and chip columns by pointer table (hsw_gadget_bind_column_tables; read by the wide instantiations only,
+    // null = the pitch model: ExpandParams / VerifyParams::frame_lookups, chip_col_stride and chip_ctx_extra).  Rows
+    // per Context, in cells modulo 2^64 like cum:
+    //   lk_row[c]    what Context c's lookup column lies further from the launch's `lookup` than c lookup columns of
+    //                an unbound gadget (Lp cells each) would put it -- the launch's frame_lookups steps Lp
+    //   chip_row[(c * ncols + k) * 2 + f]   f = 0 dense, 1 spread: chip column k of Context c, from the launch's
+    //                `chip_dense` / `chip_spread` taken as the columns' absolute row cursor0 / ncols: limb call N
+    //                (absolute) sits chip_row + N / ncols - cursor0 / ncols cells from that pointer
+    // A launch's first block need not be its Context's first: c counts from the pass's first Context (ctx0 + ...).
+    const uint64_t *lk_row, *chip_row;
 };
 
 struct FrameDesc;   // hsw_frame.hpp

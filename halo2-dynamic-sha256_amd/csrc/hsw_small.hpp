@@ -149,6 +149,17 @@ DEV void scatter_chip(const EM &em, const ExpandParams &p, u64 block_first_limb,
         const size_t cell = (size_t)(x - row * ncols) * p.chip_col_stride + rbase + row;
         char *cd = reinterpret_cast<char *>(p.chip_dense) + cell * CB;
         char *cs = reinterpret_cast<char *>(p.chip_spread) + cell * CB;
+        if constexpr (EM::WIDE) {
+            // chip columns by pointer table: the column differs from lane to lane, so each lane gathers its column's
+            // two offsets (16 adjacent bytes of a row of 2 * ncols words, L2-resident; the loads do not depend on
+            // the staged limbs and are in flight during the conversions below).  A pass per column would keep
+            // the offsets scalar but leave 1 / ncols of the lanes active in ncols times as many store instructions.
+            if (em.chip_row) {
+                const uint64_t *o = em.chip_row + 2u * (x - row * ncols);
+                cd = reinterpret_cast<char *>(p.chip_dense) + (size_t)(o[0] + rbase + row) * CB;
+                cs = reinterpret_cast<char *>(p.chip_spread) + (size_t)(o[1] + rbase + row) * CB;
+            }
+        }
         if constexpr (EM::COMPACT) {
             store8(cd, 0, limb);
             store8(cs, 0, spread16(limb));
@@ -275,6 +286,8 @@ DEV void small_role(const ExpandParams &p, const u32 *bw, const u32 (&ps)[8], si
     if constexpr (TABLE)
         if (!EM::WIDE || !tbl->ctx_blocks)     // (a pointer table's Contexts: frame_lookups steps a Context, no per-digest shift)
         lk_blk += (size_t)(tbl_uniform(tbl->lk_shift, (u64)(blk / p.frame_every)) - tbl_uniform(tbl->lk_shift, 0));
+    if constexpr (TABLE)
+        wide_context_rows(em, *tbl, p.ncols, tbl->ctx_blocks ? (u32)blk / (u32)p.frame_every : 0u, lk_blk);
     em.write_gate = (p.flags & HSW_K_SKIP_GATE) == 0u;
     const u64 blk_limb0 = p.cursor0 + (u64)blk * (u64)LY::LIMB_CALLS;
 

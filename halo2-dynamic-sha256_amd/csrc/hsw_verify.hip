@@ -144,7 +144,7 @@ DEV bool row_holds(const Cell x[4]) {
 // caller's entries queued before its digest.
 template <bool MONT>
 __global__ __launch_bounds__(256) void hsw_verify_kernel(VerifyParams p) {
-    constexpr bool TABLE = false;
+    constexpr bool TABLE = false, WIDE = false;
     const PlaceTable *tbl = nullptr;
     (void)tbl;
 #include "hsw_verify_block_body.inc"
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void hsw_verify_kernel(VerifyParams p) {
 // shared contexts (HSW_GADGET_SHARED_CONTEXT): the same checks, placed by a jump table
 template <bool MONT>
 __global__ __launch_bounds__(256) void hsw_verify_table_kernel(VerifyParams p, PlaceTable t) {
-    constexpr bool TABLE = true;
+    constexpr bool TABLE = true, WIDE = false;
     const PlaceTable *tbl = &t;
 #include "hsw_verify_block_body.inc"
 }

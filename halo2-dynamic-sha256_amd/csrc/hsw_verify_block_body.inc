@@ -1,5 +1,6 @@
 // hsw_verify_block_body.inc -- the body of hsw_verify_kernel and of hsw_verify_table_kernel (hsw_verify.hip), included in both.  Expects in scope:
-// MONT, TABLE (shared contexts: cells placed by the jump table), p, tbl (PlaceTable *, null without TABLE).
+// MONT, TABLE (shared contexts: cells placed by the jump table), WIDE (columns by pointer table), p, tbl (PlaceTable *, null
+// without TABLE).
 // (A textual body rather than a __device__ function: through a function the existing kernels compiled to different code.)
     const u64 blk = blockIdx.x / p.slices;
     const u32 tid = (blockIdx.x % p.slices) * blockDim.x + threadIdx.x, nt = p.slices * blockDim.x;
@@ -142,7 +143,10 @@
             const bool act = n < p.limb_calls;
             const u32 nn = act ? n : 0u;
             const u64 N = p.cursor0 + in_blk * (u64)p.limb_calls + nn;
-            const u64 at = (N % p.ncols) * (u64)p.chip_col_stride + (N / p.ncols - row0);
+            u64 at = (N % p.ncols) * (u64)p.chip_col_stride + (N / p.ncols - row0);
+            if constexpr (WIDE)     // chip columns by pointer table: the column's own dense / spread offset (PlaceTable::chip_row)
+                if (tbl->chip_row)
+                    at = tbl->chip_row[((tbl->ctx0 + (tbl->ctx_blocks ? dg : 0)) * p.ncols + N % p.ncols) * 2u + half] + (N / p.ncols - p.cursor0 / p.ncols);
             const Cell rv = load_cell(half ? csp : cd, at);
             const int64_t id = p.chip[2 * nn + half];
             bool tied;
@@ -169,6 +173,8 @@
             u64 at = p.lookup_cell0 + blk * (u64)p.lookup_cells + dg * p.frame_lookups + j;
             if constexpr (TABLE)
                 if (!tbl->ctx_blocks) at += tbl->lk_shift[dg] - tbl->lk_shift[0];   // (a group's launch: one digest index, its shift is in p.lookup)
+            if constexpr (WIDE)     // lookup columns by pointer table: the Context's own offset (PlaceTable::lk_row)
+                if (tbl->lk_row && tbl->ctx_blocks) at += tbl->lk_row[tbl->ctx0 + dg] - tbl->lk_row[tbl->ctx0];
             const Cell rv = load_cell(lk, at);
             Cell v = rv;
             bool enc = true;

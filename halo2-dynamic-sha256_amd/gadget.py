@@ -146,7 +146,7 @@ class Sha256DynamicConfig:
         if columns is None:
             self._ok(self.lib.hsw_gadget_bind_region(self.h, None))
             self._bound = None
-            self._column_ptrs = None
+            self._column_ptrs = self._lookup_ptrs = self._chip_ptrs = None
             return
 
         def ptr(x):
@@ -155,23 +155,50 @@ class Sha256DynamicConfig:
                             ptr(chip_dense), ptr(chip_spread), chip_col_stride, chip_rows_capacity, chip_context_pitch)
         self._ok(self.lib.hsw_gadget_bind_region(self.h, C.byref(b)))
         self._bound = (columns, lookup, chip_dense, chip_spread)      # keeps tensors alive while they are bound
-        self._column_ptrs = None
+        self._column_ptrs = self._lookup_ptrs = self._chip_ptrs = None
 
     def bind_columns(self, column_ptrs, column_pitch, columns_capacity, lookup=None, lookup_capacity=0, chip_dense=None,
-                     chip_spread=None, chip_col_stride=0, chip_rows_capacity=0, lookup_pitch=0, chip_context_pitch=0):
+                     chip_spread=None, chip_col_stride=0, chip_rows_capacity=0, lookup_pitch=0, chip_context_pitch=0,
+                     lookup_ptrs=None, chip_dense_ptrs=None, chip_spread_ptrs=None):
         """hsw_gadget_bind_columns: like bind_region, but every FlexGate image column is an allocation of its own.
         column_ptrs[c * columns_capacity + k]: torch tensor or raw device pointer of row 0 of image column k of proof c
         (K * columns_capacity entries; the caller keeps them alive); column_pitch: cells each column holds.  Lookup and
-        chip areas as in bind_region.  bind_region(None) unbinds."""
+        chip areas as in bind_region -- or, with lookup_ptrs= (K entries: proof c's lookup-advice column) and / or
+        chip_dense_ptrs= and chip_spread_ptrs= (K * ncols entries each: [c * ncols + k] = chip column k of proof c), by
+        pointer table too (hsw_gadget_bind_column_tables; tensors or integers like column_ptrs, lookup_capacity /
+        chip_rows_capacity = what each allocation holds).  bind_region(None) unbinds."""
         def ptr(x):
             return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x or 0)
-        ptrs = [ptr(x) for x in column_ptrs]
-        arr = (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+
+        def table(xs):
+            v = [ptr(x) for x in xs]
+            return v, (C.c_void_p * max(len(v), 1))(*v)
+        ptrs, arr = table(column_ptrs)
         b = N.RegionBinding(None, column_pitch, columns_capacity, 0, ptr(lookup), lookup_capacity, lookup_pitch,
                             ptr(chip_dense), ptr(chip_spread), chip_col_stride, chip_rows_capacity, chip_context_pitch)
-        self._ok(self.lib.hsw_gadget_bind_columns(self.h, C.byref(b), arr, len(ptrs)))
-        self._bound = (list(column_ptrs), lookup, chip_dense, chip_spread)
+        lks = cds = css = None
+        if lookup_ptrs is None and chip_dense_ptrs is None and chip_spread_ptrs is None:
+            self._ok(self.lib.hsw_gadget_bind_columns(self.h, C.byref(b), arr, len(ptrs)))
+        else:
+            t = N.ColumnTables(C.cast(arr, C.POINTER(C.c_void_p)), len(ptrs), None, 0, None, None, 0)
+            keep = [arr]
+            if lookup_ptrs is not None:
+                lks, a = table(lookup_ptrs)
+                t.d_lookup_ptrs, t.n_lookup_ptrs = C.cast(a, C.POINTER(C.c_void_p)), len(lks)
+                keep.append(a)
+            if chip_dense_ptrs is not None:
+                cds, a = table(chip_dense_ptrs)
+                t.d_chip_dense_ptrs, t.n_chip_ptrs = C.cast(a, C.POINTER(C.c_void_p)), len(cds)
+                keep.append(a)
+            if chip_spread_ptrs is not None:
+                css, a = table(chip_spread_ptrs)
+                t.d_chip_spread_ptrs, t.n_chip_ptrs = C.cast(a, C.POINTER(C.c_void_p)), max(len(css), int(t.n_chip_ptrs))
+                keep.append(a)
+            self._ok(self.lib.hsw_gadget_bind_column_tables(self.h, C.byref(b), C.byref(t)))
+        self._bound = (list(column_ptrs), lookup, chip_dense, chip_spread, lookup_ptrs, chip_dense_ptrs, chip_spread_ptrs)
         self._column_ptrs = ptrs
+        self._lookup_ptrs = lks
+        self._chip_ptrs = (cds, css) if cds is not None and css is not None else None
 
     def _unbound_only(self, what):
         """The numpy conveniences size their host buffers for library-owned geometry; a bound gadget's host layout
@@ -376,11 +403,13 @@ class Sha256DynamicConfig:
             return cp[c * cap + j] if cp else b.d_columns + (c * int(b.context_pitch) + j * int(b.column_pitch)) * 32
         gate = np.stack([np.stack([grab(column(c, j), mr) for j in range(cols)]) for c in range(k)])
         lp = int(self.context_region(0).lookup_cells) if multi else int(v.lookup_cells)
-        lookup = np.concatenate([grab(b.d_lookup + c * int(b.lookup_pitch) * 32, lp) for c in range(k)])
+        lks, chips = getattr(self, "_lookup_ptrs", None), getattr(self, "_chip_ptrs", None)   # by pointer table: the caller's own pointers
+        lookup = np.concatenate([grab(lks[c] if lks else b.d_lookup + c * int(b.lookup_pitch) * 32, lp) for c in range(k)])
         per = rows // k if multi else rows             # chip rows of one proof (a whole number of rows each)
 
-        def chip(base):
-            return np.stack([np.concatenate([grab(base + (c * int(b.chip_context_pitch) + j * int(b.chip_col_stride)) * 32, per)
+        def chip(base, tab):
+            return np.stack([np.concatenate([grab(tab[c * ncols + j] if tab else
+                                                  base + (c * int(b.chip_context_pitch) + j * int(b.chip_col_stride)) * 32, per)
                                              for c in range(k)]) for j in range(ncols)])
-        return dict(gate=gate if multi else gate[0], dense=chip(b.d_chip_dense), spread=chip(b.d_chip_spread), rows=rows,
-                    lookup=lookup)
+        return dict(gate=gate if multi else gate[0], dense=chip(b.d_chip_dense, chips and chips[0]),
+                    spread=chip(b.d_chip_spread, chips and chips[1]), rows=rows, lookup=lookup)

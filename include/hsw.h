@@ -48,6 +48,7 @@ extern "C" {
 #endif
 
 #define HSW_ABI_VERSION 3   /* 3: hsw_gadget_view grew the origin fields; hsw_gadget_set_origin */
+#define HSW_ABI_MINOR 1     /* additions that leave every existing entry point as it was: 1: hsw_gadget_bind_column_tables */
 
 /* ---- status codes ---- */
 #define HSW_OK                 0
@@ -752,6 +753,42 @@ int hsw_gadget_region_binding(const hsw_gadget *g, hsw_region_binding *out);
  * hsw_last_launch reports such a gadget's expansion launches with bit 2 of `split` set (split = 4 or 6): the wide
  * instantiations hsw_expand_table_kernel<.., true> / hsw_small_table_kernel<.., true>. */
 int hsw_gadget_bind_columns(hsw_gadget *g, const hsw_region_binding *b, void *const *d_column_ptrs, size_t n_ptrs);
+/* Like hsw_gadget_bind_columns, with the lookup-advice column and the chip columns by pointer table too: a prover
+ * whose allocator hands out EVERY advice column one at a time (K lookup columns, 2 x K x ncols chip columns, ncols =
+ * num_advice_columns) in no address order.  All tables are host arrays, copied by the call:
+ *   d_column_ptrs, n_column_ptrs   K * b->columns_capacity, as hsw_gadget_bind_columns (required: without an image
+ *                                  table this is hsw_gadget_bind_region)
+ *   d_lookup_ptrs, n_lookup_ptrs   K: [c] = row 0 of proof c's lookup-advice column, an allocation of
+ *                                  b->lookup_capacity cells.  NULL / 0: the pitch model of b
+ *   d_chip_dense_ptrs,             K * ncols each: [c * ncols + k] = row 0 of chip column k of proof c, an allocation
+ *   d_chip_spread_ptrs,            of b->chip_rows_capacity rows.  Both families or neither; NULL / 0: the pitch
+ *   n_chip_ptrs                    model of b
+ * The two families are independent: lookup pointers with pitch-model chips, or the other way round.  Where a table
+ * is given the matching fields of b are ignored: d_lookup and lookup_pitch; d_chip_dense, d_chip_spread,
+ * chip_col_stride and chip_context_pitch.  Gadget kinds, "fresh or reset gadget only", ownership, lifetime (the
+ * binding survives hsw_gadget_reset and every layout call that still fits) and every refusal are those of
+ * hsw_gadget_bind_columns; hsw_gadget_bind_region(g, NULL) unbinds.  Caller memory is never freed, grown, zeroed or
+ * filled; unassigned cells keep the caller's content.
+ * HSW_ERR_INVALID_ARG: t or the image table missing, a table of the wrong size, one chip family without the other, a
+ * null table entry or one not 128-byte aligned; HSW_ERR_TOO_LARGE: lookup_capacity below Lp, chip_rows_capacity below
+ * one proof's chip rows, columns_capacity below the layout's columns.  The whole call is validated before anything
+ * changes: a failing call leaves the previous binding or the library's buffers in place.
+ * Positions are unchanged (hsw_gadget_cell_position, hsw_gadget_result_cells, hsw_hash_result: binding changes
+ * addresses, never positions).  hsw_gadget_streams reports proof 0's lookup pointer and chip column-0 pointers and
+ * hsw_gadget_context_region(g, c) proof c's; hsw_gadget_region_binding reports proof 0's pointers with lookup_pitch,
+ * respectively chip_col_stride and chip_context_pitch, = 0 for a family bound by table -- the further columns are
+ * the caller's table's, no pitch describes them (the convention of context_pitch = 0).  hsw_gadget_verify reads
+ * through the tables.  hsw_gadget_download_region lays its host `lookup`, `chip_dense` and `chip_spread` buffers out
+ * as an UNBOUND gadget's (like `gate`): K lookup columns of Lp cells back to back, ncols chip columns of K x (one
+ * proof's rows) each, proof c's rows after proof c-1's; used rows only, everything else in the host buffers is left
+ * untouched. */
+typedef struct hsw_column_tables {
+    void *const *d_column_ptrs;      size_t n_column_ptrs;
+    void *const *d_lookup_ptrs;      size_t n_lookup_ptrs;
+    void *const *d_chip_dense_ptrs;
+    void *const *d_chip_spread_ptrs; size_t n_chip_ptrs;
+} hsw_column_tables;
+int hsw_gadget_bind_column_tables(hsw_gadget *g, const hsw_region_binding *b, const hsw_column_tables *t);
 /* Start the next synthesis pass with the same buffers and layout: every cursor back to
  * its initial value (cur_hash_idx, num_limb_sum, the stream cursors, the Context's zero
  * cell).  What the reference's harnesses do by cloning the config per synthesis

@@ -362,6 +362,18 @@ pub struct hsw_region_binding {
     pub chip_context_pitch: u64,
 }
 
+/// hsw_column_tables: host arrays of device pointers, one per column per proof (hsw_gadget_bind_column_tables).
+#[repr(C)]
+pub struct hsw_column_tables {
+    pub d_column_ptrs: *const *mut c_void,
+    pub n_column_ptrs: usize,
+    pub d_lookup_ptrs: *const *mut c_void,
+    pub n_lookup_ptrs: usize,
+    pub d_chip_dense_ptrs: *const *mut c_void,
+    pub d_chip_spread_ptrs: *const *mut c_void,
+    pub n_chip_ptrs: usize,
+}
+
 extern "C" {
     pub fn hsw_abi_version() -> u32;
     pub fn hsw_strerror(status: c_int) -> *const c_char;
@@ -461,6 +473,12 @@ extern "C" {
         b: *const hsw_region_binding,
         d_column_ptrs: *const *mut c_void,
         n_ptrs: usize,
+    ) -> c_int;
+    /// The lookup-advice and chip columns by pointer table too: every advice column an allocation of its own.
+    pub fn hsw_gadget_bind_column_tables(
+        g: *mut hsw_gadget,
+        b: *const hsw_region_binding,
+        t: *const hsw_column_tables,
     ) -> c_int;
     pub fn hsw_frame_query(shape: *const hsw_shape, max_variable_byte_size: usize, is_input_range_check: c_int,
                            out: *mut hsw_frame_shape) -> c_int;

@@ -7,9 +7,11 @@ tools/bound_region_rate.py: all gadgets in the SAME process, their timed calls a
   bound     (b) hsw_gadget_bind_region to one plain slab per proof (pitches)
   carved    (c) K x 9 columns by pointer table, carved from one plain allocation in shuffled order (fixed seed)
   separate  (d) the same columns as K x 9 separate allocations, wherever the allocator puts them
-Lookup and chip columns keep the pitch model everywhere (5 polynomials per proof in one allocation).
-Writes profiles/bound_columns_rate.json -- (c)/(a), (d)/(a), (c)/(b) -- and prints the same JSON line.
-usage: bound_columns_rate.py [--only=owned|bound|carved|separate] [K]   (default K = 256)"""
+  tables    (e) every advice column a separate allocation: the K x 9 image columns AND, by pointer table too
+                (hsw_gadget_bind_column_tables), the K lookup columns and the K x 2 x 2 chip columns
+Lookup and chip columns keep the pitch model in (b)-(d) (5 polynomials per proof in one allocation).
+Writes profiles/bound_columns_rate.json -- (c)/(a), (d)/(a), (c)/(b), (e)/(a) -- and prints the same JSON line.
+usage: bound_columns_rate.py [--only=owned|bound|carved|separate|tables] [K]   (default K = 256)"""
 import ctypes as C
 import hashlib
 import importlib
@@ -34,7 +36,7 @@ MAX_ROWS, N17, POLYS, COLS = (1 << 17) - 9, 1 << 17, 14, 9
 def main():
     assert torch.cuda.is_available(), "no HIP device"
     only = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--only=")]
-    names = ("owned", "bound", "carved", "separate")
+    names = ("owned", "bound", "carved", "separate", "tables")
     layouts = tuple(only) if only else names
     assert all(x in names for x in layouts), layouts
     ks = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -82,6 +84,13 @@ def main():
             rest, kw = rest_areas()
             keep += [cols, rest]
             g.bind_columns(cols, N17, COLS, **kw)
+        if name == "tables":
+            def polys(n):
+                return [torch.zeros((N17, 4), dtype=torch.int64, device="cuda") for _ in range(n)]
+            cols, lks, cds, css = polys(K * COLS), polys(K), polys(K * 2), polys(K * 2)
+            keep += [cols, lks, cds, css]
+            g.bind_columns(cols, N17, COLS, lookup_capacity=N17, chip_rows_capacity=N17, lookup_ptrs=lks, chip_dense_ptrs=cds,
+                           chip_spread_ptrs=css)
         G[name] = d
     torch.cuda.synchronize()
 
@@ -110,8 +119,9 @@ def main():
     def ratio(a, b):
         return out[a]["ms"] / out[b]["ms"] if a in out and b in out else None
     res["carved_over_owned"], res["separate_over_owned"], res["carved_over_bound"] = ratio("carved", "owned"), ratio("separate", "owned"), ratio("carved", "bound")
-    got = [x for x in (res["carved_over_owned"], res["separate_over_owned"]) if x is not None]
-    if len(got) == 2:
+    res["tables_over_owned"] = ratio("tables", "owned")
+    got = [x for x in (res["carved_over_owned"], res["separate_over_owned"], res["tables_over_owned"]) if x is not None]
+    if len(got) == 3:
         res["target_met"] = bool(max(got) <= 1.10)            # within the 10 % run-to-run placement swing
     eng.close()
     line = json.dumps(res)

@@ -161,9 +161,8 @@ hipError_t fresh_zeroed(void **out, size_t bytes, const void *old = nullptr, siz
 
 struct DeviceScopeG : DeviceScope { using DeviceScope::DeviceScope; };   // for the C ABI functions below
 
-int digest_prepare(const uint8_t *input, size_t input_byte_size, size_t precomputed_input_len,
-                   size_t max_variable_byte_size, DigestPlan *plan) {
-    if (!plan || (!input && input_byte_size)) return HSW_ERR_INVALID_ARG;
+int digest_plan(size_t input_byte_size, size_t precomputed_input_len, size_t max_variable_byte_size, DigestPlan *plan) {
+    if (!plan) return HSW_ERR_INVALID_ARG;
     const size_t one_round_size = 64;                                         // lib.rs:48
     if (max_variable_byte_size % one_round_size != 0) return HSW_ERR_SHAPE;   // lib.rs:57-59
     const size_t input_byte_size_with_9 = input_byte_size + 9;                // lib.rs:78
@@ -173,9 +172,24 @@ int digest_prepare(const uint8_t *input, size_t input_byte_size, size_t precompu
     if (precomputed_input_len > padded_size ||
         padded_size - precomputed_input_len > max_variable_byte_size)
         return HSW_ERR_TOO_LARGE;                                             // lib.rs:90
-    const size_t zero_padding_byte_size = padded_size - input_byte_size_with_9;               // lib.rs:91
+    plan->num_round = num_round;
+    plan->precomputed_round = precomputed_input_len / one_round_size;         // lib.rs:93
+    plan->target_round = num_round - plan->precomputed_round;
+    plan->max_variable_round = max_variable_byte_size / one_round_size;
+    return HSW_OK;
+}
+
+int digest_prepare(const uint8_t *input, size_t input_byte_size, size_t precomputed_input_len,
+                   size_t max_variable_byte_size, DigestPlan *plan) {
+    if (!plan || (!input && input_byte_size)) return HSW_ERR_INVALID_ARG;
+    DigestPlan lengths;
+    const int rc = digest_plan(input_byte_size, precomputed_input_len, max_variable_byte_size, &lengths);
+    if (rc != HSW_OK) return rc;
+    const size_t one_round_size = 64;
+    const size_t num_round = lengths.num_round, padded_size = one_round_size * num_round;
+    const size_t zero_padding_byte_size = padded_size - (input_byte_size + 9);                // lib.rs:91
     const size_t remaining_byte_size = max_variable_byte_size + precomputed_input_len - padded_size;   // lib.rs:92
-    const size_t precomputed_round = precomputed_input_len / one_round_size;  // lib.rs:93
+    const size_t precomputed_round = lengths.precomputed_round;
     const size_t total = max_variable_byte_size + precomputed_input_len;
 
     std::memcpy(plan->init_state, INIT_STATE, sizeof INIT_STATE);             // lib.rs:155
@@ -205,8 +219,8 @@ int digest_prepare(const uint8_t *input, size_t input_byte_size, size_t precompu
     }
     plan->num_round = num_round;
     plan->precomputed_round = precomputed_round;
-    plan->target_round = num_round - precomputed_round;
-    plan->max_variable_round = max_variable_byte_size / one_round_size;
+    plan->target_round = lengths.target_round;
+    plan->max_variable_round = lengths.max_variable_round;
     return HSW_OK;
 }
 
@@ -240,7 +254,7 @@ std::vector<std::pair<uint64_t, uint64_t>> Sha256DynamicConfig::load() const {
 Context::~Context() {
     if (!bound) { (void)hipFree(d_gate); (void)hipFree(d_chip_dense); (void)hipFree(d_chip_spread); (void)hipFree(d_lookup); }
     (void)hipFree(d_next_states); (void)hipFree(d_blocks); (void)hipFree(d_pre_states);
-    (void)hipFree(d_init_states); (void)hipFree(d_offsets); (void)hipFree(d_place);
+    (void)hipFree(d_init_states); (void)hipFree(d_offsets); (void)hipFree(d_place); (void)hipFree(d_ingest);
     if (hp_blocks) (void)hipHostFree(hp_blocks);
     free_compact_staging();
 }
@@ -780,64 +794,16 @@ int Sha256DynamicConfig::digest(Context &ctx, const uint8_t *input, size_t input
     return digest_batch(ctx, 1, &input, &input_len, &precomputed_input_len, result);
 }
 
-int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *const *inputs,
-                                      const size_t *input_lens, const size_t *precomputed_input_lens,
-                                      AssignedHashResult *results) {
-    if (!results || !inputs || !input_lens) return HSW_ERR_INVALID_ARG;
-    if (n == 0) return HSW_OK;
-    // max_variable_byte_sizes[cur_hash_idx] must exist for every hash (lib.rs:86 would panic)
-    if (cur_hash_idx + n > max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
-
-    // ---- host: lib.rs:77-160 for every message; nothing is committed on error ----
-    std::vector<DigestPlan> plans(n);
-    size_t batch_blocks = 0;
-    for (size_t i = 0; i < n; i++) {
-        const size_t max_sz = max_variable_byte_sizes[cur_hash_idx + i];
-        const int rc = digest_prepare(inputs[i], input_lens[i],
-                                      precomputed_input_lens ? precomputed_input_lens[i] : 0, max_sz, &plans[i]);
-        if (rc != HSW_OK) return rc;
-        batch_blocks += plans[i].max_variable_round;
-    }
-    if (ctx.blocks_done + batch_blocks > ctx.capacity_blocks || n > ctx.init_capacity) return HSW_ERR_INVALID_ARG;
-
-    std::vector<uint8_t> h_blocks(batch_blocks * 64 ? batch_blocks * 64 : 1);
-    std::vector<uint32_t> h_init(n * 8), h_offsets(n + 1);
-    size_t off = 0;
-    for (size_t i = 0; i < n; i++) {
-        h_offsets[i] = (uint32_t)off;
-        if (!plans[i].blocks.empty()) std::memcpy(h_blocks.data() + off * 64, plans[i].blocks.data(), plans[i].blocks.size());
-        std::memcpy(&h_init[8 * i], plans[i].init_state, 32);
-        off += plans[i].max_variable_round;
-    }
-    h_offsets[n] = (uint32_t)off;
-    // The plain SHA chain (pre-state of every block, lib.rs:188,236) is the only serial part.  Chained
-    // on the host it sits next to the prefix pre-hash the reference also does on the CPU (lib.rs:153-160)
-    // and saves a dependent kernel launch; on the GPU (hsw_chain_var_kernel) every message has its own
-    // lane.  Either way the witness cells -- and the next_states the digest is read from -- come from the
-    // GPU.  Host-chained batches stage blocks and pre-states in pinned, device-mapped host memory.
-    // Which side chains: the host walks all blocks at ~0.1 us each (x86 SHA extensions; 0.4 us scalar), the
-    // GPU chains every message on its own wave (up to 2,048 messages: ~1.8 us per block) or lane (~3.6 us per
-    // block) plus a dependent launch.  Many short messages -> GPU; few long ones -> host.
-    size_t longest = 0;
-    for (size_t i = 0; i < n; i++) longest = plans[i].max_variable_round > longest ? plans[i].max_variable_round : longest;
-    const double t_host_us = (double)batch_blocks * (host_sha_is_fast() ? 0.1 : 0.4);
-    const double t_gpu_us = 15.0 + (n <= (size_t)HSW_CHAIN_WAVE_MAX_MESSAGES ? 1.8 : 3.6) * (double)longest;   // a wave / a lane per message
-    const bool host_chain = t_host_us <= t_gpu_us;
+// (c) The common tail of digest_batch and digest_batch_device, the plans made and nothing committed yet:
+// stage(stream, zero_copy) issues what puts the batch's blocks at d_blocks + 64 * b0 and their pre-states at
+// d_pre_states + 8 * b0 (zero_copy: the host-fed staging left them in the pinned buffers, read in place); then the
+// expansion / frame launches, the next states, the results and the cursors.  Nothing after the staging knows where
+// the bytes came from.  device_fed: the staged blocks and the states after the prefixes come back with the next states.
+template <class Stage>
+int Sha256DynamicConfig::digest_tail(Context &ctx, size_t n, const size_t *input_lens, std::vector<DigestPlan> &plans,
+                                     size_t batch_blocks, bool host_chain, bool device_fed, Stage &&stage,
+                                     AssignedHashResult *results) {
     const size_t b0 = ctx.blocks_done;
-    if (host_chain && batch_blocks) {
-        std::memcpy(ctx.hp_blocks + 64 * b0, h_blocks.data(), batch_blocks * 64);
-        uint32_t *h_pre = ctx.hp_pre + 8 * b0;
-        for (size_t i = 0; i < n; i++) {
-            uint32_t st[8];
-            std::memcpy(st, plans[i].init_state, 32);
-            for (size_t j = 0; j < plans[i].max_variable_round; j++) {
-                const size_t b = h_offsets[i] + j;
-                std::memcpy(&h_pre[8 * b], st, 32);
-                plain_compress(st, h_blocks.data() + 64 * b);
-            }
-        }
-    }
-
     // ---- device: chain pre-pass + ONE expansion launch for the whole batch ----
     hipStream_t stream = nullptr;
     int device = 0;
@@ -854,27 +820,32 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
     if (ctx.group_m && !ctx.layout.max_rows) return HSW_ERR_UNSUPPORTED;        // K images: hsw_gadget_set_columns first
     const bool small = !ctx.group_m && hsw_small_eligible(ctx.engine, batch_blocks);
     const bool zero_copy = host_chain && (ctx.whole ? small : (small || batch_blocks <= 32));
-    const uint8_t *d_blk = (zero_copy ? ctx.dp_blocks : ctx.d_blocks) + 64 * b0;
     uint32_t *d_next = ctx.d_next_states + 8 * b0;
-    uint32_t *d_off = ctx.d_offsets;
     uint32_t *h_next = ctx.hp_next + 8 * b0;                                     // pinned: the D2H below is asynchronous
+    // device-fed: the batch's staged blocks come back into its hp_blocks range (AssignedHashResult::input_bytes) and
+    // the n states after the prefixes (the target_round == 0 selection) into its idle hp_pre range where they fit
+    std::vector<uint32_t> init_pageable;
+    uint32_t *h_init = nullptr;
+    if (device_fed) {
+        if (n > batch_blocks) init_pageable.resize(8 * n);
+        h_init = n > batch_blocks ? init_pageable.data() : ctx.hp_pre + 8 * b0;
+    }
+    auto fetch_staged = [&]() -> hipError_t {
+        if (!device_fed) return hipSuccess;
+        hipError_t e = hipSuccess;
+        if (batch_blocks) e = hipMemcpyAsync(ctx.hp_blocks + 64 * b0, ctx.d_blocks + 64 * b0, batch_blocks * 64, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_init, ctx.d_init_states, n * 32, hipMemcpyDeviceToHost, stream);
+        return e;
+    };
     hipError_t he = hipSuccess;
     int rc = HSW_OK;
     bool next_in_pinned = false;               // the kernel wrote the next states into hp_next itself
     std::vector<hsw_frame_desc> frames;
     uint64_t new_gate_cursor = ctx.gate_cursor, new_lookup_cursor = ctx.lookup_cursor;
     do {
-        if (batch_blocks == 0) break;
-        if (host_chain && !zero_copy) {      // from pinned memory: both copies are asynchronous DMA
-            if ((he = hipMemcpyAsync(ctx.d_blocks + 64 * b0, ctx.hp_blocks + 64 * b0, batch_blocks * 64, hipMemcpyHostToDevice, stream)) != hipSuccess) break;
-            if ((he = hipMemcpyAsync(ctx.d_pre_states + 8 * b0, ctx.hp_pre + 8 * b0, batch_blocks * 32, hipMemcpyHostToDevice, stream)) != hipSuccess) break;
-        }
-        if (!host_chain) {
-            if ((he = hipMemcpyAsync(ctx.d_blocks + 64 * b0, h_blocks.data(), batch_blocks * 64, hipMemcpyHostToDevice, stream)) != hipSuccess) break;
-            if ((he = hipMemcpyAsync(ctx.d_init_states, h_init.data(), n * 32, hipMemcpyHostToDevice, stream)) != hipSuccess) break;
-            if ((he = hipMemcpyAsync(d_off, h_offsets.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream)) != hipSuccess) break;
-            if ((he = launch_chain_var(d_blk, n, d_off, ctx.d_init_states, ctx.d_pre_states + 8 * b0, stream)) != hipSuccess) break;
-        }
+        if (batch_blocks == 0 && !device_fed) break;
+        if ((he = stage(stream, zero_copy)) != hipSuccess) break;
+        if (batch_blocks == 0) { if ((he = fetch_staged()) == hipSuccess) he = hipStreamSynchronize(stream); break; }   // (device-fed: the prefix states)
         const size_t G = ctx.shape.gate_cells_per_block;
         // shared context: every launch placed by the jump table (uploaded when the layout changed)
         if (ctx.table_path() && (rc = ctx.upload_place()) != HSW_OK) break;
@@ -961,13 +932,18 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
         if (rc != HSW_OK) break;
         if (!next_in_pinned &&
             (he = hipMemcpyAsync(h_next, d_next, batch_blocks * 32, hipMemcpyDeviceToHost, stream)) != hipSuccess) break;
+        if ((he = fetch_staged()) != hipSuccess) break;
         he = hipStreamSynchronize(stream);
     } while (0);
     if (rc != HSW_OK) return rc;
     if (he != hipSuccess) return hip_status(he);
+    for (size_t i = 0, blk = b0; device_fed && i < n; blk += plans[i++].max_variable_round) {   // what the host-fed plans hold
+        std::memcpy(plans[i].init_state, h_init + 8 * i, 32);
+        plans[i].blocks.assign(ctx.hp_blocks + 64 * blk, ctx.hp_blocks + 64 * (blk + plans[i].max_variable_round));
+    }
 
     // ---- results: the "select state #target_round" rule (lib.rs:294-310) ----
-    off = 0;
+    size_t off = 0;
     for (size_t i = 0; i < n; i++) {
         AssignedHashResult &r = results[i];
         const DigestPlan &pl = plans[i];
@@ -1000,6 +976,122 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
     ctx.num_limb_sum += (uint64_t)batch_blocks * ctx.shape.limb_calls_per_block;   // spread.rs:228
     cur_hash_idx += n;                                                             // lib.rs:347
     return HSW_OK;
+}
+
+int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *const *inputs,
+                                      const size_t *input_lens, const size_t *precomputed_input_lens,
+                                      AssignedHashResult *results) {
+    if (!results || !inputs || !input_lens) return HSW_ERR_INVALID_ARG;
+    if (n == 0) return HSW_OK;
+    // max_variable_byte_sizes[cur_hash_idx] must exist for every hash (lib.rs:86 would panic)
+    if (cur_hash_idx + n > max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
+
+    // ---- host: lib.rs:77-160 for every message; nothing is committed on error ----
+    // (a) the plans, (b) host-fed staging: padded blocks, prefix pre-hash and -- usually -- the chain, (c) the tail
+    std::vector<DigestPlan> plans(n);
+    size_t batch_blocks = 0;
+    for (size_t i = 0; i < n; i++) {
+        const size_t max_sz = max_variable_byte_sizes[cur_hash_idx + i];
+        const int rc = digest_prepare(inputs[i], input_lens[i],
+                                      precomputed_input_lens ? precomputed_input_lens[i] : 0, max_sz, &plans[i]);
+        if (rc != HSW_OK) return rc;
+        batch_blocks += plans[i].max_variable_round;
+    }
+    if (ctx.blocks_done + batch_blocks > ctx.capacity_blocks || n > ctx.init_capacity) return HSW_ERR_INVALID_ARG;
+
+    std::vector<uint8_t> h_blocks(batch_blocks * 64 ? batch_blocks * 64 : 1);
+    std::vector<uint32_t> h_init(n * 8), h_offsets(n + 1);
+    size_t off = 0;
+    for (size_t i = 0; i < n; i++) {
+        h_offsets[i] = (uint32_t)off;
+        if (!plans[i].blocks.empty()) std::memcpy(h_blocks.data() + off * 64, plans[i].blocks.data(), plans[i].blocks.size());
+        std::memcpy(&h_init[8 * i], plans[i].init_state, 32);
+        off += plans[i].max_variable_round;
+    }
+    h_offsets[n] = (uint32_t)off;
+    // The plain SHA chain (pre-state of every block, lib.rs:188,236) is the only serial part.  Chained
+    // on the host it sits next to the prefix pre-hash the reference also does on the CPU (lib.rs:153-160)
+    // and saves a dependent kernel launch; on the GPU (hsw_chain_var_kernel) every message has its own
+    // lane.  Either way the witness cells -- and the next_states the digest is read from -- come from the
+    // GPU.  Host-chained batches stage blocks and pre-states in pinned, device-mapped host memory.
+    // Which side chains: the host walks all blocks at ~0.1 us each (x86 SHA extensions; 0.4 us scalar), the
+    // GPU chains every message on its own wave (up to 2,048 messages: ~1.8 us per block) or lane (~3.6 us per
+    // block) plus a dependent launch.  Many short messages -> GPU; few long ones -> host.
+    size_t longest = 0;
+    for (size_t i = 0; i < n; i++) longest = plans[i].max_variable_round > longest ? plans[i].max_variable_round : longest;
+    const double t_host_us = (double)batch_blocks * (host_sha_is_fast() ? 0.1 : 0.4);
+    const double t_gpu_us = 15.0 + (n <= (size_t)HSW_CHAIN_WAVE_MAX_MESSAGES ? 1.8 : 3.6) * (double)longest;   // a wave / a lane per message
+    const bool host_chain = t_host_us <= t_gpu_us;
+    const size_t b0 = ctx.blocks_done;
+    if (host_chain && batch_blocks) {
+        std::memcpy(ctx.hp_blocks + 64 * b0, h_blocks.data(), batch_blocks * 64);
+        uint32_t *h_pre = ctx.hp_pre + 8 * b0;
+        for (size_t i = 0; i < n; i++) {
+            uint32_t st[8];
+            std::memcpy(st, plans[i].init_state, 32);
+            for (size_t j = 0; j < plans[i].max_variable_round; j++) {
+                const size_t b = h_offsets[i] + j;
+                std::memcpy(&h_pre[8 * b], st, 32);
+                plain_compress(st, h_blocks.data() + 64 * b);
+            }
+        }
+    }
+
+    // what the tail issues once it knows whether the kernels read the pinned staging in place
+    auto stage = [&](hipStream_t stream, bool zero_copy) -> hipError_t {
+        hipError_t he = hipSuccess;
+        uint32_t *d_off = ctx.d_offsets;
+        if (host_chain && !zero_copy) {      // from pinned memory: both copies are asynchronous DMA
+            if ((he = hipMemcpyAsync(ctx.d_blocks + 64 * b0, ctx.hp_blocks + 64 * b0, batch_blocks * 64, hipMemcpyHostToDevice, stream)) != hipSuccess) return he;
+            if ((he = hipMemcpyAsync(ctx.d_pre_states + 8 * b0, ctx.hp_pre + 8 * b0, batch_blocks * 32, hipMemcpyHostToDevice, stream)) != hipSuccess) return he;
+        }
+        if (!host_chain) {
+            if ((he = hipMemcpyAsync(ctx.d_blocks + 64 * b0, h_blocks.data(), batch_blocks * 64, hipMemcpyHostToDevice, stream)) != hipSuccess) return he;
+            if ((he = hipMemcpyAsync(ctx.d_init_states, h_init.data(), n * 32, hipMemcpyHostToDevice, stream)) != hipSuccess) return he;
+            if ((he = hipMemcpyAsync(d_off, h_offsets.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream)) != hipSuccess) return he;
+            if ((he = launch_chain_var(ctx.d_blocks + 64 * b0, n, d_off, ctx.d_init_states, ctx.d_pre_states + 8 * b0, stream)) != hipSuccess) return he;
+        }
+        return he;
+    };
+    return digest_tail(ctx, n, input_lens, plans, batch_blocks, host_chain, /*device_fed=*/false, stage, results);
+}
+
+// The same batch with the message bytes in device memory (hsw_gadget_digest_batch_device): the plans follow from the
+// lengths alone, and ONE hsw_ingest_kernel launch does what the host-fed staging does with padding, prefix pre-hash,
+// copies and chain.  The host never reads a message byte.
+int Sha256DynamicConfig::digest_batch_device(Context &ctx, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                                             const size_t *precomputed_input_lens, AssignedHashResult *results) {
+    if (!results || !d_inputs || !input_lens) return HSW_ERR_INVALID_ARG;
+    if (n == 0) return HSW_OK;
+    if (cur_hash_idx + n > max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
+    std::vector<DigestPlan> plans(n);
+    std::vector<IngestDesc> descs(n);
+    size_t batch_blocks = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (!d_inputs[i] && input_lens[i]) return HSW_ERR_INVALID_ARG;
+        int rc = digest_plan(input_lens[i], precomputed_input_lens ? precomputed_input_lens[i] : 0,
+                             max_variable_byte_sizes[cur_hash_idx + i], &plans[i]);
+        if (rc == HSW_OK && (uint64_t)input_lens[i] > 0xffffffffull) rc = HSW_ERR_TOO_LARGE;   // (the kernel's round counters are 32-bit)
+        if (rc != HSW_OK) return rc;
+        descs[i] = IngestDesc{static_cast<const uint8_t *>(d_inputs[i]), input_lens[i], (uint32_t)(ctx.blocks_done + batch_blocks),
+                              (uint32_t)plans[i].max_variable_round, (uint32_t)plans[i].num_round, (uint32_t)plans[i].precomputed_round};
+        batch_blocks += plans[i].max_variable_round;
+    }
+    if (ctx.blocks_done + batch_blocks > ctx.capacity_blocks || n > ctx.init_capacity) return HSW_ERR_INVALID_ARG;
+    if (!ctx.d_ingest) {                                     // first device-fed batch: a descriptor per hash in flight
+        int device = 0;
+        hsw_engine_stream(ctx.engine, nullptr, &device);
+        DeviceScope ds(device);
+        if (!ds.ok) return HSW_ERR_NO_DEVICE;
+        const hipError_t he = hipMalloc(&ctx.d_ingest, (ctx.init_capacity ? ctx.init_capacity : 1) * sizeof(IngestDesc));
+        if (he != hipSuccess) { ctx.d_ingest = nullptr; return hip_status(he); }
+    }
+    auto stage = [&](hipStream_t stream, bool) -> hipError_t {
+        const hipError_t he = hipMemcpyAsync(ctx.d_ingest, descs.data(), n * sizeof(IngestDesc), hipMemcpyHostToDevice, stream);
+        if (he != hipSuccess) return he;
+        return launch_ingest(static_cast<const IngestDesc *>(ctx.d_ingest), n, ctx.d_blocks, ctx.d_init_states, ctx.d_pre_states, stream);
+    };
+    return digest_tail(ctx, n, input_lens, plans, batch_blocks, /*host_chain=*/false, /*device_fed=*/true, stage, results);
 }
 
 }  // namespace hsw
@@ -1109,6 +1201,19 @@ int hsw_gadget_digest_batch(hsw_gadget *g, size_t n, const uint8_t *const *input
     if (!g || !results) return HSW_ERR_INVALID_ARG;
     std::vector<hsw::AssignedHashResult> rs(n);
     const int rc = g->cfg.digest_batch(*g->ctx, n, inputs, input_lens, precomputed_input_lens, rs.data());
+    if (rc != HSW_OK) return rc;
+    for (size_t i = 0; i < n; i++) {
+        fill_result(rs[i], &results[i]);
+        g->results.push_back(std::move(rs[i]));
+    }
+    return HSW_OK;
+} HSW_NO_UNWIND
+
+int hsw_gadget_digest_batch_device(hsw_gadget *g, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                                   const size_t *precomputed_input_lens, hsw_hash_result *results) try {
+    if (!g || !results) return HSW_ERR_INVALID_ARG;
+    std::vector<hsw::AssignedHashResult> rs(n);
+    const int rc = g->cfg.digest_batch_device(*g->ctx, n, d_inputs, input_lens, precomputed_input_lens, rs.data());
     if (rc != HSW_OK) return rc;
     for (size_t i = 0; i < n; i++) {
         fill_result(rs[i], &results[i]);

@@ -38,6 +38,10 @@ struct DigestPlan {
     size_t max_variable_round = 0; // lib.rs:87: compressions synthesised, always the maximum
 };
 
+// The part of lib.rs:77-93 that needs no bytes: the four round counts of *plan from the lengths alone, with the
+// refusals below (blocks and init_state are left alone).
+int digest_plan(size_t input_byte_size, size_t precomputed_input_len, size_t max_variable_byte_size, DigestPlan *plan);
+
 // lib.rs:77-117,153-160.  Returns HSW_OK or the status the reference's
 // assert!/debug_assert! maps to (HSW_ERR_SHAPE / HSW_ERR_TOO_LARGE).
 int digest_prepare(const uint8_t *input, size_t input_byte_size, size_t precomputed_input_len,
@@ -85,9 +89,19 @@ class Sha256DynamicConfig {
     // n consecutive digest() calls with one kernel launch; results[i] as if called in order.
     int digest_batch(Context &ctx, size_t n, const uint8_t *const *inputs, const size_t *input_lens,
                      const size_t *precomputed_input_lens, AssignedHashResult *results);
+    // digest_batch with the message bytes in DEVICE memory (hsw_gadget_digest_batch_device): d_inputs[i] is a device
+    // pointer of any alignment, the lengths are host values, the host never reads a byte.  Results as digest_batch's.
+    int digest_batch_device(Context &ctx, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                            const size_t *precomputed_input_lens, AssignedHashResult *results);
 
     // lib.rs:366-368 -> spread.rs:165-194: the (dense, spread) lookup table rows.
     std::vector<std::pair<uint64_t, uint64_t>> load() const;
+
+  private:
+    // what digest_batch and digest_batch_device share once the batch's blocks and pre-states are staged (hsw_gadget.cpp)
+    template <class Stage>
+    int digest_tail(Context &ctx, size_t n, const size_t *input_lens, std::vector<DigestPlan> &plans, size_t batch_blocks,
+                    bool host_chain, bool device_fed, Stage &&stage, AssignedHashResult *results);
 };
 
 // The Region-owning context of lib.rs:351-360, re-imagined for HBM: it owns the
@@ -110,6 +124,7 @@ class Context {
     uint32_t *d_init_states = nullptr;   // one per hash in flight
     uint32_t *d_offsets = nullptr;       // first block of every hash in flight (+ 1): hsw_chain_var_kernel
     size_t init_capacity = 0;
+    void *d_ingest = nullptr;            // device-fed batches: a message descriptor per hash in flight (hsw_ingest_kernel), on first use
     // small batches: pinned, device-mapped host staging the kernels read directly (no H2D copies) and
     // the next states are copied back into (a truly asynchronous D2H): capacity_blocks * (64 + 32 + 32) bytes
     uint8_t *hp_blocks = nullptr;        // host views ...

@@ -92,6 +92,114 @@ __global__ __launch_bounds__(64) void hsw_chain_wave_kernel(const uint8_t *block
     }
 }
 
+// The two halves of hsw_chain_wave_kernel's chunk as helpers for hsw_ingest_kernel (the chain kernel itself keeps its
+// own text: the code the compiler schedules for it is left exactly as it was).  A lane's block, as 16 big-endian
+// words, becomes the 64 words K[t] + W[t] of its LDS row ...
+constexpr u32 CHAIN_CH = 32;                               // blocks per chunk
+constexpr u32 CHAIN_ROW = 64 + 4;                          // +4: rows of consecutive lanes start in different banks
+DEV void chain_schedule(u32 (&w)[16], u32 *row) {
+#pragma unroll
+    for (int i = 0; i < 16; i++) row[i] = w[i] + K256[i];
+#pragma unroll
+    for (int t = 16; t < 64; t++) {
+        w[t & 15] = w[t & 15] + sha_s0(w[(t - 15) & 15]) + w[(t - 7) & 15] + sha_s1(w[(t - 2) & 15]);
+        row[t] = w[t & 15] + K256[t];
+    }
+}
+// ... and the 64 rounds of one block run wave-uniform, K + W from its row four rounds at a time.
+DEV void chain_rounds(u32 (&st)[8], const u32 *row) {
+    u32 a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
+#pragma unroll
+    for (int t = 0; t < 64; t += 4) {
+        const uint4 kw = *reinterpret_cast<const uint4 *>(&row[t]);
+        const u32 q[4] = {kw.x, kw.y, kw.z, kw.w};
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const u32 t1 = h + q[u] + sha_S1(e) + sha_ch(e, f, g);
+            const u32 t2 = sha_S0(a) + sha_maj(a, b, c);
+            h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+        }
+    }
+    st[0] += a; st[1] += b; st[2] += c; st[3] += d;
+    st[4] += e; st[5] += f; st[6] += g; st[7] += h;
+}
+// the (wave-uniform) state to 32-byte aligned memory: two 16-byte stores of lane 0
+DEV void chain_store_state(const u32 (&st)[8], u32 lane, u32 *dst) {
+    if (lane == 0) {
+        reinterpret_cast<uint4 *>(dst)[0] = make_uint4(st[0], st[1], st[2], st[3]);
+        reinterpret_cast<uint4 *>(dst)[1] = make_uint4(st[4], st[5], st[6], st[7]);
+    }
+}
+
+// The chain pre-pass for messages that already live in device memory (hsw_gadget_digest_batch_device): one wave per
+// message pads it (lib.rs:98-117), compresses the rounds of the precomputed prefix (lib.rs:156-160; the state after
+// them goes to init_states[m]) and stages every later round -- its 64 bytes to `blocks`, its pre-state to
+// `pre_states` -- where the host-fed path puts them with two copies and hsw_chain_wave_kernel.  lane = round, in
+// chunks of CHAIN_CH rounds, over the rounds [0, precomputed_round + n_blocks) of the padded stream.
+// The source has any byte alignment: a lane reads the aligned dwords its 64 bytes lie in and realigns them, and
+// NO load touches a 16-byte granule that holds no byte of [src, src + len) -- a message that ends with its
+// allocation is not read past, a zero-length message is not read at all.
+__global__ __launch_bounds__(64) void hsw_ingest_kernel(const IngestDesc *descs, size_t n_messages, uint8_t *blocks,
+                                                        u32 *init_states, u32 *pre_states) {
+    __shared__ u32 s_kw[CHAIN_CH][CHAIN_ROW];
+    const size_t m = blockIdx.x;
+    if (m >= n_messages) return;
+    const u32 lane = threadIdx.x;
+    const IngestDesc d = descs[m];
+    const u64 src = (u64)(uintptr_t)d.src, len = d.len;
+    const u64 src_end = (src + len + 15u) & ~(u64)15;      // end of the last granule with a message byte
+    const u64 pre = d.precomputed_round, total = pre + d.n_blocks;
+    u32 st[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) st[i] = IV256[i];
+    for (u64 c0 = 0; c0 < total; c0 += CHAIN_CH) {
+        const u32 nb = (u32)(total - c0 < CHAIN_CH ? total - c0 : CHAIN_CH);
+        if (lane < nb) {
+            const u64 r = c0 + lane, p0 = 64 * r;          // the round, its first byte in the padded stream
+            const u64 a0 = (src + p0) & ~(u64)3;
+            const u32 shift = (u32)(src + p0) & 3u;
+            u32 q[17];                                     // the aligned dwords around the round's 64 source bytes
+#pragma unroll
+            for (int i = 0; i < 17; i++) {
+                const u64 a = a0 + 4u * (u32)i;
+                q[i] = len != 0 && a < src_end ? *reinterpret_cast<const u32 *>((uintptr_t)a) : 0u;
+            }
+            u32 v[16], w[16];                              // the block in memory order, and as big-endian words
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const u64 p = p0 + 4u * (u32)i;            // the "padded byte at position p" rule, four bytes at a time
+                u32 x = __builtin_amdgcn_alignbyte(q[i + 1], q[i], shift);
+                if (p + 4 > len) {
+                    const u32 k = p <= len ? 8u * (u32)(len - p) : 32u;      // message bytes (in bits) the word still holds
+                    x = k < 32u ? (x & ((1u << k) - 1u)) | (0x80u << k) : 0u;
+                }
+                v[i] = x;
+            }
+            if (r + 1 == d.num_round) {                    // the big-endian bit length closes the last round
+                const u64 bits = 8 * len;
+                v[14] = __builtin_bswap32((u32)(bits >> 32)); v[15] = __builtin_bswap32((u32)bits);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) w[i] = __builtin_bswap32(v[i]);
+            if (r >= pre) {
+                uint4 *dst = reinterpret_cast<uint4 *>(blocks + 64 * ((u64)d.first_block + (r - pre)));
+#pragma unroll
+                for (int i = 0; i < 4; i++) dst[i] = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+            }
+            chain_schedule(w, s_kw[lane]);
+        }
+        __syncthreads();
+        for (u32 j = 0; j < nb; j++) {
+            const u64 r = c0 + j;
+            if (r == pre) chain_store_state(st, lane, init_states + 8 * m);
+            if (r >= pre) chain_store_state(st, lane, pre_states + 8 * ((u64)d.first_block + (r - pre)));
+            chain_rounds(st, s_kw[j]);
+        }
+        __syncthreads();
+    }
+    if (pre == total) chain_store_state(st, lane, init_states + 8 * m);      // nothing but the prefix
+}
+
 // One thread per message, uniform blocks per message (hsw.h hsw_sha256_chain).
 __global__ __launch_bounds__(64) void hsw_chain_kernel(const uint8_t *blocks, size_t n_messages,
                                                        size_t bpm, const u32 *init_states,
@@ -223,6 +331,14 @@ hipError_t launch_chain_var(const uint8_t *blocks, size_t n_messages, const uint
     }
     const unsigned grid = (unsigned)((n_messages + 63) / 64);
     hipLaunchKernelGGL(hsw_chain_var_kernel, dim3(grid), dim3(64), 0, stream, blocks, n_messages, offsets,
+                       init_states, pre_states);
+    return hipGetLastError();
+}
+
+hipError_t launch_ingest(const IngestDesc *d_descs, size_t n_messages, uint8_t *blocks, uint32_t *init_states,
+                         uint32_t *pre_states, hipStream_t stream) {
+    if (n_messages == 0) return hipSuccess;
+    hipLaunchKernelGGL(hsw_ingest_kernel, dim3((unsigned)n_messages), dim3(64), 0, stream, d_descs, n_messages, blocks,
                        init_states, pre_states);
     return hipGetLastError();
 }

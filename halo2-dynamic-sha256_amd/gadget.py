@@ -120,6 +120,40 @@ class Sha256DynamicConfig:
         self._pending.extend(out)
         return out
 
+    def digest_batch_device(self, inputs, precomputed_input_lens=None):
+        """hsw_gadget_digest_batch_device: digest_batch for messages that already live in device memory.  Every
+        input is a contiguous 1-D torch.uint8 device tensor (its data_ptr() and numel() are taken; the caller keeps
+        it alive) or a (device_ptr, length) pair; lengths are host values.  The bytes must be complete before the
+        call -- produced on the engine's stream, or synchronised -- and must not overlap what the gadget writes."""
+        ptrs_, lens_ = [], []
+        for x in inputs:                         # checked in full before any call into the library
+            if isinstance(x, (tuple, list)):
+                p, ln = x
+                p, ln = int(p or 0), int(ln)
+                if ln < 0 or (ln and not p):
+                    raise ValueError("a (device_ptr, length) input needs a pointer for a non-zero length")
+            else:
+                import torch
+                if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 1:
+                    raise TypeError("inputs are 1-D torch.uint8 device tensors or (device_ptr, length) pairs")
+                if not x.is_cuda or not x.is_contiguous():
+                    raise ValueError("an input tensor must be contiguous and live on the device")
+                p, ln = (int(x.data_ptr()) if x.numel() else 0), int(x.numel())
+            ptrs_.append(p)
+            lens_.append(ln)
+        n = len(ptrs_)
+        ptrs = (C.c_void_p * max(n, 1))(*ptrs_)
+        lens = (C.c_size_t * max(n, 1))(*lens_)
+        pl = precomputed_input_lens or [None] * n
+        pre = (C.c_size_t * max(n, 1))(*[int(p or 0) for p in pl])
+        res = (N.HashResult * max(n, 1))()
+        self._ok(self.lib.hsw_gadget_digest_batch_device(self.h, n, ptrs, lens, pre, res))
+        base = self._n
+        out = [AssignedHashResult(res[i], (lambda k=base + i: self._input_bytes(k))) for i in range(n)]
+        self._n += n
+        self._pending.extend(out)
+        return out
+
     def set_columns(self, max_rows):
         """Lay the whole-digest stream out as FlexGate advice columns of max_rows rows (before the
         first digest).  Returns the number of columns."""

@@ -48,7 +48,7 @@ extern "C" {
 #endif
 
 #define HSW_ABI_VERSION 3   /* 3: hsw_gadget_view grew the origin fields; hsw_gadget_set_origin */
-#define HSW_ABI_MINOR 1     /* additions that leave every existing entry point as it was: 1: hsw_gadget_bind_column_tables */
+#define HSW_ABI_MINOR 1     /* additions that leave every existing entry point as it was: 1: hsw_gadget_bind_column_tables; hsw_gadget_digest_batch_device came later under the same minor (probe for the symbol) */
 
 /* ---- status codes ---- */
 #define HSW_OK                 0
@@ -919,6 +919,22 @@ int hsw_gadget_digest(hsw_gadget *g, const uint8_t *input, size_t input_len,
 int hsw_gadget_digest_batch(hsw_gadget *g, size_t n, const uint8_t *const *inputs,
                             const size_t *input_lens, const size_t *precomputed_input_lens,
                             hsw_hash_result *results);
+/* hsw_gadget_digest_batch with the message bytes in DEVICE memory.  d_inputs, input_lens and
+ * precomputed_input_lens are HOST arrays of n entries; d_inputs[i] is a device pointer of any byte alignment to
+ * input_lens[i] readable bytes (may be NULL when input_lens[i] == 0).  The host never reads the bytes: ONE kernel
+ * launch pads every message, hashes its precomputed prefix and stages its blocks, reading no 16-byte granule that
+ * holds no byte of the message.
+ * Synchronous, like hsw_gadget_digest_batch.  The bytes must be complete before the call: the caller has either
+ * synchronised their producer or produced them on the stream the engine was created with.  The buffers must not
+ * overlap anything the gadget writes, bound columns included.  Everything else is the host-fed call's, for every
+ * kind of gadget and binding: results, cursors, hsw_gadget_result_cells, hsw_gadget_input_bytes (the padded bytes
+ * come back with the states, 64 bytes per block), hsw_gadget_verify, seek, reset and every delivery.
+ * Argument errors are the host-fed call's too, decided from the lengths alone before anything is launched or
+ * committed: HSW_ERR_SHAPE (lib.rs:89), HSW_ERR_TOO_LARGE (lib.rs:90; also a message above 4 GiB),
+ * HSW_ERR_INVALID_ARG for a NULL pointer with a non-zero length or a batch past the gadget's capacity. */
+int hsw_gadget_digest_batch_device(hsw_gadget *g, size_t n, const void *const *d_inputs,
+                                   const size_t *input_lens, const size_t *precomputed_input_lens,
+                                   hsw_hash_result *results);
 int hsw_gadget_streams(hsw_gadget *g, hsw_gadget_view *view);
 /* Where the cells of digest #hash_idx's AssignedHashResult (lib.rs:31-36, 342-346) sit -- what a shim
  * needs to hand back to the circuit (the reference's TestCircuit constrains output_bytes to its instance

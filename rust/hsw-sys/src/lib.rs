@@ -492,6 +492,11 @@ extern "C" {
     pub fn hsw_gadget_digest_batch(g: *mut hsw_gadget, n: usize, inputs: *const *const u8,
                                    input_lens: *const usize, precomputed_input_lens: *const usize,
                                    results: *mut hsw_hash_result) -> c_int;
+    /// `hsw_gadget_digest_batch` with the message bytes in device memory: `d_inputs`, `input_lens` and
+    /// `precomputed_input_lens` are host arrays, `d_inputs[i]` a device pointer of any alignment.
+    pub fn hsw_gadget_digest_batch_device(g: *mut hsw_gadget, n: usize, d_inputs: *const *const c_void,
+                                          input_lens: *const usize, precomputed_input_lens: *const usize,
+                                          results: *mut hsw_hash_result) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

@@ -221,7 +221,7 @@ SYMBOLS = (
     "hsw_gadget_set_origin", "hsw_gadget_region_tape", "hsw_gadget_download_region_distinct", "hsw_gadget_replay_region",
     "hsw_gadget_context_region", "hsw_gadget_set_digest_origin", "hsw_gadget_create_contexts",
     "hsw_gadget_bind_region", "hsw_gadget_region_binding", "hsw_gadget_bind_columns", "hsw_gadget_bind_column_tables",
-    "hsw_gadget_digest_batch_device",
+    "hsw_gadget_digest_batch_device", "hsw_gadget_digest_levels_device",
 )
 
 
@@ -300,6 +300,9 @@ def lib():
         L.hsw_gadget_digest_batch_device.restype = C.c_int
         L.hsw_gadget_digest_batch_device.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t),
                                                      C.POINTER(C.c_size_t), C.POINTER(HashResult)]
+        L.hsw_gadget_digest_levels_device.restype = C.c_int
+        L.hsw_gadget_digest_levels_device.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                                      C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(HashResult)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

@@ -362,6 +362,8 @@ int hsw_witness_blocks_ex(hsw_engine *e, const hsw_witness_args *args) try {
 
 }  // extern "C"
 
+int hsw_engine_fail(hsw_engine *e, int status, const char *what) { return set_err(e, status, what); }
+
 // The small-batch kernel (hsw_small.hpp) takes a launch when the table is the reference's 8-bit one and the
 // batch is tiny (or the "split" option asks for it); everything else goes to hsw_expand_kernel.
 bool hsw_small_eligible(const hsw_engine *e, size_t n_blocks) {

@@ -78,6 +78,8 @@ inline int set_err(hsw_engine *e, int status, const char *what, hipError_t he = 
 
 namespace hsw { struct SmallFrames; struct ContextPeriod; }
 bool hsw_small_eligible(const hsw_engine *e, size_t n_blocks);
+// for translation units that see the engine as an opaque handle: sets hsw_last_error's text, returns status
+int hsw_engine_fail(hsw_engine *e, int status, const char *what);
 // period: context images (hsw_kernels.h ContextPeriod; NULL = off) -- the gadget's HSW_GADGET_CONTEXT_IMAGES launches
 int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const hsw::SmallFrames *frames,
                             uint32_t *host_next_states, const hsw::ContextPeriod *period);

@@ -20,6 +20,7 @@
 
 // library-internal entry points of hsw_api.cpp (hsw_engine.hpp)
 bool hsw_small_eligible(const hsw_engine *e, size_t n_blocks);
+int hsw_engine_fail(hsw_engine *e, int status, const char *what);
 int hsw_witness_blocks_impl(hsw_engine *e, const hsw_witness_args *args, const hsw::SmallFrames *frames,
                             uint32_t *host_next_states, const hsw::ContextPeriod *period);
 int hsw_witness_digests_impl(hsw_engine *e, const hsw_digests_args *args, uint32_t *dev_next_states,
@@ -1056,16 +1057,20 @@ int Sha256DynamicConfig::digest_batch(Context &ctx, size_t n, const uint8_t *con
     return digest_tail(ctx, n, input_lens, plans, batch_blocks, host_chain, /*device_fed=*/false, stage, results);
 }
 
-// The same batch with the message bytes in device memory (hsw_gadget_digest_batch_device): the plans follow from the
-// lengths alone, and ONE hsw_ingest_kernel launch does what the host-fed staging does with padding, prefix pre-hash,
-// copies and chain.  The host never reads a message byte.
-int Sha256DynamicConfig::digest_batch_device(Context &ctx, size_t n, const void *const *d_inputs, const size_t *input_lens,
-                                             const size_t *precomputed_input_lens, AssignedHashResult *results) {
+// The same batch with the message bytes in device memory (hsw_gadget_digest_levels_device; every level equal and no
+// outputs: hsw_gadget_digest_batch_device): the plans follow from the lengths alone, and ONE hsw_ingest_kernel launch
+// per dependency level does what the host-fed staging does with padding, prefix pre-hash, copies and chain -- and
+// leaves each digest where a message of a later level reads it.  The launches follow each other on the engine's
+// stream with nothing in between: the kernel boundary orders a level's stores before the next level's loads.  The
+// host reads neither a message byte nor a digest from those addresses.
+int Sha256DynamicConfig::digest_levels_device(Context &ctx, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                                              const size_t *precomputed_input_lens, const uint32_t *levels,
+                                              void *const *d_outputs, AssignedHashResult *results) {
     if (!results || !d_inputs || !input_lens) return HSW_ERR_INVALID_ARG;
     if (n == 0) return HSW_OK;
     if (cur_hash_idx + n > max_variable_byte_sizes.size()) return HSW_ERR_INVALID_ARG;
     std::vector<DigestPlan> plans(n);
-    std::vector<IngestDesc> descs(n);
+    std::vector<IngestDesc> by_msg(n);
     size_t batch_blocks = 0;
     for (size_t i = 0; i < n; i++) {
         if (!d_inputs[i] && input_lens[i]) return HSW_ERR_INVALID_ARG;
@@ -1073,11 +1078,46 @@ int Sha256DynamicConfig::digest_batch_device(Context &ctx, size_t n, const void 
                              max_variable_byte_sizes[cur_hash_idx + i], &plans[i]);
         if (rc == HSW_OK && (uint64_t)input_lens[i] > 0xffffffffull) rc = HSW_ERR_TOO_LARGE;   // (the kernel's round counters are 32-bit)
         if (rc != HSW_OK) return rc;
-        descs[i] = IngestDesc{static_cast<const uint8_t *>(d_inputs[i]), input_lens[i], (uint32_t)(ctx.blocks_done + batch_blocks),
-                              (uint32_t)plans[i].max_variable_round, (uint32_t)plans[i].num_round, (uint32_t)plans[i].precomputed_round};
+        by_msg[i] = IngestDesc{static_cast<const uint8_t *>(d_inputs[i]), input_lens[i], (uint32_t)(ctx.blocks_done + batch_blocks),
+                               (uint32_t)plans[i].max_variable_round, (uint32_t)plans[i].num_round, (uint32_t)plans[i].precomputed_round,
+                               d_outputs ? static_cast<uint8_t *>(d_outputs[i]) : nullptr, (uint32_t)i, 0u};
         batch_blocks += plans[i].max_variable_round;
     }
     if (ctx.blocks_done + batch_blocks > ctx.capacity_blocks || n > ctx.init_capacity) return HSW_ERR_INVALID_ARG;
+
+    // ---- who may read whom: byte ranges (a wave discards the bytes of a granule that are not its message's), sorted
+    auto level = [&](size_t i) -> uint32_t { return levels ? levels[i] : 0u; };
+    std::vector<std::pair<uintptr_t, size_t>> outs;              // (address, message) of every destination, by address
+    for (size_t i = 0; d_outputs && i < n; i++)
+        if (d_outputs[i]) outs.emplace_back(reinterpret_cast<uintptr_t>(d_outputs[i]), i);
+    std::sort(outs.begin(), outs.end());
+    char why[160];
+    for (size_t k = 1; k < outs.size(); k++)
+        if (outs[k].first - outs[k - 1].first < 32) {
+            std::snprintf(why, sizeof why, "hsw_gadget_digest_levels_device: the outputs of messages %zu and %zu overlap",
+                          outs[k - 1].second, outs[k].second);
+            return hsw_engine_fail(ctx.engine, HSW_ERR_INVALID_ARG, why);
+        }
+    for (size_t i = 0; i < n && !outs.empty(); i++) {
+        if (!input_lens[i]) continue;
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(d_inputs[i]), hi = lo + input_lens[i];
+        // the first destination that ends after lo (destinations are disjoint: at most one starts below lo and does)
+        auto it = std::lower_bound(outs.begin(), outs.end(), std::make_pair(lo, (size_t)0));
+        if (it != outs.begin() && lo - (it - 1)->first < 32) --it;
+        for (; it != outs.end() && it->first < hi; ++it)
+            if (level(it->second) >= level(i)) {
+                std::snprintf(why, sizeof why, "hsw_gadget_digest_levels_device: message %zu (level %u) reads the output of message %zu "
+                              "(level %u), which is not of a lower level", i, level(i), it->second, level(it->second));
+                return hsw_engine_fail(ctx.engine, HSW_ERR_INVALID_ARG, why);
+            }
+    }
+
+    // ---- the descriptor table, stably sorted by level: a level is a run of it, and a launch
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; i++) order[i] = i;
+    if (levels) std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return levels[a] < levels[b]; });
+    std::vector<IngestDesc> descs(n);
+    for (size_t k = 0; k < n; k++) descs[k] = by_msg[order[k]];
     if (!ctx.d_ingest) {                                     // first device-fed batch: a descriptor per hash in flight
         int device = 0;
         hsw_engine_stream(ctx.engine, nullptr, &device);
@@ -1087,11 +1127,20 @@ int Sha256DynamicConfig::digest_batch_device(Context &ctx, size_t n, const void 
         if (he != hipSuccess) { ctx.d_ingest = nullptr; return hip_status(he); }
     }
     auto stage = [&](hipStream_t stream, bool) -> hipError_t {
-        const hipError_t he = hipMemcpyAsync(ctx.d_ingest, descs.data(), n * sizeof(IngestDesc), hipMemcpyHostToDevice, stream);
-        if (he != hipSuccess) return he;
-        return launch_ingest(static_cast<const IngestDesc *>(ctx.d_ingest), n, ctx.d_blocks, ctx.d_init_states, ctx.d_pre_states, stream);
+        hipError_t he = hipMemcpyAsync(ctx.d_ingest, descs.data(), n * sizeof(IngestDesc), hipMemcpyHostToDevice, stream);
+        for (size_t k0 = 0, k1; he == hipSuccess && k0 < n; k0 = k1) {
+            for (k1 = k0 + 1; k1 < n && level(order[k1]) == level(order[k0]); k1++) {}
+            he = launch_ingest(static_cast<const IngestDesc *>(ctx.d_ingest) + k0, k1 - k0, ctx.d_blocks, ctx.d_init_states,
+                               ctx.d_pre_states, stream);
+        }
+        return he;
     };
     return digest_tail(ctx, n, input_lens, plans, batch_blocks, /*host_chain=*/false, /*device_fed=*/true, stage, results);
+}
+
+int Sha256DynamicConfig::digest_batch_device(Context &ctx, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                                             const size_t *precomputed_input_lens, AssignedHashResult *results) {
+    return digest_levels_device(ctx, n, d_inputs, input_lens, precomputed_input_lens, nullptr, nullptr, results);
 }
 
 }  // namespace hsw
@@ -1214,6 +1263,20 @@ int hsw_gadget_digest_batch_device(hsw_gadget *g, size_t n, const void *const *d
     if (!g || !results) return HSW_ERR_INVALID_ARG;
     std::vector<hsw::AssignedHashResult> rs(n);
     const int rc = g->cfg.digest_batch_device(*g->ctx, n, d_inputs, input_lens, precomputed_input_lens, rs.data());
+    if (rc != HSW_OK) return rc;
+    for (size_t i = 0; i < n; i++) {
+        fill_result(rs[i], &results[i]);
+        g->results.push_back(std::move(rs[i]));
+    }
+    return HSW_OK;
+} HSW_NO_UNWIND
+
+int hsw_gadget_digest_levels_device(hsw_gadget *g, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                                    const size_t *precomputed_input_lens, const uint32_t *levels, void *const *d_outputs,
+                                    hsw_hash_result *results) try {
+    if (!g || !results) return HSW_ERR_INVALID_ARG;
+    std::vector<hsw::AssignedHashResult> rs(n);
+    const int rc = g->cfg.digest_levels_device(*g->ctx, n, d_inputs, input_lens, precomputed_input_lens, levels, d_outputs, rs.data());
     if (rc != HSW_OK) return rc;
     for (size_t i = 0; i < n; i++) {
         fill_result(rs[i], &results[i]);

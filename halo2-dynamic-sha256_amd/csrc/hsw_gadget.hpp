@@ -93,6 +93,15 @@ class Sha256DynamicConfig {
     // pointer of any alignment, the lengths are host values, the host never reads a byte.  Results as digest_batch's.
     int digest_batch_device(Context &ctx, size_t n, const void *const *d_inputs, const size_t *input_lens,
                             const size_t *precomputed_input_lens, AssignedHashResult *results);
+    // digest_batch_device over dependency levels (hsw_gadget_digest_levels_device): levels[i] (NULL: all 0) orders the
+    // messages, d_outputs[i] (NULL table or entry: none) receives digest i's 32 bytes in DEVICE memory, and a message
+    // may read what a message of a strictly lower level writes.  One hsw_ingest_kernel launch per distinct level,
+    // back to back on the engine's stream, then the common tail once; the host reads neither inputs nor outputs.
+    // Overlapping outputs, and an input that overlaps the output of a message not of a lower level, are refused
+    // (HSW_ERR_INVALID_ARG, the engine's error text names the two messages) before anything is launched or committed.
+    int digest_levels_device(Context &ctx, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                             const size_t *precomputed_input_lens, const uint32_t *levels, void *const *d_outputs,
+                             AssignedHashResult *results);
 
     // lib.rs:366-368 -> spread.rs:165-194: the (dense, spread) lookup table rows.
     std::vector<std::pair<uint64_t, uint64_t>> load() const;

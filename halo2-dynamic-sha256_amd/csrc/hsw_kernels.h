@@ -78,16 +78,21 @@ hipError_t launch_chain(const uint8_t *blocks, size_t n_messages, size_t blocks_
 
 hipError_t launch_chain_var(const uint8_t *blocks, size_t n_messages, const uint32_t *offsets,
                             const uint32_t *init_states, uint32_t *pre_states, hipStream_t stream);
-// One message of hsw_gadget_digest_batch_device for hsw_ingest_kernel: len bytes at the DEVICE address src (any
+// One message of hsw_gadget_digest_levels_device for hsw_ingest_kernel: len bytes at the DEVICE address src (any
 // alignment; never dereferenced when len == 0), padded to num_round rounds of which the first precomputed_round are
 // only compressed and the next n_blocks (zero rounds past num_round included) are staged from block first_block on.
+// msg: the message's index in the call (its row of init_states), whatever its place in the table.  dst: NULL, or the
+// DEVICE address (any alignment) of the 32 bytes that receive the digest, the state after round num_round - 1.
 struct IngestDesc {
     const uint8_t *src;
     uint64_t len;
     uint32_t first_block, n_blocks, num_round, precomputed_round;
+    uint8_t *dst;
+    uint32_t msg, reserved;
 };
-// Padding, prefix pre-hash, staging and chain in one launch: blocks / pre_states are the staging buffers from their
-// block 0, init_states[8 * m] receives message m's state after its prefix.
+// Padding, prefix pre-hash, staging and chain in one launch over the n_messages descriptors at d_descs (the whole
+// table of a call, or the part of it that forms one dependency level): blocks / pre_states are the staging buffers
+// from their block 0, init_states[8 * msg] receives a message's state after its prefix.
 hipError_t launch_ingest(const IngestDesc *d_descs, size_t n_messages, uint8_t *blocks, uint32_t *init_states,
                          uint32_t *pre_states, hipStream_t stream);
 hipError_t launch_fill(void *dst, size_t bytes, hipStream_t stream);

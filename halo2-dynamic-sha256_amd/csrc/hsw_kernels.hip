@@ -131,7 +131,17 @@ DEV void chain_store_state(const u32 (&st)[8], u32 lane, u32 *dst) {
     }
 }
 
-// The chain pre-pass for messages that already live in device memory (hsw_gadget_digest_batch_device): one wave per
+// the 32 big-endian digest bytes of the (wave-uniform) state to dst, which has ANY byte alignment: lane i stores
+// byte i and nothing else, so no store touches a byte outside [dst, dst + 32) -- a sibling digest next to it, written
+// by another wave of the same launch, is never read, merged or rewritten
+DEV void chain_store_digest(const u32 (&st)[8], u32 lane, uint8_t *dst) {
+    const u32 shift = 24 - 8 * (lane & 3);                 // lib.rs:311-341: word i, most significant byte first
+#pragma unroll
+    for (u32 i = 0; i < 8; i++)                            // (a store per word under its lanes' predicate: st stays in registers)
+        if ((lane >> 2) == i) dst[lane] = (uint8_t)(st[i] >> shift);
+}
+
+// The chain pre-pass for messages that already live in device memory (hsw_gadget_digest_levels_device): one wave per
 // message pads it (lib.rs:98-117), compresses the rounds of the precomputed prefix (lib.rs:156-160; the state after
 // them goes to init_states[m]) and stages every later round -- its 64 bytes to `blocks`, its pre-state to
 // `pre_states` -- where the host-fed path puts them with two copies and hsw_chain_wave_kernel.  lane = round, in
@@ -139,6 +149,10 @@ DEV void chain_store_state(const u32 (&st)[8], u32 lane, u32 *dst) {
 // The source has any byte alignment: a lane reads the aligned dwords its 64 bytes lie in and realigns them, and
 // NO load touches a 16-byte granule that holds no byte of [src, src + len) -- a message that ends with its
 // allocation is not read past, a zero-length message is not read at all.
+// descs[blockIdx.x] is any (sorted) part of the call's table: d.msg is the message's index in the call, the row of
+// init_states it owns.  A message with a destination gets its digest there, the state after round num_round - 1 --
+// wherever that round lies: in the prefix (target_round == 0), in the middle of a chunk, before zero rounds that the
+// wave still has to stage.
 __global__ __launch_bounds__(64) void hsw_ingest_kernel(const IngestDesc *descs, size_t n_messages, uint8_t *blocks,
                                                         u32 *init_states, u32 *pre_states) {
     __shared__ u32 s_kw[CHAIN_CH][CHAIN_ROW];
@@ -191,13 +205,14 @@ __global__ __launch_bounds__(64) void hsw_ingest_kernel(const IngestDesc *descs,
         __syncthreads();
         for (u32 j = 0; j < nb; j++) {
             const u64 r = c0 + j;
-            if (r == pre) chain_store_state(st, lane, init_states + 8 * m);
+            if (r == pre) chain_store_state(st, lane, init_states + 8 * (u64)d.msg);
             if (r >= pre) chain_store_state(st, lane, pre_states + 8 * ((u64)d.first_block + (r - pre)));
             chain_rounds(st, s_kw[j]);
+            if (r + 1 == d.num_round && d.dst) chain_store_digest(st, lane, d.dst);
         }
         __syncthreads();
     }
-    if (pre == total) chain_store_state(st, lane, init_states + 8 * m);      // nothing but the prefix
+    if (pre == total) chain_store_state(st, lane, init_states + 8 * (u64)d.msg);      // nothing but the prefix
 }
 
 // One thread per message, uniform blocks per message (hsw.h hsw_sha256_chain).

@@ -125,8 +125,21 @@ class Sha256DynamicConfig:
         input is a contiguous 1-D torch.uint8 device tensor (its data_ptr() and numel() are taken; the caller keeps
         it alive) or a (device_ptr, length) pair; lengths are host values.  The bytes must be complete before the
         call -- produced on the engine's stream, or synchronised -- and must not overlap what the gadget writes."""
+        ptrs_, lens_ = self._device_inputs(inputs)
+        n = len(ptrs_)
+        ptrs = (C.c_void_p * max(n, 1))(*ptrs_)
+        lens = (C.c_size_t * max(n, 1))(*lens_)
+        pl = precomputed_input_lens or [None] * n
+        pre = (C.c_size_t * max(n, 1))(*[int(p or 0) for p in pl])
+        res = (N.HashResult * max(n, 1))()
+        self._ok(self.lib.hsw_gadget_digest_batch_device(self.h, n, ptrs, lens, pre, res))
+        return self._assigned(res, n)
+
+    @staticmethod
+    def _device_inputs(inputs):
+        """(pointers, lengths) of device-fed inputs, checked in full before any call into the library."""
         ptrs_, lens_ = [], []
-        for x in inputs:                         # checked in full before any call into the library
+        for x in inputs:
             if isinstance(x, (tuple, list)):
                 p, ln = x
                 p, ln = int(p or 0), int(ln)
@@ -141,18 +154,86 @@ class Sha256DynamicConfig:
                 p, ln = (int(x.data_ptr()) if x.numel() else 0), int(x.numel())
             ptrs_.append(p)
             lens_.append(ln)
-        n = len(ptrs_)
-        ptrs = (C.c_void_p * max(n, 1))(*ptrs_)
-        lens = (C.c_size_t * max(n, 1))(*lens_)
-        pl = precomputed_input_lens or [None] * n
-        pre = (C.c_size_t * max(n, 1))(*[int(p or 0) for p in pl])
-        res = (N.HashResult * max(n, 1))()
-        self._ok(self.lib.hsw_gadget_digest_batch_device(self.h, n, ptrs, lens, pre, res))
+        return ptrs_, lens_
+
+    def _assigned(self, res, n):
         base = self._n
         out = [AssignedHashResult(res[i], (lambda k=base + i: self._input_bytes(k))) for i in range(n)]
         self._n += n
         self._pending.extend(out)
         return out
+
+    def digest_levels_device(self, inputs, levels=None, outputs=None, precomputed_input_lens=None):
+        """hsw_gadget_digest_levels_device: digest_batch_device for messages that depend on each other's digests.
+        inputs as for digest_batch_device.  levels[i] (default: all 0) is message i's dependency level, in any order.
+        outputs[i] is a contiguous 1-D torch.uint8 device tensor of 32 elements, an integer device pointer to 32
+        writable bytes of any alignment, or None; digest i is written there, and a message may read what a message
+        of a strictly lower level of the same call writes -- with no host read in between.  Overlapping outputs, and
+        an input overlapping the output of a message not of a lower level, raise HswError (HSW_ERR_INVALID_ARG)."""
+        ptrs_, lens_ = self._device_inputs(inputs)
+        n = len(ptrs_)
+        if levels is not None:
+            levels = [int(v) for v in levels]
+            if len(levels) != n or any(v < 0 or v > 0xffffffff for v in levels):
+                raise ValueError("levels holds one non-negative 32-bit level per input")
+        outs_ = None
+        if outputs is not None:
+            outputs = list(outputs)
+            if len(outputs) != n:
+                raise ValueError("outputs holds one entry (or None) per input")
+            outs_ = []
+            for x in outputs:
+                if x is None:
+                    p = 0
+                elif hasattr(x, "data_ptr") or isinstance(x, bool) or not hasattr(x, "__index__"):
+                    import torch
+                    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 1:
+                        raise TypeError("outputs are 1-D torch.uint8 device tensors of 32 elements, device pointers or None")
+                    if not x.is_cuda or not x.is_contiguous() or x.numel() != 32:
+                        raise ValueError("an output tensor must hold 32 contiguous bytes on the device")
+                    p = int(x.data_ptr())
+                else:
+                    p = int(x)
+                    if p <= 0:
+                        raise ValueError("an integer output is a non-null device pointer (None: no output)")
+                outs_.append(p)
+        if precomputed_input_lens is not None and len(precomputed_input_lens) != n:
+            raise ValueError("precomputed_input_lens holds one entry (or None) per input")
+        ptrs = (C.c_void_p * max(n, 1))(*ptrs_)
+        lens = (C.c_size_t * max(n, 1))(*lens_)
+        pl = precomputed_input_lens or [None] * n
+        pre = (C.c_size_t * max(n, 1))(*[int(p or 0) for p in pl])
+        lv = (C.c_uint32 * max(n, 1))(*levels) if levels is not None else None
+        outs = (C.c_void_p * max(n, 1))(*outs_) if outs_ is not None else None
+        res = (N.HashResult * max(n, 1))()
+        self._ok(self.lib.hsw_gadget_digest_levels_device(self.h, n, ptrs, lens, pre, lv, outs, res))
+        return self._assigned(res, n)
+
+    def merkle_tree_device(self, leaves, nodes):
+        """A binary Merkle tree over n = 2^d leaves in one digest_levels_device call (the gadget's next 2n - 1
+        digests).  leaves: device inputs as for digest_batch_device; nodes: a contiguous 1-D torch.uint8 device tensor
+        of 32 * (2n - 1) bytes.  Level 0, the leaf digests, fills nodes[0 : 32n]; every further level follows the one
+        below it in memory; an inner message is the 64 bytes of its two children where they lie, never copied; the
+        root is the last 32 bytes.  Returns the results, leaves first."""
+        import torch
+        leaves = list(leaves)
+        n = len(leaves)
+        if n < 1 or n & (n - 1):
+            raise ValueError("merkle_tree_device takes a power-of-two number of leaves")
+        if not isinstance(nodes, torch.Tensor) or nodes.dtype != torch.uint8 or nodes.dim() != 1:
+            raise TypeError("nodes is a 1-D torch.uint8 device tensor")
+        if not nodes.is_cuda or not nodes.is_contiguous() or nodes.numel() != 32 * (2 * n - 1):
+            raise ValueError("nodes must hold 32 * (2n - 1) contiguous bytes on the device")
+        base = int(nodes.data_ptr())
+        inputs, levels = leaves, [0] * n
+        below, width, level = 0, n, 0            # the level below: its first node and its width
+        while width > 1:
+            level += 1
+            inputs = inputs + [(base + 32 * (below + 2 * j), 64) for j in range(width // 2)]
+            levels += [level] * (width // 2)
+            below, width = below + width, width // 2
+        outputs = [base + 32 * k for k in range(2 * n - 1)]
+        return self.digest_levels_device(inputs, levels, outputs)
 
     def set_columns(self, max_rows):
         """Lay the whole-digest stream out as FlexGate advice columns of max_rows rows (before the

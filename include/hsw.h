@@ -48,7 +48,7 @@ extern "C" {
 #endif
 
 #define HSW_ABI_VERSION 3   /* 3: hsw_gadget_view grew the origin fields; hsw_gadget_set_origin */
-#define HSW_ABI_MINOR 1     /* additions that leave every existing entry point as it was: 1: hsw_gadget_bind_column_tables; hsw_gadget_digest_batch_device came later under the same minor (probe for the symbol) */
+#define HSW_ABI_MINOR 1     /* additions that leave every existing entry point as it was: 1: hsw_gadget_bind_column_tables; hsw_gadget_digest_batch_device and hsw_gadget_digest_levels_device came later under the same minor (probe for the symbol) */
 
 /* ---- status codes ---- */
 #define HSW_OK                 0
@@ -935,6 +935,28 @@ int hsw_gadget_digest_batch(hsw_gadget *g, size_t n, const uint8_t *const *input
 int hsw_gadget_digest_batch_device(hsw_gadget *g, size_t n, const void *const *d_inputs,
                                    const size_t *input_lens, const size_t *precomputed_input_lens,
                                    hsw_hash_result *results);
+/* hsw_gadget_digest_batch_device for messages that DEPEND on each other's digests: a Merkle tree, an iterated hash,
+ * a transcript that absorbs a digest -- in one call, with no host read between the dependency levels.
+ * The n messages are the gadget's next n digests in digest order, exactly as for hsw_gadget_digest_batch_device.
+ * levels (HOST array, n entries; NULL: every message is of level 0): levels[i] is message i's dependency level,
+ * in any order and with gaps -- in a Context group the trees of the proofs interleave.
+ * d_outputs (HOST array, n entries; NULL, or NULL entries: no destination): d_outputs[i] is a device pointer of any
+ * byte alignment to 32 writable bytes that receive digest i, big-endian as in hsw_hash_result.output_bytes; no byte
+ * outside those 32 is written, read or rewritten.
+ * A message may read bytes that a message of a STRICTLY LOWER level of the same call writes: one hsw_ingest_kernel
+ * launch per distinct level, in ascending order, back to back on the engine's stream, then the expansion once over
+ * the whole batch.  Results, hsw_gadget_input_bytes, hsw_gadget_verify and everything else are the device-fed call's,
+ * for every kind of gadget and binding.  Every level equal and d_outputs == NULL: hsw_gadget_digest_batch_device.
+ * Refused with HSW_ERR_INVALID_ARG, from the pointers and lengths alone, before anything is launched or committed,
+ * hsw_last_error naming the two messages: two outputs whose 32-byte ranges overlap; an input range
+ * [d_inputs[i], + input_lens[i]) that overlaps the output of a message whose level is not strictly lower (the same
+ * level is a race, a higher level reads stale bytes).  The argument errors of hsw_gadget_digest_batch_device apply
+ * unchanged.  Outputs, like inputs, must not overlap anything the gadget writes, bound columns included: this is
+ * NOT checked.  Bytes that no message of the call writes must be complete before the call, as above. */
+int hsw_gadget_digest_levels_device(hsw_gadget *g, size_t n, const void *const *d_inputs,
+                                    const size_t *input_lens, const size_t *precomputed_input_lens,
+                                    const uint32_t *levels, void *const *d_outputs,
+                                    hsw_hash_result *results);
 int hsw_gadget_streams(hsw_gadget *g, hsw_gadget_view *view);
 /* Where the cells of digest #hash_idx's AssignedHashResult (lib.rs:31-36, 342-346) sit -- what a shim
  * needs to hand back to the circuit (the reference's TestCircuit constrains output_bytes to its instance

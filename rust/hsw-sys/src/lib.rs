@@ -497,6 +497,13 @@ extern "C" {
     pub fn hsw_gadget_digest_batch_device(g: *mut hsw_gadget, n: usize, d_inputs: *const *const c_void,
                                           input_lens: *const usize, precomputed_input_lens: *const usize,
                                           results: *mut hsw_hash_result) -> c_int;
+    /// `hsw_gadget_digest_batch_device` over dependency levels: `levels` (may be null: all 0) orders the messages,
+    /// `d_outputs` (may be null, entries may be null) names the 32 device bytes that receive each digest, and a
+    /// message may read what a message of a strictly lower level of the same call writes.
+    pub fn hsw_gadget_digest_levels_device(g: *mut hsw_gadget, n: usize, d_inputs: *const *const c_void,
+                                           input_lens: *const usize, precomputed_input_lens: *const usize,
+                                           levels: *const u32, d_outputs: *const *mut c_void,
+                                           results: *mut hsw_hash_result) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

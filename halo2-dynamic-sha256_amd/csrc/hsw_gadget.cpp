@@ -1788,9 +1788,11 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
         const int rc0 = c.upload_place();
         if (rc0 != HSW_OK) return rc0;
     }
-    auto merge = [&](const hsw_verify_report &r) {
+    // block0: a block launch reports blocks counted from its own first one (the frames report the pass's), the
+    // gadget's report names blocks of the pass
+    auto merge = [&](const hsw_verify_report &r, uint64_t block0) {
         if (r.violations && !report->violations) {
-            report->first_block = r.first_block; report->first_cell = r.first_cell; report->first_class = r.first_class;
+            report->first_block = r.first_block + block0; report->first_cell = r.first_cell; report->first_class = r.first_class;
         }
         report->violations += r.violations; report->checks += r.checks; report->kernel_ms += r.kernel_ms;
     };
@@ -1801,7 +1803,7 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
             L.blocks(b.first_block, b.n_blocks);
             const int rc = hsw_verify_blocks(c.engine, &L.a, &r);
             if (rc != HSW_OK) return rc;
-            merge(r);
+            merge(r, b.first_block);
             continue;
         }
         // the launches of the batch as it was generated: runs of equally sized digests, or a group's digest indices
@@ -1813,7 +1815,7 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
             L.run(b.first_digest + run.first, r0, r0.first_block, run.count, fs);
             rc = hsw_verify_blocks_impl(c.engine, &L.a, &r, L.per);
             if (rc != HSW_OK) return rc;
-            merge(r);
+            merge(r, r0.first_block);
             std::vector<hsw_frame_desc> descs(run.count);
             for (size_t k = 0; k < run.count; k++) {
                 const hsw::AssignedHashResult &rk = g->results[b.first_digest + run.first + k * run.step];
@@ -1830,7 +1832,7 @@ int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report) try {
             rc = hsw_verify_frames_impl(c.engine, descs.data(), descs.size(), L.in_blocks, L.in_pre, c.d_next_states, c.gate_stream(),
                                         c.d_lookup, L.frame_pack, b.repr_flags, &r, L.per);
             if (rc != HSW_OK) return rc;
-            merge(r);
+            merge(r, 0);
         }
     }
     return HSW_OK;

@@ -887,7 +887,8 @@ int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx);
 /* Check everything the gadget has written so far against the constraint system, on the device:
  * hsw_verify_blocks on every run of blocks + hsw_verify_frames on their frames (whole-digest contexts;
  * linear stream or column image), or hsw_verify_blocks alone (block-stream contexts).  Canonical or
- * Montgomery cells. */
+ * Montgomery cells.  report->first_block counts the gadget's blocks (hsw_hash_result.first_block), whichever
+ * launch found the failure. */
 int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report);
 /* (column, row) of gate-stream cell `cell` (identity on row without set_columns). */
 int hsw_gadget_cell_position(const hsw_gadget *g, uint64_t cell, uint64_t *column, uint64_t *row);

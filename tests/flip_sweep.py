@@ -3,7 +3,10 @@
 time -- all gate cells, both chip columns, the lookup column, the next state, every input byte and pre-state
 word -- and require a violation each time.  A cell whose corruption passes would be a witness the constraint
 system (as recorded from the reference's source) leaves free, or a gap in the verifier.
-Test infrastructure.  usage: python tests/flip_sweep.py [bits] [ncols] [montgomery 0/1]"""
+sweep_frames does the same for the digest frames of one Context; sweep_layout corrupts a seeded sample of cells
+(select_cells) of the jump-table, period and bound layouts, in library-owned or caller-owned memory.
+Test infrastructure.  usage: python tests/flip_sweep.py [bits] [ncols] [montgomery 0/1]
+                             python tests/flip_sweep.py layouts      (cases a-h of tests/test_gpu_flip_layouts.py)"""
 import importlib
 import json
 import os
@@ -143,7 +146,268 @@ def sweep_frames(sizes=(128, 64), rc=True, mont=False, columns=None, limb=0, log
     return missed
 
 
+# ---- the table, period and bound layouts: a seeded sample of cells instead of every cell ---------------------------
+# The two witnesses per digest the reference's circuit leaves free (tests/test_gpu_flip_sweep.py), section-relative:
+FREE_PROLOGUE = 27                                            # frame::P_ISZ + 2, the inverse of is_zero(limb1) (lib.rs:142-143)
+
+
+def free_epilogue(target_round):
+    """The inverse of the is_equal of the selected round (lib.rs:296-310): 76 cells per candidate state, is_equal's
+    four cells, then is_zero's [z, a, inv, ...]."""
+    return 76 * target_round + 4 + 2
+
+
+def _pick(must, n, count, rng):
+    """The offsets `must` that lie in range(n), once each, then `count` distinct seeded random ones (fewer if n is small)."""
+    out = []
+    for x in must:
+        if 0 <= x < n and x not in out:
+            out.append(x)
+    want = min(len(out) + count, n)
+    while len(out) < want:
+        x = int(rng.integers(0, n))
+        if x not in out:
+            out.append(x)
+    return out
+
+
+def select_cells(contexts, seed=5, n_random=8, n_random_lookup=4, n_random_chip=4):
+    """The sample of a layout sweep -- pure: layout facts in, a list of (context, digest, section, cell) out.
+
+    contexts[c][d] is the list of digest d of Context c's sections in stream order, each a dict:
+      name        "prologue" (the Context's zero cell included where the digest assigns it), "block<k>" or "epilogue"
+      cells       gate cells of the section
+      jumps       offsets j in [0, cells]: cell j does not sit one row below cell j - 1 (a column break or an interlude;
+                  0: the jump lies before the section's first cell, cells: behind its last)
+      free        offsets of the witnesses the reference leaves free   (optional)
+      zero        offset of the Context's zero cell, or None           (optional)
+      lookups     entries of the section's run in the lookup-advice column
+      limb_calls  limb calls of a block: one cell each in the dense and in the spread chip column   (blocks only)
+    Gate cells come back under the section's name: its first and last cell, both neighbours of every jump, the free
+    witnesses, the zero cell and n_random random ones.  Lookup entries under "lookup:<name>": first, last and
+    n_random_lookup random ones.  Chip cells under "dense:<name>" / "spread:<name>" (cell = the block's limb call, which
+    alternates between the chip columns): first, last and n_random_chip random ones."""
+    import numpy as np
+    out = []
+    for c, digests in enumerate(contexts):
+        for d, sections in enumerate(digests):
+            for s, sec in enumerate(sections):
+                name, n = sec["name"], int(sec["cells"])
+                special = list(sec.get("free") or []) + ([sec["zero"]] if sec.get("zero") is not None else [])
+                assert n >= 1 and all(0 <= x < n for x in special) and all(0 <= j <= n for j in sec.get("jumps") or []), sec
+                must = [0, n - 1] + [x for j in sec.get("jumps") or [] for x in (j - 1, j)] + special
+                out += [(c, d, name, x) for x in _pick(must, n, n_random, np.random.default_rng([seed, c, d, s, 0]))]
+                m = int(sec.get("lookups") or 0)
+                if m:
+                    out += [(c, d, "lookup:" + name, x) for x in _pick([0, m - 1], m, n_random_lookup, np.random.default_rng([seed, c, d, s, 1]))]
+                m = int(sec.get("limb_calls") or 0)
+                for k, fam in enumerate(("dense", "spread")):
+                    if m:
+                        out += [(c, d, fam + ":" + name, x) for x in _pick([0, m - 1], m, n_random_chip, np.random.default_rng([seed, c, d, s, 2 + k]))]
+    return out
+
+
+def stream_jumps(cfg, lo, hi):
+    """The stream cells i in (lo, hi] that do not sit one row below cell i - 1, from cfg.cell_position.  Jumps only skip
+    cells, so two cells of one column as many rows apart as stream cells have none between them: a bisection, a few
+    dozen cell_position calls per jump instead of one per cell."""
+    out = []
+
+    def walk(a, pa, b, pb):
+        if pa[0] == pb[0] and pb[1] - pa[1] == b - a:
+            return
+        if b == a + 1:
+            out.append(b)
+            return
+        m = (a + b) // 2
+        pm = cfg.cell_position(m)
+        walk(a, pa, m, pm)
+        walk(m, pm, b, pb)
+    if hi > lo:
+        walk(lo, cfg.cell_position(lo), hi, cfg.cell_position(hi))
+    return out
+
+
+def layout_facts(cfg, results, contexts=1, rc=True):
+    """select_cells' layout facts of a finished whole-digest pass: `contexts` Contexts of len(results) / contexts digests
+    each, the sections from every AssignedHashResult, the jumps from cell_position."""
+    eng = cfg.engine
+    G, LC, LK = eng.G, eng.limb_calls, eng.lookup_cells
+    per = len(results) // contexts
+    assert per * contexts == len(results)
+    facts = []
+    for c in range(contexts):
+        rs = results[c * per: (c + 1) * per]
+        jumps = stream_jumps(cfg, rs[0].prologue_cell, rs[-1].end_cell - 1)
+        digests = []
+        for d, r in enumerate(rs):
+            size = cfg.max_variable_byte_sizes[(c * per + d) % len(cfg.max_variable_byte_sizes)]
+            assert r.n_blocks * 64 == size and r.epilogue_cell == r.block_cell + r.n_blocks * G
+            pro = 46 + size * (5 if rc else 1)                 # frame::prologue_cells
+            assert r.block_cell - r.prologue_cell in (pro, pro + 1) and r.end_cell - r.epilogue_cell == 76 * (r.n_blocks + 1) + 288
+            spans = [("prologue", r.prologue_cell, r.block_cell, r.block_lookup - r.prologue_lookup, 0)]
+            spans += [("block%d" % k, r.block_cell + k * G, r.block_cell + (k + 1) * G, LK, LC) for k in range(r.n_blocks)]
+            spans += [("epilogue", r.epilogue_cell, r.end_cell, 64, 0)]
+            assert r.epilogue_lookup == r.block_lookup + r.n_blocks * LK
+            digests.append([dict(name=name, cells=b - a, jumps=[j - a for j in jumps if a <= j <= b], lookups=lookups, limb_calls=limbs,
+                                 free=[FREE_PROLOGUE] if name == "prologue" else [free_epilogue(r.target_round)] if name == "epilogue" else [],
+                                 zero=pro if name == "prologue" and b - a == pro + 1 else None)
+                            for name, a, b, lookups, limbs in spans])
+        facts.append(digests)
+    return facts
+
+
+def free_witnesses(results, contexts=1):
+    """What a sweep of this pass may miss, and must: the two free witnesses of every digest."""
+    per = len(results) // contexts
+    out = []
+    for i, r in enumerate(results):
+        out += [(i // per, i % per, "prologue", FREE_PROLOGUE), (i // per, i % per, "epilogue", free_epilogue(r.target_round))]
+    return out
+
+
+def _dev_view(ptr, n):
+    import torch
+    return torch.as_tensor(_DevCells(ptr, n), device="cuda")
+
+
+class OwnedMemory:
+    """Where the cells of a library-owned region are: view().d_gate / d_lookup / the chip pointers of a single Context,
+    context_region(c) of a context-image gadget or a Context group -- each as an (n, 4) int64 view of device memory."""
+
+    def __init__(self, cfg, contexts=1):
+        v = cfg.view()
+        ncols = cfg.engine.ncols
+        self.rows, cols = int(v.max_rows), int(v.columns)
+        assert self.rows, "a column image (set_columns)"
+        self.image, self.look, self.dense, self.spread = [], [], [], []
+        if cfg.context_images or cfg.n_contexts is not None:
+            for c in range(contexts):
+                r = cfg.context_region(c)
+                assert int(r.assigned) == 1 and int(r.columns) == cols and int(r.max_rows) == self.rows
+                self.image.append(_dev_view(r.d_image, cols * self.rows))
+                self.look.append(_dev_view(r.d_lookup, int(r.lookup_cells)))
+                self.dense.append([_dev_view(r.d_chip_dense + 32 * k * int(r.chip_col_stride), int(r.chip_rows)) for k in range(ncols)])
+                self.spread.append([_dev_view(r.d_chip_spread + 32 * k * int(r.chip_col_stride), int(r.chip_rows)) for k in range(ncols)])
+        else:
+            assert contexts == 1
+            rows = (int(v.num_limb_sum) + ncols - 1) // ncols
+            self.image.append(_dev_view(v.d_gate, cols * self.rows))
+            self.look.append(_dev_view(v.d_lookup, int(v.lookup_cells)))
+            self.dense.append([_dev_view(v.d_chip_dense + 32 * k * int(v.chip_col_stride), rows) for k in range(ncols)])
+            self.spread.append([_dev_view(v.d_chip_spread + 32 * k * int(v.chip_col_stride), rows) for k in range(ncols)])
+
+    def gate(self, c, column, row):
+        return self.image[c], column * self.rows + row
+
+    def lookup(self, c, k):
+        return self.look[c], k
+
+    def chip(self, fam, c, column, row):
+        return (self.dense if fam == "dense" else self.spread)[c][column], row
+
+    def tensors(self):
+        return self.image + self.look + [t for fam in (self.dense, self.spread) for cols in fam for t in cols]
+
+
+class CallerMemory:
+    """Where the cells of a bound region are: in the caller's own tensor `t`, at the indices the caller's carving gives
+    -- gate(c, image column, row), lookup(c, entry of Context c's lookup column), chip(family, c, chip column, row of
+    Context c's chip rows), each returning a cell index of t."""
+
+    def __init__(self, t, gate, lookup, chip):
+        self.t, self._gate, self._lookup, self._chip = t, gate, lookup, chip
+
+    def gate(self, c, column, row):
+        return self.t, self._gate(c, column, row)
+
+    def lookup(self, c, k):
+        return self.t, self._lookup(c, k)
+
+    def chip(self, fam, c, column, row):
+        return self.t, self._chip(fam, c, column, row)
+
+    def tensors(self):
+        return [self.t]
+
+
+def sweep_layout(cfg, results, cells, mem, contexts=1, mont=False, limb=0, log=None, name="layout"):
+    """Corrupt the cells `cells` (select_cells' tuples) of a finished whole-digest pass one at a time, in place in device
+    memory `mem` (OwnedMemory / CallerMemory), with hsw_gadget_verify after each: canonical limb ^= 1, Montgomery ^= 0x10
+    as in sweep().  A stream cell's place comes from cfg.cell_position.  Returns dict(tested, missed, misattributed,
+    seconds): `missed` the cells whose corruption passed, `misattributed` (cell, report) where the report's first_block
+    lies outside the owning digest's blocks or a chip / lookup cell was reported under another class.  Afterwards the
+    region verifies again and every tensor of `mem` equals its snapshot from before the first flip."""
+    import torch
+    eng = cfg.engine
+    G, LC, LK, ncols = eng.G, eng.limb_calls, eng.lookup_cells, eng.ncols
+    per = len(results) // contexts
+    multi = cfg.context_images or cfg.n_contexts is not None
+    oc = int(cfg.view().origin_column)
+    Lp = int(cfg.context_region(0).lookup_cells) if multi else 0
+    # a result's lookup indices count Context c's column from c * the lookup pitch in force: the binding's, or Lp (unbound
+    # and by pointer table, where the binding reports 0)
+    step = (int(cfg.region_binding().lookup_pitch) or Lp) if multi else 0
+    rows_ctx = [int(cfg.context_region(c).chip_rows) for c in range(contexts)] if multi else []
+    assert cfg.verify()["violations"] == 0
+    torch.cuda.synchronize()
+    snaps = [t.clone() for t in mem.tensors()]
+
+    def where(c, d, section, cell):
+        r = results[c * per + d]
+        kind, _, sec = section.rpartition(":")
+        blk = int(sec[5:]) if sec.startswith("block") else None
+        assert 0 <= cell and (blk is None or blk < r.n_blocks)
+        if kind == "":
+            base, n = {"prologue": (r.prologue_cell, r.block_cell - r.prologue_cell), "epilogue": (r.epilogue_cell, r.end_cell - r.epilogue_cell)}.get(
+                sec, (r.block_cell + (blk or 0) * G, G))
+            assert cell < n
+            col, row = cfg.cell_position(base + cell)
+            return mem.gate(c, col - oc, row)
+        if kind == "lookup":
+            base, n = {"prologue": (r.prologue_lookup, r.block_lookup - r.prologue_lookup), "epilogue": (r.epilogue_lookup, 64)}.get(
+                sec, (r.block_lookup + (blk or 0) * LK, LK))
+            assert cell < n and 0 <= base - c * step and (not multi or base - c * step + cell < Lp)
+            return mem.lookup(c, base - c * step + cell)
+        assert kind in ("dense", "spread") and blk is not None and cell < LC
+        call = (r.first_block + blk) * LC + cell               # the absolute limb call: column call % ncols, row call // ncols
+        row = call // ncols - sum(rows_ctx[:c])
+        assert row >= 0 and (not multi or row < rows_ctx[c])
+        return mem.chip(kind, c, call % ncols, row)
+
+    out = dict(tested=0, missed=[], misattributed=[])
+    t0 = time.time()
+    for cell in cells:
+        c, d, section, _ = cell
+        t, at = where(*cell)
+        saved = t[at].clone()
+        t[at][limb] ^= 1 if not mont else 0x10
+        rep = cfg.verify()
+        t[at] = saved
+        out["tested"] += 1
+        if rep["violations"] == 0:
+            out["missed"].append(cell)
+            continue
+        r = results[c * per + d]
+        want = {"dense": "chip", "spread": "chip", "lookup": "lookup"}.get(section.rpartition(":")[0])
+        if not r.first_block <= rep["first_block"] < r.first_block + r.n_blocks or (want and rep["first_class"] != want):
+            out["misattributed"].append((cell, {k: rep[k] for k in ("first_block", "first_cell", "first_class")}))
+    out["seconds"] = time.time() - t0
+    rep = cfg.verify()
+    assert rep["violations"] == 0, rep
+    torch.cuda.synchronize()
+    for t, s in zip(mem.tensors(), snaps):
+        assert torch.equal(t, s), "the sweep left a cell changed"
+    if log:
+        print("%-12s %6d cells, %d undetected  (%.0f s)" % (name, out["tested"], len(out["missed"]), out["seconds"]), file=log, flush=True)
+    return out
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["layouts"]:                      # cases a-h of tests/test_gpu_flip_layouts.py, both forms
+        from tests.test_gpu_flip_layouts import run_all
+        run_all(log=sys.stdout)
+        sys.exit(0)
     bits = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     ncols = int(sys.argv[2]) if len(sys.argv) > 2 else 2
     mont = bool(int(sys.argv[3])) if len(sys.argv) > 3 else False

@@ -202,6 +202,16 @@ class ContextRegion(C.Structure):
                [("assigned", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class CellTie(C.Structure):
+    """hsw_cell_tie: input-byte cell dst_byte of digest dst_hash equals output-byte cell src_byte of digest src_hash."""
+    _fields_ = [("src_hash", C.c_uint64), ("dst_hash", C.c_uint64), ("src_byte", C.c_uint32), ("dst_byte", C.c_uint32),
+                ("src_cell", C.c_uint64), ("dst_cell", C.c_uint64)]
+
+
+class TieReport(C.Structure):
+    _fields_ = [("violations", C.c_uint64), ("checks", C.c_uint64), ("first", C.c_uint64), ("kernel_ms", C.c_float)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -222,6 +232,7 @@ SYMBOLS = (
     "hsw_gadget_context_region", "hsw_gadget_set_digest_origin", "hsw_gadget_create_contexts",
     "hsw_gadget_bind_region", "hsw_gadget_region_binding", "hsw_gadget_bind_columns", "hsw_gadget_bind_column_tables",
     "hsw_gadget_digest_batch_device", "hsw_gadget_digest_levels_device",
+    "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
 )
 
 
@@ -303,6 +314,15 @@ def lib():
         L.hsw_gadget_digest_levels_device.restype = C.c_int
         L.hsw_gadget_digest_levels_device.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                                       C.POINTER(C.c_uint32), C.POINTER(vp), C.POINTER(HashResult)]
+        if hasattr(L, "hsw_gadget_ties"):   # absent only in A/B builds of an earlier commit (HSW_LIB_OVERRIDE)
+            L.hsw_gadget_ties.restype = C.c_int
+            L.hsw_gadget_ties.argtypes = [vp, C.POINTER(CellTie), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]
+            L.hsw_gadget_cell_address.restype = C.c_int
+            L.hsw_gadget_cell_address.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
+            L.hsw_gadget_verify_ties.restype = C.c_int
+            L.hsw_gadget_verify_ties.argtypes = [vp, C.POINTER(TieReport)]
+            L.hsw_gadget_verify_equal.restype = C.c_int
+            L.hsw_gadget_verify_equal.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(TieReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

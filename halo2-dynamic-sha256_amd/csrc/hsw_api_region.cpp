@@ -340,6 +340,40 @@ int hsw_verify_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n,
     return HSW_OK;
 }
 
+// hsw_gadget_verify_ties / hsw_gadget_verify_equal once the gadget has resolved every cell to its device address
+int hsw_verify_pairs_impl(hsw_engine *e, const uint64_t *host_pairs, void *d_pairs, size_t n, hsw_tie_report *report) {
+    if (!e || !report) return HSW_ERR_INVALID_ARG;
+    std::memset(report, 0, sizeof *report);
+    if (n == 0) return HSW_OK;
+    if (!host_pairs || !d_pairs) return set_err(e, HSW_ERR_INVALID_ARG, "null pointer");
+    static_assert(sizeof(hsw::CellPair) == 2 * sizeof(uint64_t), "a pair is two device addresses");
+    // the kernel reads every cell as two 16-byte pieces: a misaligned address would become a device fault
+    for (size_t i = 0; i < 2 * n; i++)
+        if (!host_pairs[i] || (host_pairs[i] & 15u)) return set_err(e, HSW_ERR_INVALID_ARG, "cell address null or not 16-byte aligned");
+    DeviceScope ds(e->device);
+    if (!ds.ok) return set_err(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
+    if (!e->d_report) {
+        hipError_t h0 = hipMalloc((void **)&e->d_report, sizeof(hsw::VerifyReport));
+        if (h0 != hipSuccess) return set_err(e, HSW_ERR_NOMEM, "hipMalloc", h0);
+    }
+    const hsw::VerifyReport zero{0, ~0ull, 0};
+    hipError_t he = hipMemcpyAsync(d_pairs, host_pairs, n * sizeof(hsw::CellPair), hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(e->d_report, &zero, sizeof zero, hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) he = hipEventRecord(e->ev0, e->stream);
+    if (he == hipSuccess) he = hsw::launch_verify_pairs(static_cast<const hsw::CellPair *>(d_pairs), n, e->d_report, e->stream);
+    if (he == hipSuccess) he = hipEventRecord(e->ev1, e->stream);
+    hsw::VerifyReport got{};
+    if (he == hipSuccess) he = hipMemcpyAsync(&got, e->d_report, sizeof got, hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he == hipSuccess) he = hipEventElapsedTime(&report->kernel_ms, e->ev0, e->ev1);
+    e->timed = false;
+    if (he != hipSuccess) return set_err(e, HSW_ERR_HIP, "hsw_gadget_verify_ties", he);
+    report->violations = got.violations;
+    report->checks = n;
+    if (got.violations) report->first = got.first_key;
+    return HSW_OK;
+}
+
 extern "C" {
 
 int hsw_frame_structure(const hsw_shape *shape, size_t max_variable_byte_size, int is_input_range_check,

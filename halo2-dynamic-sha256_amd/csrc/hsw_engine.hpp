@@ -94,6 +94,9 @@ int hsw_verify_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n,
                            const uint32_t *d_pre_states, const uint32_t *d_next_states, const void *d_gate,
                            const void *d_lookup, const hsw_pack_plan *pack, uint32_t flags, hsw_verify_report *report,
                            const hsw::ContextPeriod *period);
+// n pairs of cells by device address (host_pairs: 2 n addresses, a0 b0 a1 b1 ...) through d_pairs, the caller's device
+// staging of 16 n bytes: upload, hsw_verify_pairs_kernel, the report read back.  Synchronous
+int hsw_verify_pairs_impl(hsw_engine *e, const uint64_t *host_pairs, void *d_pairs, size_t n, hsw_tie_report *report);
 
 // Makes the engine's device current for the scope of one call (a no-op when it already is: the usual case,
 // and these scopes nest three deep on the latency-critical path of a small digest).

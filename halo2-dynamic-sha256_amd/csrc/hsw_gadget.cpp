@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
+#include <iterator>
 #include <vector>
 #include <cstring>
 #include <new>
@@ -34,6 +35,7 @@ int hsw_verify_frames_impl(hsw_engine *e, const hsw_frame_desc *descs, size_t n,
                            const uint32_t *d_pre_states, const uint32_t *d_next_states, const void *d_gate,
                            const void *d_lookup, const hsw_pack_plan *pack, uint32_t flags, hsw_verify_report *report,
                            const hsw::ContextPeriod *period);
+int hsw_verify_pairs_impl(hsw_engine *e, const uint64_t *host_pairs, void *d_pairs, size_t n, hsw_tie_report *report);
 
 namespace hsw {
 
@@ -1147,6 +1149,53 @@ int Sha256DynamicConfig::digest_batch_device(Context &ctx, size_t n, const void 
 
 // ------------------------------------------------------------------- C ABI
 
+// The digest-to-digest copy constraints a device-fed batch adds (include/hsw.h, "ties").  The call has succeeded, so
+// its destinations are disjoint and an input overlaps a destination of the same call only if that one's level is
+// strictly lower: putting every destination of the call into the owner map first, then intersecting every message
+// with the map, sees exactly "a lower level of this call, or an earlier call of the pass".  O((n + ties) log n).
+void hsw_gadget::record_ties(size_t first, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                             const size_t *precomputed_input_lens, void *const *d_outputs) {
+    for (size_t i = 0; d_outputs && i < n; i++) {
+        if (!d_outputs[i]) continue;
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(d_outputs[i]), hi = lo + 32;
+        // what [lo, hi) covers of earlier runs goes: the run that begins below lo keeps its head, a run that ends
+        // after hi keeps its tail (from the output byte that lies at hi)
+        auto it = tie_owners.lower_bound(lo);
+        if (it != tie_owners.begin()) {
+            auto pv = std::prev(it);
+            const uintptr_t ps = pv->first, pe = ps + pv->second.len;
+            if (pe > lo) {
+                const TieOwner o = pv->second;
+                pv->second.len = lo - ps;
+                if (pe > hi) tie_owners.emplace(hi, TieOwner{pe - hi, o.hash, o.byte0 + (uint32_t)(hi - ps)});
+            }
+        }
+        while (it != tie_owners.end() && it->first < hi) {
+            const uintptr_t s = it->first, e = s + it->second.len;
+            const TieOwner o = it->second;
+            it = tie_owners.erase(it);
+            if (e > hi) { tie_owners.emplace(hi, TieOwner{e - hi, o.hash, o.byte0 + (uint32_t)(hi - s)}); break; }
+        }
+        tie_owners[lo] = TieOwner{32, (uint64_t)(first + i), 0};
+    }
+    if (tie_owners.empty()) return;
+    for (size_t i = 0; i < n; i++) {
+        if (!input_lens[i]) continue;
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(d_inputs[i]), hi = lo + input_lens[i];
+        const size_t pre = precomputed_input_lens ? precomputed_input_lens[i] : 0;
+        auto it = tie_owners.upper_bound(lo);                // the first run that ends after lo
+        if (it != tie_owners.begin() && std::prev(it)->first + std::prev(it)->second.len > lo) --it;
+        for (; it != tie_owners.end() && it->first < hi; ++it) {
+            const uintptr_t s = it->first > lo ? it->first : lo, e = it->first + it->second.len < hi ? it->first + it->second.len : hi;
+            for (uintptr_t a = s; a < e; a++) {
+                const size_t off = a - lo;                   // the byte's place in the message: input byte off - pre
+                if (off < pre) tie_prefix_bytes++;           // hashed on the host side of the circuit: no cell
+                else ties.push_back(Tie{it->second.hash, (uint64_t)(first + i), it->second.byte0 + (uint32_t)(a - it->first), (uint32_t)(off - pre)});
+            }
+        }
+    }
+}
+
 extern "C" {
 
 int hsw_digest_prepare(const uint8_t *input, size_t input_len, size_t precomputed_input_len,
@@ -1227,6 +1276,12 @@ int hsw_gadget_create_contexts(hsw_engine *e, const size_t *max_variable_byte_si
 
 void hsw_gadget_destroy(hsw_gadget *g) {
     if (!g) return;
+    if (g->d_pairs) {                                        // (every check that used it was synchronous)
+        int device = 0;
+        hsw_engine_stream(g->ctx->engine, nullptr, &device);
+        hsw::DeviceScopeG ds(device);
+        (void)hipFree(g->d_pairs);
+    }
     delete g->ctx;
     delete g;
 }
@@ -1264,6 +1319,8 @@ int hsw_gadget_digest_batch_device(hsw_gadget *g, size_t n, const void *const *d
     std::vector<hsw::AssignedHashResult> rs(n);
     const int rc = g->cfg.digest_batch_device(*g->ctx, n, d_inputs, input_lens, precomputed_input_lens, rs.data());
     if (rc != HSW_OK) return rc;
+    // (nothing to intersect without an earlier destination in the pass: no bookkeeping)
+    if (g->ctx->whole && !g->tie_owners.empty()) g->record_ties(g->results.size(), n, d_inputs, input_lens, precomputed_input_lens, nullptr);
     for (size_t i = 0; i < n; i++) {
         fill_result(rs[i], &results[i]);
         g->results.push_back(std::move(rs[i]));
@@ -1278,6 +1335,7 @@ int hsw_gadget_digest_levels_device(hsw_gadget *g, size_t n, const void *const *
     std::vector<hsw::AssignedHashResult> rs(n);
     const int rc = g->cfg.digest_levels_device(*g->ctx, n, d_inputs, input_lens, precomputed_input_lens, levels, d_outputs, rs.data());
     if (rc != HSW_OK) return rc;
+    if (g->ctx->whole && (d_outputs || !g->tie_owners.empty())) g->record_ties(g->results.size(), n, d_inputs, input_lens, precomputed_input_lens, d_outputs);
     for (size_t i = 0; i < n; i++) {
         fill_result(rs[i], &results[i]);
         g->results.push_back(std::move(rs[i]));
@@ -1479,6 +1537,7 @@ int hsw_gadget_reset(hsw_gadget *g) try {
     c.batches.clear();
     g->cfg.cur_hash_idx = 0;            // lib.rs:66
     g->results.clear();
+    g->tie_owners.clear(); g->ties.clear(); g->tie_prefix_bytes = 0;   // the ties are the pass's
     return HSW_OK;
 } HSW_NO_UNWIND
 
@@ -1774,6 +1833,7 @@ int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx) try {
     g->cfg.cur_hash_idx = hash_idx;
     c.batches.clear();
     g->results.clear();
+    g->tie_owners.clear(); g->ties.clear(); g->tie_prefix_bytes = 0;   // (digests assigned elsewhere: nothing to tie to)
     g->results.resize(hash_idx);        // keeps hash_idx -> result indexing of hsw_gadget_input_bytes
     return HSW_OK;
 } HSW_NO_UNWIND
@@ -1877,6 +1937,93 @@ int hsw_gadget_cell_position(const hsw_gadget *g, uint64_t cell, uint64_t *colum
     if (!g) return HSW_ERR_INVALID_ARG;
     g->ctx->layout.position(cell, column, row);
     return HSW_OK;
+} HSW_NO_UNWIND
+
+// ---- digest-to-digest copy constraints (include/hsw.h, "ties")
+
+// gate-stream cells of one recorded tie: the child's output-byte cell (hsw_gadget_result_cells), the parent's input-byte cell
+static void tie_cells(const hsw_gadget *g, const hsw_gadget::Tie &t, uint64_t *src_cell, uint64_t *dst_cell) {
+    const hsw::AssignedHashResult &s = g->results[(size_t)t.src_hash], &d = g->results[(size_t)t.dst_hash];
+    *src_cell = s.epilogue_cell + (uint64_t)hsw::frame::E_STATE * (s.n_blocks + 1) + (uint64_t)hsw::frame::E_WORD * (t.src_byte / 4) +
+                5u * (t.src_byte % 4);
+    *dst_cell = d.prologue_cell + hsw::frame::P_BYTES + t.dst_byte;
+}
+
+// a gate-stream cell some digest of this pass has been assigned (the pass order is the stream order)
+static bool cell_assigned(const hsw_gadget *g, uint64_t cell) {
+    const hsw::Context &c = *g->ctx;
+    if (!c.whole || c.batches.empty() || c.batches[0].first_digest >= g->results.size()) return false;
+    return cell >= g->results[c.batches[0].first_digest].prologue_cell && cell < c.gate_cursor;
+}
+
+static uint64_t cell_device_address(const hsw::Context &c, uint64_t cell) {
+    return (uint64_t)reinterpret_cast<uintptr_t>(c.d_gate) + c.cell_offset(cell) * HSW_CELL_BYTES;   // (pointer tables: modulo 2^64)
+}
+
+int hsw_gadget_ties(const hsw_gadget *g, hsw_cell_tie *out, size_t cap, size_t *n, uint64_t *prefix_bytes_untied) try {
+    if (!g) return HSW_ERR_INVALID_ARG;
+    if (!g->ctx->whole) return HSW_ERR_UNSUPPORTED;                  // block-stream contexts have no byte cells
+    if (n) *n = g->ties.size();
+    if (prefix_bytes_untied) *prefix_bytes_untied = g->tie_prefix_bytes;
+    if (!out) return HSW_OK;
+    if (cap < g->ties.size()) return HSW_ERR_TOO_LARGE;
+    for (size_t i = 0; i < g->ties.size(); i++) {
+        const hsw_gadget::Tie &t = g->ties[i];
+        hsw_cell_tie &o = out[i];
+        o.src_hash = t.src_hash; o.dst_hash = t.dst_hash; o.src_byte = t.src_byte; o.dst_byte = t.dst_byte;
+        tie_cells(g, t, &o.src_cell, &o.dst_cell);
+    }
+    return HSW_OK;
+} HSW_NO_UNWIND
+
+int hsw_gadget_cell_address(const hsw_gadget *g, uint64_t cell, void **d_cell) try {
+    if (!g || !d_cell) return HSW_ERR_INVALID_ARG;
+    if (!g->ctx->whole) return HSW_ERR_UNSUPPORTED;
+    if (!cell_assigned(g, cell)) return HSW_ERR_INVALID_ARG;
+    *d_cell = reinterpret_cast<void *>((uintptr_t)cell_device_address(*g->ctx, cell));
+    return HSW_OK;
+} HSW_NO_UNWIND
+
+// n pairs (cells[2 i], cells[2 i + 1]): every cell validated and resolved before anything is launched
+static int verify_pairs(hsw_gadget *g, size_t n, const std::vector<uint64_t> &cells, hsw_tie_report *report) {
+    hsw::Context &c = *g->ctx;
+    std::memset(report, 0, sizeof *report);
+    if (n == 0) return HSW_OK;
+    std::vector<uint64_t> addr(2 * n);
+    for (size_t i = 0; i < 2 * n; i++) {
+        const uint64_t cell = cells[i];
+        if (!cell_assigned(g, cell)) return hsw_engine_fail(c.engine, HSW_ERR_INVALID_ARG, "a cell out of range or not assigned in this pass");
+        addr[i] = cell_device_address(c, cell);
+    }
+    if (n > g->pairs_cap) {                                  // (every earlier check has been waited for: nothing reads the old one)
+        int device = 0;
+        hsw_engine_stream(c.engine, nullptr, &device);
+        hsw::DeviceScopeG ds(device);
+        if (!ds.ok) return HSW_ERR_NO_DEVICE;
+        void *p = nullptr;
+        const size_t cap = n > 2 * g->pairs_cap ? n : 2 * g->pairs_cap;
+        const hipError_t he = hipMalloc(&p, cap * 16);
+        if (he != hipSuccess) return hsw::hip_status(he);
+        (void)hipFree(g->d_pairs);
+        g->d_pairs = p; g->pairs_cap = cap;
+    }
+    return hsw_verify_pairs_impl(c.engine, addr.data(), g->d_pairs, n, report);
+}
+
+int hsw_gadget_verify_ties(hsw_gadget *g, hsw_tie_report *report) try {
+    if (!g || !report) return HSW_ERR_INVALID_ARG;
+    if (!g->ctx->whole) return HSW_ERR_UNSUPPORTED;
+    std::vector<uint64_t> cells(2 * g->ties.size());
+    for (size_t i = 0; i < g->ties.size(); i++) tie_cells(g, g->ties[i], &cells[2 * i], &cells[2 * i + 1]);
+    return verify_pairs(g, g->ties.size(), cells, report);
+} HSW_NO_UNWIND
+
+int hsw_gadget_verify_equal(hsw_gadget *g, const uint64_t *cells_a, const uint64_t *cells_b, size_t n, hsw_tie_report *report) try {
+    if (!g || !report || ((!cells_a || !cells_b) && n)) return HSW_ERR_INVALID_ARG;
+    if (!g->ctx->whole) return HSW_ERR_UNSUPPORTED;
+    std::vector<uint64_t> cells(2 * n);
+    for (size_t i = 0; i < n; i++) { cells[2 * i] = cells_a[i]; cells[2 * i + 1] = cells_b[i]; }
+    return verify_pairs(g, n, cells, report);
 } HSW_NO_UNWIND
 
 int hsw_gadget_set_repr(hsw_gadget *g, uint32_t repr) try {

@@ -21,6 +21,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <map>
 #include <vector>
 
 #include "../../include/hsw.h"
@@ -186,6 +187,17 @@ class Context {
     uint64_t column_cell(uint64_t c, uint64_t k) const {
         return by_pointer ? col_off[(size_t)(c * binding.columns_capacity + k)] : c * layout.image_cells() + k * layout.column_pitch();
     }
+    // cells from d_gate to gate-stream cell `cell` (whole-digest contexts) in the layout and binding in force, modulo
+    // 2^64: the linear stream, the image after its jumps, the owning Context's image, the caller's pitches or its
+    // own column pointer (hsw_gadget_cell_address)
+    uint64_t cell_offset(uint64_t cell) const {
+        const Layout &l = layout;
+        if (!l.max_rows) return cell;
+        if (!by_pointer) return l.image_cell(cell);
+        const uint64_t h = l.period ? cell / l.period : 0, local = cell - h * l.period;
+        const uint64_t at = local + l.origin_row + l.gap_at(local), P = l.column_pitch();
+        return column_cell(h, at / P) + at % P;
+    }
     // hsw_gadget_bind_column_tables: the lookup-advice column and / or the chip columns one allocation each as well (an
     // empty vector: that family keeps the pitch model).  lk_off[c] = cells from d_lookup (proof 0's column) to row 0
     // of proof c's; chip_dense_off / chip_spread_off[c * ncols + k] = cells from d_chip_dense / d_chip_spread (proof
@@ -288,6 +300,19 @@ struct hsw_gadget {
     hsw::Context *ctx = nullptr;
     std::vector<hsw::AssignedHashResult> results;   // one per digest so far (input_bytes kept for queries)
     hsw::RegionTape *tape = nullptr;                // built on first use, dropped when the layout changes
+    // Digest-to-digest copy constraints of the pass (hsw_gadget_ties; whole-digest gadgets).  tie_owners: the device
+    // bytes that hold a digest of the pass, as disjoint runs -- [start, start + len) holds output bytes byte0.. of
+    // digest `hash` -- a later destination replacing what it covers.  Host memory only; hsw_gadget_reset clears it
+    struct TieOwner { size_t len; uint64_t hash; uint32_t byte0; };
+    struct Tie { uint64_t src_hash, dst_hash; uint32_t src_byte, dst_byte; };
+    std::map<uintptr_t, TieOwner> tie_owners;
+    std::vector<Tie> ties;                          // in (dst_hash, dst_byte) order: digests and bytes are walked ascending
+    uint64_t tie_prefix_bytes = 0;                  // shared bytes inside a precomputed prefix: no cell, not tied
+    // the device-fed batch just committed as digests [first, first + n): its destinations, then its ties
+    void record_ties(size_t first, size_t n, const void *const *d_inputs, const size_t *input_lens,
+                     const size_t *precomputed_input_lens, void *const *d_outputs);
+    void *d_pairs = nullptr;                        // hsw_gadget_verify_ties / _equal: address pairs on the device,
+    size_t pairs_cap = 0;                           // grown on demand, freed by hsw_gadget_destroy
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

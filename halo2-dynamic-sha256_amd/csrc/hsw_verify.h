@@ -80,5 +80,10 @@ hipError_t launch_verify_frames(const FrameVerifyParams &p, size_t n_digests, hi
 hipError_t launch_verify_table(const VerifyParams &p, const PlaceTable &t, size_t n_blocks, hipStream_t stream);
 hipError_t launch_verify_frames_table(const FrameVerifyParams &p, const PlaceTable &t, size_t n_digests, hipStream_t stream);
 
+// hsw_verify_pairs_kernel: n pairs of 32-byte cells by device address (16-byte aligned), compared as stored.
+// report->violations counts the pairs that differ, report->first_key is the lowest failing index (~0 = none).
+struct CellPair { const void *a, *b; };
+hipError_t launch_verify_pairs(const CellPair *d_pairs, size_t n, VerifyReport *report, hipStream_t stream);
+
 }  // namespace hsw
 #endif

@@ -198,6 +198,28 @@ __global__ __launch_bounds__(256) void hsw_verify_frame_table_kernel(FrameVerify
 #include "hsw_verify_frame_body.inc"
 }
 
+// ---------------------------------------------------------------- copy constraints between any two cells
+// hsw_gadget_verify_ties / hsw_gadget_verify_equal: the host has resolved both cells of every pair to device addresses
+// (Context::cell_offset: layout, jumps, Context images, pitches and pointer tables are all in the address), so the
+// kernel knows no layout.  One lane per pair, each cell two 16-byte loads, compared as stored; a failing lane counts
+// itself and offers its index as the first.
+__global__ __launch_bounds__(256) void hsw_verify_pairs_kernel(const CellPair *pairs, u64 n, VerifyReport *report) {
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const CellPair pr = pairs[i];
+    const Cell a = load_cell(static_cast<const uint4 *>(pr.a), 0), b = load_cell(static_cast<const uint4 *>(pr.b), 0);
+    if (!same(a, b)) {
+        atomicAdd(reinterpret_cast<unsigned long long *>(&report->violations), 1ull);
+        atomicMin(reinterpret_cast<unsigned long long *>(&report->first_key), (unsigned long long)i);
+    }
+}
+
+hipError_t launch_verify_pairs(const CellPair *d_pairs, size_t n, VerifyReport *report, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(hsw_verify_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_pairs, (u64)n, report);
+    return hipGetLastError();
+}
+
 hipError_t launch_verify_frames_table(const FrameVerifyParams &p, const PlaceTable &t, size_t n_digests, hipStream_t stream) {
     if (n_digests == 0) return hipSuccess;
     if (t.cum_stride) {

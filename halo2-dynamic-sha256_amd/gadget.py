@@ -448,6 +448,46 @@ class Sha256DynamicConfig:
                     first_cell=int(rep.first_cell), first_class=N.VerifyReport.CLASSES.get(int(rep.first_class)),
                     kernel_ms=float(rep.kernel_ms))
 
+    def ties(self):
+        """hsw_gadget_ties: the digest-to-digest copy constraints of the pass -- (ties, prefix_bytes_untied), ties a
+        numpy structured array (src_hash, dst_hash, src_byte, dst_byte, src_cell, dst_cell) in (dst_hash, dst_byte)
+        order: the circuit adds constrain_equal(src_cell, dst_cell) for each."""
+        import numpy as np
+        dt = np.dtype([("src_hash", "<u8"), ("dst_hash", "<u8"), ("src_byte", "<u4"), ("dst_byte", "<u4"),
+                       ("src_cell", "<u8"), ("dst_cell", "<u8")])
+        n, pre = C.c_size_t(), C.c_uint64()
+        self._ok(self.lib.hsw_gadget_ties(self.h, None, 0, C.byref(n), C.byref(pre)))
+        out = np.zeros(n.value, dtype=dt)
+        if n.value:
+            self._ok(self.lib.hsw_gadget_ties(self.h, out.ctypes.data_as(C.POINTER(N.CellTie)), n.value, None, None))
+        return out, int(pre.value)
+
+    def cell_address(self, cell):
+        """hsw_gadget_cell_address: device address of a gate-stream cell in the layout and binding in force."""
+        p = C.c_void_p()
+        self._ok(self.lib.hsw_gadget_cell_address(self.h, int(cell), C.byref(p)))
+        return int(p.value or 0)
+
+    @staticmethod
+    def _tie_report(rep):
+        return dict(violations=int(rep.violations), checks=int(rep.checks), first=int(rep.first), kernel_ms=float(rep.kernel_ms))
+
+    def verify_ties(self):
+        """hsw_gadget_verify_ties: every recorded tie, cell against cell on the device."""
+        rep = N.TieReport()
+        self._ok(self.lib.hsw_gadget_verify_ties(self.h, C.byref(rep)))
+        return self._tie_report(rep)
+
+    def verify_equal(self, cells_a, cells_b):
+        """hsw_gadget_verify_equal: the caller's own constrain_equal pairs (gate-stream cells), compared as stored."""
+        a, b = [int(x) for x in cells_a], [int(x) for x in cells_b]
+        if len(a) != len(b):
+            raise ValueError("verify_equal takes as many cells on one side as on the other")
+        n = len(a)
+        rep = N.TieReport()
+        self._ok(self.lib.hsw_gadget_verify_equal(self.h, (C.c_uint64 * max(n, 1))(*a), (C.c_uint64 * max(n, 1))(*b), n, C.byref(rep)))
+        return self._tie_report(rep)
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

@@ -974,6 +974,50 @@ typedef struct hsw_result_cells {
     uint64_t output_byte_pos[32][2];
 } hsw_result_cells;
 int hsw_gadget_result_cells(const hsw_gadget *g, size_t hash_idx, hsw_result_cells *out);
+/* ---- digest-to-digest copy constraints ("ties") of a pass: HSW_GADGET_WHOLE_DIGEST gadgets (else HSW_ERR_UNSUPPORTED) ----
+ * hsw_block_structure / hsw_frame_structure give a replayer every copy constraint INSIDE a digest; what makes the
+ * digests of a pass a Merkle tree or a hash chain is one more family: input-byte cell k of a parent equals
+ * output-byte cell j of a child.  The gadget records them from what the device-fed calls were handed:
+ *   - every destination d_outputs[i] of hsw_gadget_digest_levels_device, with the digest that wrote it; a later write
+ *     of the same pass to the same bytes, in the same or a later call, replaces the earlier owner byte by byte;
+ *   - every device-fed message (either device-fed call) is intersected with the destinations written before it -- a
+ *     strictly lower level of the same call, any earlier call of the pass.  Every byte they share is one tie; partial
+ *     overlaps and destinations of any byte alignment give exactly the shared bytes.
+ * dst_byte indexes the digest's assigned input bytes (hsw_result_cells.input_bytes_cell0 + dst_byte), which start
+ * AFTER the precomputed prefix: dst_byte = offset in the message - precomputed_input_len.  A shared byte inside the
+ * prefix has no cell: it is not tied, it is counted in *prefix_bytes_untied.  Host-fed digests produce no ties.
+ * hsw_gadget_reset clears the record; nothing of it lives on the device.  The list is what the circuit adds as
+ * constrain_equal(src_cell, dst_cell); a caller that expects a tree asserts *n == 64 per inner node.
+ * hsw_gadget_ties: ties in (dst_hash, dst_byte) order.  *n (may be NULL) is always set; out = NULL only queries;
+ * cap < *n: HSW_ERR_TOO_LARGE, nothing written.  prefix_bytes_untied may be NULL.
+ * (The four calls below came under HSW_ABI_MINOR 1 like the device-fed calls: probe for the symbol.) */
+typedef struct hsw_cell_tie {
+    uint64_t src_hash, dst_hash;     /* digests in gadget order (a Context group: c*M + m) */
+    uint32_t src_byte, dst_byte;     /* output byte 0..31; index into input_bytes */
+    uint64_t src_cell, dst_cell;     /* gate-stream cells: hsw_result_cells.output_byte_cells[src_byte],
+                                        input_bytes_cell0 + dst_byte */
+} hsw_cell_tie;
+typedef struct hsw_tie_report {
+    uint64_t violations, checks, first; /* first: lowest failing index (valid if violations) */
+    float kernel_ms;
+} hsw_tie_report;
+int hsw_gadget_ties(const hsw_gadget *g, hsw_cell_tie *out, size_t cap, size_t *n, uint64_t *prefix_bytes_untied);
+/* Device address of gate-stream cell `cell` in the layout and binding in force -- what hsw_gadget_cell_position plus
+ * the binding's geometry give: the linear stream, a column image at its origin, a shared context after its jumps,
+ * proof c's image of HSW_GADGET_CONTEXT_IMAGES or a Context group, a pitch binding (hsw_gadget_bind_region), the
+ * caller's own column pointer (hsw_gadget_bind_columns / hsw_gadget_bind_column_tables) + row * 32.
+ * HSW_ERR_INVALID_ARG: a cell out of range or of a digest not yet assigned in this pass. */
+int hsw_gadget_cell_address(const hsw_gadget *g, uint64_t cell, void **d_cell);
+/* On-device check of the recorded ties (hsw_gadget_verify_ties) or of the caller's own constrain_equal pairs between
+ * any two assigned gate-stream cells (hsw_gadget_verify_equal: cells_a[i] against cells_b[i]), cell against cell in
+ * every layout and binding: the two cells of a pair are compared as stored -- 32 bytes, canonical or Montgomery, like
+ * the verifier's copies.  This is what hsw_gadget_verify does NOT see: it checks each digest against its own staging
+ * arrays, so a parent that hashed stale bytes (a slot no message writes, a nodes buffer overlapping something else,
+ * bytes changed between two calls of a pass) passes it and fails here.  checks = pairs compared; first = index of
+ * the lowest failing tie / pair.  n == 0 (no ties): no launch, checks = 0.  An invalid cell anywhere:
+ * HSW_ERR_INVALID_ARG before anything is launched.  Synchronous on the engine's stream. */
+int hsw_gadget_verify_ties(hsw_gadget *g, hsw_tie_report *report);
+int hsw_gadget_verify_equal(hsw_gadget *g, const uint64_t *cells_a, const uint64_t *cells_b, size_t n, hsw_tie_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */

@@ -246,6 +246,29 @@ pub struct hsw_verify_report {
     pub kernel_ms: f32,
 }
 
+/// One digest-to-digest copy constraint of a pass (`hsw_gadget_ties`): input-byte cell `dst_byte` of digest
+/// `dst_hash` equals output-byte cell `src_byte` of digest `src_hash`.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug, PartialEq, Eq)]
+pub struct hsw_cell_tie {
+    pub src_hash: u64,
+    pub dst_hash: u64,
+    pub src_byte: u32,
+    pub dst_byte: u32,
+    pub src_cell: u64,
+    pub dst_cell: u64,
+}
+
+/// Result of `hsw_gadget_verify_ties` / `hsw_gadget_verify_equal`.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_tie_report {
+    pub violations: u64,
+    pub checks: u64,
+    pub first: u64,
+    pub kernel_ms: f32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -504,6 +527,14 @@ extern "C" {
                                            input_lens: *const usize, precomputed_input_lens: *const usize,
                                            levels: *const u32, d_outputs: *const *mut c_void,
                                            results: *mut hsw_hash_result) -> c_int;
+    /// The digest-to-digest copy constraints the device-fed calls of this pass imply, in (dst_hash, dst_byte) order.
+    pub fn hsw_gadget_ties(g: *const hsw_gadget, out: *mut hsw_cell_tie, cap: usize, n: *mut usize,
+                           prefix_bytes_untied: *mut u64) -> c_int;
+    /// Device address of a gate-stream cell in the layout and binding in force.
+    pub fn hsw_gadget_cell_address(g: *const hsw_gadget, cell: u64, d_cell: *mut *mut c_void) -> c_int;
+    pub fn hsw_gadget_verify_ties(g: *mut hsw_gadget, report: *mut hsw_tie_report) -> c_int;
+    pub fn hsw_gadget_verify_equal(g: *mut hsw_gadget, cells_a: *const u64, cells_b: *const u64, n: usize,
+                                   report: *mut hsw_tie_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

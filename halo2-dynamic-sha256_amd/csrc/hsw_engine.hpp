@@ -113,4 +113,10 @@ struct DeviceScope {
     }
 };
 
+// The same from an engine, with the stream its work is issued on
+struct EngineScope : DeviceScope {
+    hipStream_t stream;
+    explicit EngineScope(const hsw_engine *e) : DeviceScope(e->device), stream(e->stream) {}
+};
+
 #endif

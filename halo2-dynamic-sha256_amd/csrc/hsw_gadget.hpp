@@ -16,6 +16,10 @@
 // output bytes :311-341) -- are emitted by a context created with
 // HSW_GADGET_WHOLE_DIGEST (hsw_frame.hpp / hsw_frame_kernel, assumption A4);
 // without it only their *values* are produced (AssignedHashResult).
+//
+// Implemented in four translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
+// call), hsw_gadget_context.cpp (Context: buffers, layouts, bind / unbind, the jump table), hsw_gadget_digest.cpp (the
+// digest paths and the ties) and hsw_gadget.cpp (the C ABI); hsw_gadget_launch.hpp is what only they share.
 #ifndef HSW_GADGET_HPP
 #define HSW_GADGET_HPP
 
@@ -43,6 +47,10 @@ struct DigestPlan {
 // refusals below (blocks and init_state are left alone).
 int digest_plan(size_t input_byte_size, size_t precomputed_input_len, size_t max_variable_byte_size, DigestPlan *plan);
 
+// sha2::compress256 (lib.rs:160) of one block on the host, and whether it runs on the x86 SHA extensions
+void plain_compress(uint32_t st[8], const uint8_t *block);
+bool host_sha_is_fast();
+
 // lib.rs:77-117,153-160.  Returns HSW_OK or the status the reference's
 // assert!/debug_assert! maps to (HSW_ERR_SHAPE / HSW_ERR_TOO_LARGE).
 int digest_prepare(const uint8_t *input, size_t input_byte_size, size_t precomputed_input_len,
@@ -56,13 +64,33 @@ struct AssignedHashResult {
     size_t first_block = 0;              // index of this hash's first block in the context's streams
     size_t n_blocks = 0;                 // max_variable_byte_size / 64
     uint64_t spread_cursor0 = 0;         // SpreadConfig.num_limb_sum when this digest started
-    size_t num_round = 0, target_round = 0;
+    size_t num_round = 0, target_round = 0, precomputed_round = 0;   // (precomputed_round: lib.rs:93, hashed outside the circuit)
     // whole-digest contexts: where the sections of this digest start (cells)
     uint64_t prologue_cell = 0, block_cell = 0, epilogue_cell = 0, end_cell = 0;
+    uint64_t zero_cell = ~0ull;          // the Context's zero cell, if this digest is the one that loads it (else ~0)
     uint64_t prologue_lookup = 0, block_lookup = 0, epilogue_lookup = 0;
 };
 
 class Context;
+
+// base + cells * cell_bytes, the offset taken modulo 2^64 as the kernels take it: a column given by pointer table may
+// lie below entry 0 of its table
+inline uint8_t *cell_ptr(const void *base, uint64_t cells, size_t cell_bytes = HSW_CELL_BYTES) {
+    return reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(base) + (uintptr_t)(cells * cell_bytes));
+}
+
+// The device jump table (Context::d_place, PlaceTable of hsw_kernels.h) in uint64 words, section by section:
+//   [jump cells n][cumulative gaps n -- by pointer table a row per Context][lookup shifts per digest, at least one word]
+//   and by pointer table too: [lookup rows K (PlaceTable::lk_row)][chip rows K * ncols * 2 (PlaceTable::chip_row)]
+// n = the layout's jumps -- by pointer table one more, jump 0 at stream cell 0.  Context::upload_place writes the table
+// through these offsets and Launch reads it through them
+struct PlaceWords {
+    size_t n = 0, cum = 0, shifts = 0, n_shifts = 0, lk_rows = 0, chip_rows = 0, total = 0;
+};
+
+// What a library-owned gadget holds (Context::owned), in cells: d_gate, d_lookup, each of d_chip_dense / d_chip_spread
+// (chip_stride rows in each of their columns, 0 for a gadget without blocks)
+struct OwnedCells { size_t image = 0, lookup = 0, chip = 0, chip_stride = 0; };
 
 class Sha256DynamicConfig {
   public:
@@ -108,7 +136,7 @@ class Sha256DynamicConfig {
     std::vector<std::pair<uint64_t, uint64_t>> load() const;
 
   private:
-    // what digest_batch and digest_batch_device share once the batch's blocks and pre-states are staged (hsw_gadget.cpp)
+    // what digest_batch and digest_batch_device share once the batch's blocks and pre-states are staged (hsw_gadget_digest.cpp)
     template <class Stage>
     int digest_tail(Context &ctx, size_t n, const size_t *input_lens, std::vector<DigestPlan> &plans, size_t batch_blocks,
                     bool host_chain, bool device_fed, Stage &&stage, AssignedHashResult *results);
@@ -167,6 +195,7 @@ class Context {
     size_t group_m = 0;
     size_t ctx_blocks = 0;                                     // blocks of one Context
     size_t contexts() const { return context_images ? init_capacity : group_m ? init_capacity / group_m : 1; }
+    size_t context_of(size_t d) const { return context_images ? d : group_m ? d / group_m : 0; }   // of digest d of the pass
     // hsw_gadget_bind_region: d_gate, d_lookup and the chip columns are the CALLER's memory -- never freed, grown,
     // zeroed or filled here -- at the caller's pitches: the image columns layout.pitch cells apart, and (K Contexts)
     // every Context's image, lookup column and chip rows in a place of its own: layout.image_pitch,
@@ -262,7 +291,26 @@ class Context {
     void *d_place = nullptr;                           // device copy of the jump table (hsw_kernels.h PlaceTable)
     size_t place_cap = 0;                              // uint64 words of d_place
     bool place_dirty = true;                           // the layout changed since the last upload
+    PlaceWords place_words() const;                    // where d_place's sections start, for the layout and binding in force
     int upload_place();                                // d_place from the layout, if it changed
+    OwnedCells owned(const Layout &l) const;
+    // the frame kernels' descriptor of digest d of the pass from its result: the generator and the verifier make it here
+    hsw_frame_desc frame_desc(const AssignedHashResult &r, size_t d, bool rc_inputs) const;
+    // The runs of the gate stream between two jumps, up to `cursor`, of every Context begun: fn(Context, lo, hi) with
+    // [lo, hi) in the Context's own stream cells (one Context: the pass's).  Each run lies in one image column
+    template <class Fn>
+    void for_each_run(uint64_t cursor, Fn &&fn) const {
+        const Layout &l = layout;
+        const uint64_t K = l.period ? (cursor + l.period - 1) / l.period : 1;
+        for (uint64_t h = 0; h < K; h++) {
+            const uint64_t end = !l.period ? cursor : cursor < (h + 1) * l.period ? cursor - h * l.period : l.period;
+            uint64_t lo = 0;
+            for (size_t k = 0; k <= l.break_cell.size() && lo < end; k++) {
+                const uint64_t hi = k < l.break_cell.size() && l.break_cell[k] < end ? l.break_cell[k] : end;
+                if (hi > lo) { fn(h, lo, hi); lo = hi; }
+            }
+        }
+    }
     // The layout this context would have with columns of `rows` cells (0: none) at the origin of *out, checked
     // against the limit of its kind (HSW_ERR_TOO_LARGE); decl: a shared context's declarations.  Touches nothing.
     int plan_layout(const std::vector<size_t> &sizes, bool rc_inputs, uint64_t rows, const std::vector<DigestOrigin> &decl,
@@ -308,6 +356,21 @@ struct hsw_gadget {
     std::map<uintptr_t, TieOwner> tie_owners;
     std::vector<Tie> ties;                          // in (dst_hash, dst_byte) order: digests and bytes are walked ascending
     uint64_t tie_prefix_bytes = 0;                  // shared bytes inside a precomputed prefix: no cell, not tied
+    // The cursors of a pass that starts at digest hash_idx (0: hsw_gadget_reset; else hsw_gadget_seek, the earlier
+    // digests assigned elsewhere): nothing recorded, nothing to verify or to tie to
+    void start_pass(size_t hash_idx, size_t blocks, uint64_t gate_cells, uint64_t lookup_cells) {
+        hsw::Context &c = *ctx;
+        c.blocks_done = blocks;
+        c.num_limb_sum = (uint64_t)blocks * c.shape.limb_calls_per_block;       // spread.rs:70-71, 228-231
+        c.gate_cursor = gate_cells;
+        c.lookup_cursor = lookup_cells;
+        c.zero_loaded = c.layout.origin_zero_loaded || hash_idx > 0;
+        c.batches.clear();
+        cfg.cur_hash_idx = hash_idx;            // lib.rs:66
+        results.clear();
+        results.resize(hash_idx);               // keeps hash_idx -> result indexing of hsw_gadget_input_bytes
+        tie_owners.clear(); ties.clear(); tie_prefix_bytes = 0;   // the ties are the pass's
+    }
     // the device-fed batch just committed as digests [first, first + n): its destinations, then its ties
     void record_ties(size_t first, size_t n, const void *const *d_inputs, const size_t *input_lens,
                      const size_t *precomputed_input_lens, void *const *d_outputs);

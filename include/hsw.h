@@ -376,7 +376,9 @@ int hsw_last_launch(const hsw_engine *e, hsw_launch_info *out);
  * Gadget front-end: the host side of Sha256DynamicConfig::digest
  * (reference src/lib.rs:71-349) -- SHA-256 padding, zero fill up to the
  * FIXED maximum size, prefix pre-hash, chaining, "select state #n" -- over
- * the engine.  csrc/hsw_gadget.hpp holds the C++ class of the same name.
+ * the engine.  csrc/hsw_gadget.hpp holds the C++ class of the same name
+ * (csrc/hsw_gadget_sha.cpp, _context.cpp, _digest.cpp; these entry points:
+ * csrc/hsw_gadget.cpp).
  * ------------------------------------------------------------------------ */
 
 typedef struct hsw_digest_info {

@@ -4,6 +4,10 @@
 // (no kernel runs: device cells stay zero), under ASan + UBSan + LeakSanitizer.  tests/test_layout_golden.py compares
 // the text with tests/golden/gadget_layouts.txt, recorded from the commit named there.
 // output_bytes of a result is not printed: without kernels it is whatever the pinned staging held.
+// With the argument `tables` it prints a second list instead -- the smallest gadgets that reach every form of the
+// device jump table (Context::place_host): the table's words, the binding, the context regions, the device offsets of
+// the cells around every jump and the delivered host cells, unbound, bound by pitch and bound by pointer table
+// (tests/golden/gadget_place_tables.txt).
 #include <hip/hip_runtime.h>
 
 #include <cinttypes>
@@ -13,7 +17,7 @@
 #include <initializer_list>
 #include <vector>
 
-#include "../../include/hsw.h"
+#include "../../halo2-dynamic-sha256_amd/csrc/hsw_gadget.hpp"   // (hsw.h + Context::upload_place / place_host)
 
 #define CHECK(cond)                                                        \
     do {                                                                   \
@@ -116,12 +120,11 @@ static void runs(const char *what, const std::vector<uint64_t> &cells) {
 }
 
 // hsw_gadget_download_region into exact-size buffers full of a sentinel: the cells it writes (zeros here)
-static void delivery(hsw_gadget *g, uint64_t n_images) {
+static void delivery_into(hsw_gadget *g, uint64_t gate_cells, uint64_t chip_stride) {
     hsw_gadget_view v;
     CHECK(hsw_gadget_streams(g, &v) == HSW_OK);
-    const uint64_t gate_cells = v.max_rows ? v.columns * v.max_rows * n_images : v.gate_capacity;
     std::vector<uint64_t> gate(gate_cells * 4, SENTINEL), lookup((v.lookup_capacity ? v.lookup_capacity : 1) * 4, SENTINEL);
-    std::vector<uint64_t> cd(2 * v.chip_col_stride * 4, SENTINEL), cs(2 * v.chip_col_stride * 4, SENTINEL);
+    std::vector<uint64_t> cd(2 * chip_stride * 4, SENTINEL), cs(2 * chip_stride * 4, SENTINEL);
     hsw_region_host dst = {gate.data(), v.d_lookup ? lookup.data() : nullptr, cd.data(), cs.data()};
     CHECK(hsw_gadget_download_region(g, &dst) == HSW_OK);
     runs("gate", gate);
@@ -129,6 +132,12 @@ static void delivery(hsw_gadget *g, uint64_t n_images) {
     runs("chip", cd);
     hsw_verify_report rep;
     CHECK(hsw_gadget_verify(g, &rep) == HSW_OK);                 // (the launch builder under the sanitizers; no kernel runs)
+}
+
+static void delivery(hsw_gadget *g, uint64_t n_images) {
+    hsw_gadget_view v;
+    CHECK(hsw_gadget_streams(g, &v) == HSW_OK);
+    delivery_into(g, v.max_rows ? v.columns * v.max_rows * n_images : v.gate_capacity, v.chip_col_stride);
 }
 
 static void context_regions(hsw_gadget *g, size_t k) {
@@ -289,8 +298,169 @@ static void pack_plans() {
     std::printf("pack plan 40 blocks of 131063 rows: rc %d\n", hsw_pack_plan_query(&s, 40, 0, 131063, &p));
 }
 
-int main() {
+
+// ---- the second list (`tables`): the device jump table in every form
+
+static uint64_t up4(uint64_t cells) { return (cells + 3) & ~3ull; }   // 128-byte lines
+enum Bind { UNBOUND, BY_PITCH, BY_COLUMNS, BY_TABLES };
+
+// Every column of one gadget out of ONE zeroed allocation, at fixed offsets (a table entry is an address difference:
+// two allocations would make it differ from run to run), the columns of a table in descending address order: column 1
+// lies below column 0, and the offsets are taken modulo 2^64
+struct Carved {
+    uint64_t *mem = nullptr;
+    std::vector<void *> img, lk, cd, cs;
+    hsw_region_binding b{};
+    ~Carved() { std::free(mem); }
+};
+
+static void bind(hsw_gadget *g, Bind how, size_t K, uint64_t pitch, Carved *s) {
+    hsw_region_binding need;
+    CHECK(hsw_gadget_region_binding(g, &need) == HSW_OK);
+    const uint64_t cols = need.columns_capacity, lk = need.lookup_capacity, rows = need.chip_rows_capacity;
+    const uint64_t col_slot = up4(pitch), lk_slot = up4(lk), chip_col = up4(rows + 1), chip_slot = 2 * chip_col;
+    const uint64_t o_lk = K * cols * col_slot, o_cd = o_lk + K * lk_slot, o_cs = o_cd + K * chip_slot, total = o_cs + K * chip_slot;
+    s->mem = static_cast<uint64_t *>(std::aligned_alloc(128, total * 32));
+    CHECK(s->mem);
+    std::memset(s->mem, 0, total * 32);
+    auto at = [&](uint64_t cell) { return static_cast<void *>(s->mem + 4 * cell); };
+    for (size_t i = 0; i < K * cols; i++) s->img.push_back(at((K * cols - 1 - i) * col_slot));
+    for (size_t i = 0; i < K; i++) s->lk.push_back(at(o_lk + (K - 1 - i) * lk_slot));
+    for (size_t i = 0; i < 2 * K; i++) {
+        s->cd.push_back(at(o_cd + (2 * K - 1 - i) * chip_col));
+        s->cs.push_back(at(o_cs + (2 * K - 1 - i) * chip_col));
+    }
+    // the pitch model: ascending, a Context per slot
+    s->b = hsw_region_binding{at(0), pitch, cols, cols * col_slot, at(o_lk), lk, lk_slot, at(o_cd), at(o_cs), rows + 1, rows, chip_slot};
+    if (how == BY_PITCH) CHECK(hsw_gadget_bind_region(g, &s->b) == HSW_OK);
+    if (how == BY_COLUMNS) CHECK(hsw_gadget_bind_columns(g, &s->b, s->img.data(), s->img.size()) == HSW_OK);
+    if (how == BY_TABLES) {
+        const hsw_column_tables t = {s->img.data(), s->img.size(), s->lk.data(), s->lk.size(), s->cd.data(), s->cs.data(), s->cd.size()};
+        CHECK(hsw_gadget_bind_column_tables(g, &s->b, &t) == HSW_OK);
+    }
+}
+
+static long long cells_between(const void *p, const void *from) {
+    return (long long)((intptr_t)p - (intptr_t)from) / (long long)HSW_CELL_BYTES;
+}
+
+static void place_table(hsw_gadget *g) {
+    CHECK(g->ctx->upload_place() == HSW_OK);
+    const std::vector<uint64_t> &w = g->ctx->place_host;
+    uint64_t sum = FNV0;
+    for (uint64_t x : w) sum = fnv(sum, {x});
+    std::printf("  place table: %zu words, sum %016llx\n   first", w.size(), (ull)sum);
+    for (size_t i = 0; i < w.size() && i < 8; i++) std::printf(" %llu", (ull)w[i]);
+    std::printf("\n   last");
+    for (size_t i = w.size() > 8 ? w.size() - 8 : 0; i < w.size(); i++) std::printf(" %llu", (ull)w[i]);
+    std::printf("\n");
+}
+
+// the binding in force: pointers as cells from the allocation the columns were carved from (unbound: from the view's)
+static void binding(hsw_gadget *g, const Carved *s) {
+    hsw_gadget_view v;
+    hsw_region_binding b;
+    CHECK(hsw_gadget_streams(g, &v) == HSW_OK && hsw_gadget_region_binding(g, &b) == HSW_OK);
+    std::printf("  binding: columns %+lld pitch %llu capacity %llu context_pitch %llu lookup %+lld capacity %llu pitch %llu "
+                "dense %+lld spread %+lld stride %llu rows %llu context_pitch %llu\n",
+                cells_between(b.d_columns, s ? s->mem : v.d_gate), (ull)b.column_pitch, (ull)b.columns_capacity, (ull)b.context_pitch,
+                cells_between(b.d_lookup, s ? s->mem : v.d_lookup), (ull)b.lookup_capacity, (ull)b.lookup_pitch,
+                cells_between(b.d_chip_dense, s ? s->mem : v.d_chip_dense), cells_between(b.d_chip_spread, s ? s->mem : v.d_chip_spread),
+                (ull)b.chip_col_stride, (ull)b.chip_rows_capacity, (ull)b.chip_context_pitch);
+}
+
+// hsw_gadget_cell_address, in cells from d_gate, of the first and the last assigned cell and of the two cells around
+// every jump of the map
+static void addresses(hsw_gadget *g) {
+    hsw_gadget_view v;
+    CHECK(hsw_gadget_streams(g, &v) == HSW_OK);
+    auto address = [&](uint64_t cell) {
+        void *p = nullptr;
+        CHECK(hsw_gadget_cell_address(g, cell, &p) == HSW_OK);
+        return cells_between(p, v.d_gate);
+    };
+    uint64_t pc = 0, pr = 0, sum = FNV0;
+    int n_jumps = 0;
+    std::printf("  address of cell 0: %+lld, of cell %llu: %+lld\n", address(0), (ull)(v.gate_cells - 1), address(v.gate_cells - 1));
+    for (uint64_t i = 0; i < v.gate_cells; i++) {
+        uint64_t c = 0, r = 0;
+        CHECK(hsw_gadget_cell_position(g, i, &c, &r) == HSW_OK);
+        if (i && !(c == pc && r == pr + 1)) {
+            std::printf("  jump before cell %llu: (%llu,%llu) %+lld -> (%llu,%llu) %+lld\n", (ull)i, (ull)pc, (ull)pr, address(i - 1),
+                        (ull)c, (ull)r, address(i));
+            sum = fnv(sum, {i, (uint64_t)address(i - 1), (uint64_t)address(i)});
+            n_jumps++;
+        }
+        if (i % 4099 == 0) sum = fnv(sum, {i, (uint64_t)address(i)});
+        pc = c; pr = r;
+    }
+    std::printf("  %d jumps; their addresses and every 4099th cell's: sum %016llx\n", n_jumps, (ull)sum);
+}
+
+// contexts: what hsw_gadget_context_region counts (0: the gadget has no such regions); n: digests of the pass
+static void table_case(const char *name, hsw_gadget *g, const std::vector<size_t> &sizes, size_t contexts, uint64_t rows, Bind how,
+                       bool with_interlude) {
+    std::printf("%s\n", name);
+    const size_t K = contexts ? contexts : 1;
+    uint64_t cols = 0;
+    CHECK(hsw_gadget_set_origin(g, 1, 33, 0, 5) == HSW_OK);
+    CHECK(hsw_gadget_set_columns(g, rows, &cols) == HSW_OK);
+    if (with_interlude) {                                         // digest 1 starts two columns after digest 0's last, 11 caller lookups
+        hsw_shape sh;
+        hsw_frame_shape fs;
+        uint64_t c = 0, r = 0;
+        CHECK(hsw_engine_shape(E, &sh) == HSW_OK && hsw_frame_query(&sh, sizes[0], 1, &fs) == HSW_OK);
+        CHECK(hsw_gadget_cell_position(g, fs.digest_cells, &c, &r) == HSW_OK);
+        CHECK(hsw_gadget_set_digest_origin(g, 1, c + 2, 41, 5 + fs.digest_lookups + 11) == HSW_OK);
+    }
+    const uint64_t pitch = rows + 128;
+    Carved s;
+    if (how != UNBOUND) bind(g, how, K, pitch, &s);
+    hsw_gadget_view v;
+    CHECK(hsw_gadget_streams(g, &v) == HSW_OK);
+    std::printf("  set_columns: %llu\n", (ull)cols);
+    digest(g, sizes, 0, sizes.size());
+    streams(g);
+    place_table(g);
+    binding(g, how != UNBOUND ? &s : nullptr);
+    context_regions(g, contexts);
+    addresses(g);
+    // host buffers: a pitch-bound image or chip column is delivered where it lies, every other one as an unbound gadget's
+    hsw_shape sh;
+    CHECK(hsw_engine_shape(E, &sh) == HSW_OK);
+    const uint64_t image = how == BY_PITCH ? (K - 1) * s.b.context_pitch + v.columns * pitch : K * v.columns * rows;
+    const uint64_t stride = how == BY_TABLES ? hsw_chip_rows(&sh, 0, v.capacity_blocks) : v.chip_col_stride;   // (by table: chip_col_stride is 0)
+    delivery_into(g, image, stride);
+    hsw_gadget_destroy(g);
+    for (uint64_t i = 0; s.mem && i < 4; i++) CHECK(s.mem[i] == 0);   // (launches do nothing here)
+}
+
+static void tables() {
+    hsw_shape sh;
+    CHECK(hsw_shape_query(8, 2, &sh) == HSW_OK);
+    const uint64_t rows = 2 * (uint64_t)sh.gate_cells_per_block + 100;   // every second block crosses a column
+    const std::vector<size_t> shared = {64, 128, 64}, image = {128, 64}, images(3, 128), group = {64, 128, 64, 128};
+    hsw_gadget *g = nullptr;
+    table_case("(a) shared context, an interlude, unbound", create(shared, 1, SHARED), shared, 0, rows, UNBOUND, true);
+    table_case("(b) shared context, an interlude, bound by pitch", create(shared, 1, SHARED), shared, 0, rows, BY_PITCH, true);
+    table_case("(c) plain image, columns by pointer table", create(image, 1, WHOLE), image, 0, rows, BY_COLUMNS, false);
+    table_case("(d) context images, K = 3, image, lookup and chip columns by pointer table", create(images, 1, IMAGES), images, 3, rows,
+               BY_TABLES, false);
+    for (Bind how : {UNBOUND, BY_TABLES}) {
+        CHECK(hsw_gadget_create_contexts(E, group.data(), 2, 2, 1, WHOLE, &g) == HSW_OK);
+        table_case(how == UNBOUND ? "(e) Context group, K = 2, M = 2, unbound" : "(f) Context group, K = 2, M = 2, all columns by pointer table",
+                   g, group, 2, rows, how, false);
+    }
+}
+
+int main(int argc, char **argv) {
     CHECK(hsw_engine_create_ex(0, nullptr, 8, 2, HSW_MODE_HALO2_INTERNALS, &E) == HSW_OK);
+    if (argc > 1 && std::strcmp(argv[1], "tables") == 0) {
+        tables();
+        hsw_engine_destroy(E);
+        std::puts("place table dump done");
+        return 0;
+    }
     const uint64_t origins[6][4] = {{0, 17, 0, 0}, {2, 131000, 0, 5}, {1, 40000, 1, 1234}, {0, MAX_ROWS - 1, 0, 0},
                                     {3, 1000, 1, 9}, {4, 69990, 0, 3}};
     plain("block stream", 0, {128, 64, 192}, 0, false, nullptr, 0);

@@ -43,7 +43,8 @@ def host_objects(tmp_path_factory):
     if not all(os.path.exists(k) for k in kernels):
         subprocess.check_call(["make", "-C", CSRC, "-s", "-j8"])
     out = str(tmp_path_factory.mktemp("san"))
-    objs = [_compile(hipcc, os.path.join(CSRC, f), out) for f in ("hsw_api.cpp", "hsw_api_region.cpp", "hsw_gadget.cpp", "hsw_gadget_layout.cpp", "hsw_replay.cpp", "hsw_devmem.cpp")]
+    objs = [_compile(hipcc, os.path.join(CSRC, f), out) for f in ("hsw_api.cpp", "hsw_api_region.cpp", "hsw_gadget.cpp", "hsw_gadget_sha.cpp", "hsw_gadget_context.cpp", "hsw_gadget_digest.cpp",
+                                                                     "hsw_gadget_layout.cpp", "hsw_replay.cpp", "hsw_devmem.cpp")]
     objs.append(_compile(hipcc, os.path.join(ROOT, "tests", "cpp", "hip_stub.cpp"), out))     # the only HIP runtime linked
     return hipcc, out, objs, kernels
 

@@ -212,6 +212,28 @@ class TieReport(C.Structure):
     _fields_ = [("violations", C.c_uint64), ("checks", C.c_uint64), ("first", C.c_uint64), ("kernel_ms", C.c_float)]
 
 
+HSW_LOOKUP_RANGE, HSW_LOOKUP_SPREAD = 0, 1
+HSW_LOOKUP_ACCUMULATE = 1
+
+
+class LookupRun(C.Structure):
+    """hsw_lookup_run: n lookup entries of proof `context` as consecutive device cells (hsw_gadget_lookup_runs)."""
+    _fields_ = [("context", C.c_uint64), ("table", C.c_uint32), ("column", C.c_uint32), ("first", C.c_uint64), ("n", C.c_uint64),
+                ("d_cells", C.c_void_p), ("d_spread", C.c_void_p)]
+
+
+class LookupCounts(C.Structure):
+    """hsw_lookup_counts: the caller's per-proof multiplicity tables (hsw_gadget_lookup_multiplicities)."""
+    _fields_ = [("d_range", C.c_void_p), ("d_spread", C.c_void_p), ("range_pitch", C.c_uint64), ("spread_pitch", C.c_uint64),
+                ("flags", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class LookupReport(C.Structure):
+    _fields_ = [("range_entries", C.c_uint64), ("spread_entries", C.c_uint64), ("not_in_table", C.c_uint64),
+                ("first_context", C.c_uint64), ("first_entry", C.c_uint64), ("first_table", C.c_uint32), ("first_column", C.c_uint32),
+                ("kernel_ms", C.c_float), ("reserved_", C.c_uint32)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -233,6 +255,7 @@ SYMBOLS = (
     "hsw_gadget_bind_region", "hsw_gadget_region_binding", "hsw_gadget_bind_columns", "hsw_gadget_bind_column_tables",
     "hsw_gadget_digest_batch_device", "hsw_gadget_digest_levels_device",
     "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
+    "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities",
 )
 
 
@@ -323,6 +346,11 @@ def lib():
             L.hsw_gadget_verify_ties.argtypes = [vp, C.POINTER(TieReport)]
             L.hsw_gadget_verify_equal.restype = C.c_int
             L.hsw_gadget_verify_equal.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(TieReport)]
+        if hasattr(L, "hsw_gadget_lookup_runs"):   # absent only in A/B builds of an earlier commit (HSW_LIB_OVERRIDE)
+            L.hsw_gadget_lookup_runs.restype = C.c_int
+            L.hsw_gadget_lookup_runs.argtypes = [vp, C.POINTER(LookupRun), C.c_size_t, C.POINTER(C.c_size_t)]
+            L.hsw_gadget_lookup_multiplicities.restype = C.c_int
+            L.hsw_gadget_lookup_multiplicities.argtypes = [vp, C.POINTER(LookupCounts), C.POINTER(LookupReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

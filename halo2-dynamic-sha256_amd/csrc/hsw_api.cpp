@@ -290,6 +290,11 @@ int hsw_engine_set_option(hsw_engine *e, const char *name, int64_t value) try {
         e->verify_slices = (int)value;
         return HSW_OK;
     }
+    if (std::strcmp(name, "lookup_lds") == 0) {        // hsw_gadget_lookup_multiplicities: 0 = every table by global atomics
+        if (value < 0 || value > 1) return set_err(e, HSW_ERR_INVALID_ARG, "lookup_lds must be 0 or 1 (default)");
+        e->lookup_lds = (int)value;
+        return HSW_OK;
+    }
     if (std::strcmp(name, "chunk_blocks") == 0) {      // blocks per launch of a long batch; tests shrink it to reach that loop
         if (value < 1 || value > (1 << 20)) return set_err(e, HSW_ERR_INVALID_ARG, "chunk_blocks must be 1 .. 2^20");
         e->chunk_blocks = (size_t)value;

@@ -89,9 +89,10 @@ int hsw_gadget_create_contexts(hsw_engine *e, const size_t *max_variable_byte_si
 
 void hsw_gadget_destroy(hsw_gadget *g) {
     if (!g) return;
-    if (g->d_pairs) {                                        // (every check that used it was synchronous)
+    if (g->d_pairs || g->d_lookup_runs) {                    // (every check and count that used them was synchronous)
         EngineScope es(g->ctx->engine);
         (void)hipFree(g->d_pairs);
+        (void)hipFree(g->d_lookup_runs);
     }
     delete g->ctx;
     delete g;

@@ -17,9 +17,10 @@
 // HSW_GADGET_WHOLE_DIGEST (hsw_frame.hpp / hsw_frame_kernel, assumption A4);
 // without it only their *values* are produced (AssignedHashResult).
 //
-// Implemented in four translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
+// Implemented in five translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
 // call), hsw_gadget_context.cpp (Context: buffers, layouts, bind / unbind, the jump table), hsw_gadget_digest.cpp (the
-// digest paths and the ties) and hsw_gadget.cpp (the C ABI); hsw_gadget_launch.hpp is what only they share.
+// digest paths and the ties), hsw_gadget_lookup.cpp (the lookup entries of a pass, listed and counted) and
+// hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
 #ifndef HSW_GADGET_HPP
 #define HSW_GADGET_HPP
 
@@ -376,6 +377,8 @@ struct hsw_gadget {
                      const size_t *precomputed_input_lens, void *const *d_outputs);
     void *d_pairs = nullptr;                        // hsw_gadget_verify_ties / _equal: address pairs on the device,
     size_t pairs_cap = 0;                           // grown on demand, freed by hsw_gadget_destroy
+    void *d_lookup_runs = nullptr;                  // hsw_gadget_lookup_multiplicities (hsw_gadget_lookup.cpp): its report, run
+    size_t lookup_runs_cap = 0;                     // table and zero lists on the device, in bytes; grown and freed like d_pairs
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

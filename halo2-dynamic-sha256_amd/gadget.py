@@ -488,6 +488,64 @@ class Sha256DynamicConfig:
         self._ok(self.lib.hsw_gadget_verify_equal(self.h, (C.c_uint64 * max(n, 1))(*a), (C.c_uint64 * max(n, 1))(*b), n, C.byref(rep)))
         return self._tie_report(rep)
 
+    def lookup_runs(self):
+        """hsw_gadget_lookup_runs: the lookup entries the digests of this pass have written, as runs of device cells --
+        a list of dicts (context, table, column, first, n, d_cells, d_spread) in (context, table, column, first) order;
+        table is HSW_LOOKUP_RANGE (lookup-advice column) or HSW_LOOKUP_SPREAD (chip column `column`)."""
+        n = C.c_size_t()
+        self._ok(self.lib.hsw_gadget_lookup_runs(self.h, None, 0, C.byref(n)))
+        out = (N.LookupRun * max(n.value, 1))()
+        if n.value:
+            self._ok(self.lib.hsw_gadget_lookup_runs(self.h, out, n.value, None))
+        return [dict(context=int(r.context), table=int(r.table), column=int(r.column), first=int(r.first), n=int(r.n),
+                     d_cells=int(r.d_cells or 0), d_spread=int(r.d_spread or 0)) for r in out[: n.value]]
+
+    def _lookup_contexts(self):
+        return self.n_contexts if self.n_contexts is not None else len(self.max_variable_byte_sizes) if self.context_images else 1
+
+    def lookup_multiplicities(self, range=True, spread=True, out_range=None, out_spread=None, accumulate=False):
+        """hsw_gadget_lookup_multiplicities: how often every row of the 2^16-row range table and of the
+        2^num_bits_lookup-row spread table is used by every proof of the pass, counted on the device.  Returns
+        (range, spread, report): two int32 device tensors of shape (contexts, pitch) -- None for a table not asked for
+        -- and the report as a dict.  out_range / out_spread: the caller's own tensors (contiguous int32 on the
+        engine's device, (contexts, pitch) with pitch >= the table size), counted into; with accumulate the counters
+        grow instead of being zeroed first.  A prover adds usable_rows - entries to row 0 of each table itself."""
+        import torch
+        k, dev = self._lookup_contexts(), self.engine.device
+        want = (("range", range, out_range, 1 << 16), ("spread", spread, out_spread, 1 << int(self.engine.shape.num_bits_lookup)))
+        if not (range or spread):
+            raise ValueError("lookup_multiplicities: neither table asked for")
+        tensors = []
+        for name, on, t, rows in want:                     # everything checked before the library is called
+            if not on:
+                if t is not None:
+                    raise ValueError("out_%s given for a table that is not asked for" % name)
+                tensors.append(None)
+                continue
+            if t is None:
+                if accumulate:
+                    raise ValueError("accumulate needs the caller's own out_%s" % name)
+                tensors.append((name, rows))
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+                raise ValueError("out_%s must be an int32 tensor" % name)
+            if t.device != dev:
+                raise ValueError("out_%s must live on %s" % (name, dev))
+            if t.dim() != 2 or t.shape[0] != k or t.shape[1] < rows or not t.is_contiguous():
+                raise ValueError("out_%s must be contiguous, of shape (%d, pitch >= %d)" % (name, k, rows))
+            tensors.append(t)
+        tensors = [torch.zeros((k, t[1]), dtype=torch.int32, device=dev) if isinstance(t, tuple) else t for t in tensors]
+        r, s = tensors
+        args = N.LookupCounts(r.data_ptr() if r is not None else None, s.data_ptr() if s is not None else None,
+                              r.shape[1] if r is not None else 0, s.shape[1] if s is not None else 0,
+                              N.HSW_LOOKUP_ACCUMULATE if accumulate else 0, 0)
+        rep = N.LookupReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the count runs on the engine's
+        self._ok(self.lib.hsw_gadget_lookup_multiplicities(self.h, C.byref(args), C.byref(rep)))
+        return r, s, dict(range_entries=int(rep.range_entries), spread_entries=int(rep.spread_entries),
+                          not_in_table=int(rep.not_in_table), first_context=int(rep.first_context), first_entry=int(rep.first_entry),
+                          first_table=int(rep.first_table), first_column=int(rep.first_column), kernel_ms=float(rep.kernel_ms))
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

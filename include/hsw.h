@@ -1020,6 +1020,66 @@ int hsw_gadget_cell_address(const hsw_gadget *g, uint64_t cell, void **d_cell);
  * HSW_ERR_INVALID_ARG before anything is launched.  Synchronous on the engine's stream. */
 int hsw_gadget_verify_ties(hsw_gadget *g, hsw_tie_report *report);
 int hsw_gadget_verify_equal(hsw_gadget *g, const uint64_t *cells_a, const uint64_t *cells_b, size_t n, hsw_tie_report *report);
+/* ---- lookup-table multiplicities of a pass, counted on the device ----
+ * The gadget's two lookup arguments, and what a prover needs first for either (halo2's permuted A'/S' pair or a logUp
+ * sum): how often each table row is used by each proof.
+ *   HSW_LOOKUP_RANGE   every entry the gadget queues into the lookup-advice column is a value below 2^16 (range_check
+ *                      limbs, bytes, byte * 2^8): a row of the 2^16-row range table;
+ *   HSW_LOOKUP_SPREAD  every (dense, spread) pair of the chip columns is row `dense` of the 2^num_bits_lookup-row
+ *                      spread table (hsw_spread_table); the lookup has no selector: every row of every chip column.
+ * hsw_gadget_lookup_runs LISTS the entries as runs of device cells (host only, no launch), exactly what the digests
+ * committed so far in this pass have written, in (context, table, column, first) order:
+ *   RANGE   one run per committed digest (its prologue, block and epilogue lookups are contiguous), neighbours merged
+ *           where nothing of the caller's lies between them.  Never in a run: the caller's entries below
+ *           lookups_queued / origin_lookups, the interlude entries of a shared context or Context group, anything of
+ *           a proof that has not been digested.  A gadget without a lookup column (no HSW_GADGET_WHOLE_DIGEST) lists none;
+ *   SPREAD  one run per (Context, chip column): column k holds the committed limb calls n = k (mod num_advice_columns),
+ *           so with 3 columns the runs of one Context differ in length.
+ * Addresses are those of the layout and binding in force (linear streams, column images, shared contexts, context
+ * images, Context groups, hsw_gadget_bind_region pitches, hsw_gadget_bind_column_tables pointers).  *n (may be NULL)
+ * is always set; out = NULL only queries; cap < *n: HSW_ERR_TOO_LARGE, nothing written.  hsw_gadget_reset empties it.
+ * hsw_gadget_lookup_multiplicities COUNTS them (hsw_lookup_counts_kernel) into the caller's tables:
+ *   d_range[c * range_pitch + t]   = listed RANGE entries of proof c whose value is t;
+ *   d_spread[c * spread_pitch + t] = listed chip rows of proof c with dense == t and spread == spread(t);
+ * with HSW_LOOKUP_ACCUMULATE the counters grow by that, else the tables of the Contexts that have at least one run
+ * are zeroed first (2^16 / 2^num_bits_lookup counters each, not `pitch`) and no other counter is touched.  An entry is
+ * in its table only if the WHOLE 32-byte cell (reduced from Montgomery form where the cells are HSW_REPR_MONTGOMERY)
+ * equals a table row: a cell whose low limb fits and whose upper limbs are not zero is counted in not_in_table and in
+ * no counter, so per proof sum(counts) + its share of not_in_table = its listed entries.  The counters are the only
+ * caller memory written.  Unassigned rows are the caller's: halo2 looks (0, 0) up there, so a prover adds
+ * usable_rows - entries to row 0 of each table.  Synchronous on the engine's stream; an empty list is HSW_OK, a zero
+ * report and no launch.  HSW_ERR_INVALID_ARG before any launch: both table pointers NULL, a pitch below the table
+ * size, a counter pointer not 4-byte aligned.  HSW_ERR_UNSUPPORTED: d_range on a gadget without a lookup column,
+ * HSW_REPR_COMPACT64 cells, a pass whose batches differ in representation.
+ * (Both calls came under HSW_ABI_MINOR 1: probe for the symbol.) */
+#define HSW_LOOKUP_RANGE 0u
+#define HSW_LOOKUP_SPREAD 1u
+#define HSW_LOOKUP_ACCUMULATE 1u      /* add to what the tables hold instead of zeroing the proofs' tables first */
+typedef struct hsw_lookup_run {
+    uint64_t context;      /* proof (Context) index; 0 for a single-Context gadget */
+    uint32_t table;        /* HSW_LOOKUP_RANGE = 0 (lookup-advice column, 2^16 rows) | HSW_LOOKUP_SPREAD = 1 */
+    uint32_t column;       /* chip column k for SPREAD, 0 for RANGE */
+    uint64_t first;        /* RANGE: entry index in the proof's lookup column; SPREAD: the column's first row of this run */
+    uint64_t n;            /* entries (cells of d_cells; for SPREAD also of d_spread) */
+    void *d_cells;         /* device address of the first cell (RANGE: the entry; SPREAD: the dense cell) */
+    void *d_spread;        /* SPREAD: the spread cell of the same row; NULL for RANGE */
+} hsw_lookup_run;
+int hsw_gadget_lookup_runs(const hsw_gadget *g, hsw_lookup_run *out, size_t cap, size_t *n);
+typedef struct hsw_lookup_counts {
+    uint32_t *d_range;     /* contexts x range_pitch u32, proof-major; counter t of proof c at c*range_pitch + t; NULL = skip */
+    uint32_t *d_spread;    /* contexts x spread_pitch u32; NULL = skip */
+    uint64_t range_pitch;  /* >= 65536;              0 = 65536 */
+    uint64_t spread_pitch; /* >= 2^num_bits_lookup;  0 = 2^num_bits_lookup */
+    uint32_t flags, reserved_;
+} hsw_lookup_counts;
+typedef struct hsw_lookup_report {
+    uint64_t range_entries, spread_entries;   /* entries looked at, per table */
+    uint64_t not_in_table;                    /* entries that are no row of their table; they are counted nowhere else */
+    uint64_t first_context, first_entry;      /* the lowest failing entry in (context, table, column, entry) order */
+    uint32_t first_table, first_column;
+    float kernel_ms; uint32_t reserved_;
+} hsw_lookup_report;
+int hsw_gadget_lookup_multiplicities(hsw_gadget *g, const hsw_lookup_counts *out, hsw_lookup_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */
@@ -1046,7 +1106,9 @@ int hsw_fill_calibrate(hsw_engine *e, void *d_buf, size_t bytes, float *ms);
  * "mont_emit": where Montgomery cells of the streaming kernel are converted (8-bit table only) -- 0 = at
  * write-out always, 1 = at emit time for default-mode launches of 1,536 blocks or more (default; fewer VALU
  * instructions than the canonical kernel, but one wave per block), 2 = at emit time always (also internals mode).
- * "chunk_blocks": blocks per kernel launch of a long batch (default and maximum 2^20; a test knob). */
+ * "chunk_blocks": blocks per kernel launch of a long batch (default and maximum 2^20; a test knob).
+ * "lookup_lds": hsw_gadget_lookup_multiplicities counts tables of up to 2^11 rows in LDS first (1, default) or every
+ * table by global atomics (0; a measuring knob). */
 int hsw_engine_set_option(hsw_engine *e, const char *name, int64_t value);
 
 const char *hsw_strerror(int status);

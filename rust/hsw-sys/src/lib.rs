@@ -269,6 +269,53 @@ pub struct hsw_tie_report {
     pub kernel_ms: f32,
 }
 
+pub const HSW_LOOKUP_RANGE: u32 = 0;
+pub const HSW_LOOKUP_SPREAD: u32 = 1;
+/// `hsw_lookup_counts.flags`: add to what the tables hold instead of zeroing the proofs' tables first.
+pub const HSW_LOOKUP_ACCUMULATE: u32 = 1;
+
+/// `n` lookup entries of proof `context` as consecutive device cells (`hsw_gadget_lookup_runs`): entries of the
+/// lookup-advice column (`HSW_LOOKUP_RANGE`, `d_spread` null) or rows of chip column `column` (`HSW_LOOKUP_SPREAD`).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_lookup_run {
+    pub context: u64,
+    pub table: u32,
+    pub column: u32,
+    pub first: u64,
+    pub n: u64,
+    pub d_cells: *mut c_void,
+    pub d_spread: *mut c_void,
+}
+
+/// The caller's per-proof multiplicity tables (`hsw_gadget_lookup_multiplicities`): `contexts x pitch` u32 counters
+/// each, a null table is skipped, a pitch of 0 is the table size.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_lookup_counts {
+    pub d_range: *mut u32,
+    pub d_spread: *mut u32,
+    pub range_pitch: u64,
+    pub spread_pitch: u64,
+    pub flags: u32,
+    pub reserved_: u32,
+}
+
+/// Result of `hsw_gadget_lookup_multiplicities`.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_lookup_report {
+    pub range_entries: u64,
+    pub spread_entries: u64,
+    pub not_in_table: u64,
+    pub first_context: u64,
+    pub first_entry: u64,
+    pub first_table: u32,
+    pub first_column: u32,
+    pub kernel_ms: f32,
+    pub reserved_: u32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -535,6 +582,12 @@ extern "C" {
     pub fn hsw_gadget_verify_ties(g: *mut hsw_gadget, report: *mut hsw_tie_report) -> c_int;
     pub fn hsw_gadget_verify_equal(g: *mut hsw_gadget, cells_a: *const u64, cells_b: *const u64, n: usize,
                                    report: *mut hsw_tie_report) -> c_int;
+    /// The lookup entries the digests of this pass have written, as runs of device cells in (context, table,
+    /// column, first) order; host only.
+    pub fn hsw_gadget_lookup_runs(g: *const hsw_gadget, out: *mut hsw_lookup_run, cap: usize, n: *mut usize) -> c_int;
+    /// Counts the listed entries into the caller's per-proof multiplicity tables on the device; synchronous.
+    pub fn hsw_gadget_lookup_multiplicities(g: *mut hsw_gadget, out: *const hsw_lookup_counts,
+                                            report: *mut hsw_lookup_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

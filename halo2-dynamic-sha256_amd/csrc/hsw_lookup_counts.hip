@@ -4,7 +4,8 @@
 // (hsw_gadget_lookup_runs: every layout, image, pitch and pointer table is in the addresses), so the kernel knows no
 // layout -- like hsw_verify_pairs_kernel it is handed addresses.  A work item is `chunk` consecutive entries of one
 // run, one workgroup each: one long run and many short ones fill the chip alike.  A lane loads its cell as two
-// 16-byte pieces (a spread row: the dense and the spread cell), reduces a Montgomery cell to its value, decides
+// 16-byte pieces (a spread row: the dense and the spread cell), reduces a Montgomery cell to its value (a stored
+// encoding >= p is no cell of the field and hence no table row), decides
 // whether the WHOLE 32-byte value is a row of its table, and counts it.  A table of up to LOOKUP_LDS_BINS rows (the
 // spread table of up to 11 bits) is counted in an LDS histogram per workgroup that is flushed with one global atomic
 // per non-zero bin; a 2^16-row table (the range table always, the 16-bit spread table) does not fit a workgroup's
@@ -61,6 +62,11 @@ DEV Cell from_mont(const Cell &a) {
     return r;
 }
 DEV bool narrow(const Cell &c) { return (c.l[1] | c.l[2] | c.l[3]) == 0; }
+DEV bool geq_p(const Cell &a) {
+    const u64 P[4] = {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull};
+    for (int i = 3; i >= 0; i--) { if (a.l[i] > P[i]) return true; if (a.l[i] < P[i]) return false; }
+    return true;
+}
 // spread.rs:169-189 for a dense value below 2^16: bit b of t at bit 2 b
 DEV u32 spread_of(u32 t) {
     t = (t | (t << 8)) & 0x00ff00ffu;
@@ -113,8 +119,11 @@ __global__ __launch_bounds__(256) void hsw_lookup_counts_kernel(LookupCountParam
             bool ok = false;
             u32 t = 0;
             if (active) {
+                // a Montgomery cell is an encoding m < p: m + p reduces to the same value, and is no table row (decided
+                // before the reduction, which is the last use of the stored limbs)
+                const bool enc = !MONT || !(geq_p(d[u]) || (is_spread && geq_p(s[u])));
                 const Cell v = MONT ? from_mont(d[u]) : d[u];
-                ok = narrow(v) && v.l[0] < rows;
+                ok = enc && narrow(v) && v.l[0] < rows;
                 t = (u32)v.l[0];
                 if (ok && is_spread) {
                     const Cell w = MONT ? from_mont(s[u]) : s[u];

@@ -92,7 +92,7 @@
         const u64 l0 = quad64(x.l[0], 0), l1 = quad64(x.l[0], 1), l2 = quad64(x.l[0], 2), l3 = quad64(x.l[0], 3);
         const u64 up = x.l[1] | x.l[2] | x.l[3];        // 0 <=> this cell is narrow
         const u64 up0 = quad64(up, 0), up1 = quad64(up, 1), up2 = quad64(up, 2), up3 = quad64(up, 3);
-        bool ok;
+        bool ok, general = false;
         if ((up0 | up1 | up2 | up3) == 0) {
             const unsigned __int128 s128 = (unsigned __int128)l1 * l2 + l0;
             ok = (u64)(s128 >> 64) == 0 && (u64)s128 == l3;
@@ -103,18 +103,35 @@
             const u64 a = P0 - l1;                                            // x1 = p - a
             ok = (up0 | up2 | up3) == 0 && l2 == 1 && x11 == P1 && x12 == P2 && x13 == P3 && a >= 1 && a <= 0x55555555ull &&
                  l0 >= a && l0 - a == l3;
+            general = !ok;                                                    // (the same in all four lanes of the quad)
         }
-        if (act && !ok && j4 == 0) fail(VERIFY_GATE_ROW, c);
-        // ---- this lane's cell
+        // ---- this lane's cell (reported below, after the row)
+        bool enc_bad = false;
+        u32 own = 0;
         if constexpr (MONT)            // a Montgomery cell is an encoding m < p: m + p reduces to the same value and would pass everything below
-            if (act && geq_p(raw)) fail(VERIFY_RANGE, cell);
+            enc_bad = act && geq_p(raw);
         if (act) {
-            if (k == 1) { if (!same(x, small((u64)rf))) fail(VERIFY_CONSTANT, cell); }
+            if (k == 1) { if (!same(x, small((u64)rf))) own = VERIFY_CONSTANT; }
             else if (k == 2) {
-                if (rf >= 0) { if (!same(raw, w)) fail(VERIFY_COPY, cell); }
-                else { bool known; const Cell e = cell_of(rf, known); if (known && !same(x, e)) fail(VERIFY_COPY, cell); }
+                if (rf >= 0) { if (!same(raw, w)) own = VERIFY_COPY; }
+                else { bool known; const Cell e = cell_of(rf, known); if (known && !same(x, e)) own = VERIFY_COPY; }
             }
         }
+        if (general) {
+            // No honest row comes here.  A forged one may still hold mod p with full-width cells (a limb rewritten to p - 1
+            // and its accumulators repaired): then the row is not what is wrong with it, and the report must name the bound
+            // or the table that is.  The general evaluation of the frames, on the whole row in every lane of the quad --
+            // after the cell's own checks, whose operands are dead by now.
+            Cell q[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int i = 0; i < 4; i++) q[j].l[i] = quad64(x.l[i], j);
+            ok = row_holds(q);
+        }
+        if (act && !ok && j4 == 0) fail(VERIFY_GATE_ROW, c);
+        if (enc_bad) fail(VERIFY_RANGE, cell);
+        if (own) fail(own, cell);
     }
     // 3. assert_equal / range_check accumulator copies
     for (u32 i = tid; i < p.n_assert_eq; i += nt) {

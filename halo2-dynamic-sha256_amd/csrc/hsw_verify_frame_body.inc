@@ -12,15 +12,18 @@
         at0 = ctx * p.ctx_stream;
         gate += 2u * (size_t)(ctx * p.ctx_image);
     }
-    auto gcell = [&](u64 idx) -> Cell {
+    auto raw_gcell = [&](u64 idx) -> Cell {            // the cell as stored
+        idx -= at0;           // (a Context group: the table is one Context's; at0 = 0 otherwise)
         if constexpr (TABLE) {
-            idx -= at0;       // (a Context group: the table is one Context's; at0 = 0 otherwise)
             const u64 k = tbl_count(*tbl, idx);
-            return load_value<MONT>(gate, idx + (k ? tbl->cum[k - 1] : 0));
+            return load_cell(gate, idx + (k ? tbl->cum[k - 1] : 0));
         } else {
-            idx -= at0;
-            return load_value<MONT>(gate, packed ? place(p, idx) : idx);
+            return load_cell(gate, packed ? place(p, idx) : idx);
         }
+    };
+    auto gcell = [&](u64 idx) -> Cell {
+        const Cell c = raw_gcell(idx);
+        if constexpr (MONT) return from_mont(c); else return c;
     };
     u32 bad = 0, first = 0xffffffffu, first_class = 0;
     auto fail = [&](u32 cls, u32 at) { bad++; if (at < first) { first = at; first_class = cls; } };
@@ -51,8 +54,13 @@
         }
         for (u32 c = tid; c < S.cells; c += nt) {
             const uint8_t k = S.kind[c];
+            const Cell raw = raw_gcell(base + c);
+            Cell v = raw;
+            if constexpr (MONT) {      // a Montgomery cell is an encoding m < p: m + p reduces to the same value and would pass everything else
+                if (geq_p(raw)) fail(VERIFY_RANGE, tag | c);
+                if (k != 0) v = from_mont(raw);
+            }
             if (k == 0) continue;
-            const Cell v = gcell(base + c);
             if (k == 1) {
                 const int64_t kv = S.ref[c];
                 Cell want = small((u64)(kv >= 0 ? kv : -kv));
@@ -73,8 +81,11 @@
         }
         if (lk)
             for (u32 j = tid; j < S.n_lookup; j += nt) {
-                const Cell v = load_value<MONT>(lk, lbase + j);
-                if (!(narrow(v) && v.l[0] < 65536 && same(v, cell_of(S.lookup_src[j])))) fail(VERIFY_LOOKUP, tag | j);
+                const Cell rv = load_cell(lk, lbase + j);
+                Cell v = rv;
+                bool enc = true;
+                if constexpr (MONT) { v = from_mont(rv); enc = !geq_p(rv); }      // canonical encoding only, as in the block body
+                if (!(enc && narrow(v) && v.l[0] < 65536 && same(v, cell_of(S.lookup_src[j])))) fail(VERIFY_LOOKUP, tag | j);
             }
     }
     // ---- the facts of this digest and the links between the sections ----
@@ -83,6 +94,8 @@
         if (!same(gcell(P0 + frame::P_LEN), small(d.input_len))) fail(VERIFY_COPY, frame::P_LEN);           // AssignedHashResult.input_len
         if (!same(gcell(P0 + frame::P_PRE), small(d.precomputed_round))) fail(VERIFY_COPY, frame::P_PRE);
         if (d.zero_cell != ~0ull && !same(gcell(d.zero_cell), small(0))) fail(VERIFY_CONSTANT, frame::P_BYTES - 1);
+        if constexpr (MONT)            // the zero cell stored as p reduces to 0
+            if (d.zero_cell != ~0ull && geq_p(raw_gcell(d.zero_cell))) fail(VERIFY_RANGE, frame::P_BYTES - 1);
         (void)target;
     }
     if (tid < 8 && !same(gcell(P0 + frame::P_STATE + tid), small(state_word(0, tid)))) fail(VERIFY_COPY, frame::P_STATE + tid);

@@ -249,7 +249,10 @@ int hsw_block_structure(const hsw_shape *shape, hsw_structure_counts *counts, ui
  * stream that passes IS the witness of its inputs (every cell is forced by those constraints).  Takes
  * the buffers and layout of a hsw_witness_blocks(_ex) call (canonical or Montgomery cells -- the latter
  * are reduced on load; pack and frame_* as given
- * there; chip, lookup and next-state pointers may be NULL = not checked).  Synchronous. */
+ * there; chip, lookup and next-state pointers may be NULL = not checked).  A Montgomery cell is an encoding
+ * m < p: a gate, chip or lookup cell whose stored limbs are >= p is reported (HSW_VERIFY_RANGE, _CHIP, _LOOKUP)
+ * although it reduces to a value that satisfies every constraint.  A gate row is evaluated mod p whatever
+ * its cells hold, so a forged row that still holds is not what is reported.  Synchronous. */
 #define HSW_VERIFY_CONSTANT   1u
 #define HSW_VERIFY_COPY       2u
 #define HSW_VERIFY_GATE_ROW   3u
@@ -889,7 +892,8 @@ int hsw_gadget_seek(hsw_gadget *g, size_t hash_idx);
 /* Check everything the gadget has written so far against the constraint system, on the device:
  * hsw_verify_blocks on every run of blocks + hsw_verify_frames on their frames (whole-digest contexts;
  * linear stream or column image), or hsw_verify_blocks alone (block-stream contexts).  Canonical or
- * Montgomery cells.  report->first_block counts the gadget's blocks (hsw_hash_result.first_block), whichever
+ * Montgomery cells; the canonical-encoding rule of hsw_verify_blocks holds for every frame cell, the Context's zero
+ * cell and every frame lookup entry too (HSW_VERIFY_RANGE / HSW_VERIFY_LOOKUP).  report->first_block counts the gadget's blocks (hsw_hash_result.first_block), whichever
  * launch found the failure. */
 int hsw_gadget_verify(hsw_gadget *g, hsw_verify_report *report);
 /* (column, row) of gate-stream cell `cell` (identity on row without set_columns). */
@@ -1045,7 +1049,8 @@ int hsw_gadget_verify_equal(hsw_gadget *g, const uint64_t *cells_a, const uint64
  * are zeroed first (2^16 / 2^num_bits_lookup counters each, not `pitch`) and no other counter is touched.  An entry is
  * in its table only if the WHOLE 32-byte cell (reduced from Montgomery form where the cells are HSW_REPR_MONTGOMERY)
  * equals a table row: a cell whose low limb fits and whose upper limbs are not zero is counted in not_in_table and in
- * no counter, so per proof sum(counts) + its share of not_in_table = its listed entries.  The counters are the only
+ * no counter, and so is a Montgomery cell (dense or spread) whose stored limbs are >= p -- an encoding m + p reduces
+ * to the value of m, but a cell is an encoding below p and nothing else is a row.  So per proof sum(counts) + its share of not_in_table = its listed entries.  The counters are the only
  * caller memory written.  Unassigned rows are the caller's: halo2 looks (0, 0) up there, so a prover adds
  * usable_rows - entries to row 0 of each table.  Synchronous on the engine's stream; an empty list is HSW_OK, a zero
  * report and no launch.  HSW_ERR_INVALID_ARG before any launch: both table pointers NULL, a pitch below the table

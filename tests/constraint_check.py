@@ -50,7 +50,13 @@ def check_block_batch(xp, cs, gate, blocks, pre, dense_limb, spread_limb, next_s
     narrow = (x[0][..., 1:] == 0).all(-1) & (x[1][..., 1:] == 0).all(-1) & (x[2][..., 1:] == 0).all(-1) & \
              (x[3][..., 1:] == 0).all(-1)
     lhs = x[0][..., 0] + x[1][..., 0] * x[2][..., 0]
-    assert bool(((lhs == x[3][..., 0]) | ~narrow).all()), "gate equation violated"
+    # ... for a witness whose rows stay below 2^64, as every honest one does.  A forged row may wrap: the same sum in
+    # float64 (limbs read as unsigned; off by 2^12 at most near 2^64, by 2^-52 of itself above) tells a multiple of 2^64 apart
+    def u64f(a):
+        f = a.astype(np.float64) if xp is np else a.double()
+        return f + (a < 0) * 18446744073709551616.0
+    near = abs(u64f(x[0][..., 0]) + u64f(x[1][..., 0]) * u64f(x[2][..., 0]) - u64f(x[3][..., 0])) < 2.0**40
+    assert bool((((lhs == x[3][..., 0]) & near) | ~narrow).all()), "gate equation violated"
     wide = ~narrow
     if bool(wide.any()):
         # the only rows with a > 64-bit cell: [a, p-a, 1, 0] and [M, p-a, 1, M-a] (compression.rs:320-335)

@@ -20,7 +20,29 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def sweep(bits=8, ncols=2, mont=False, internals=True, limb=0, stride=1, seed=5, log=None):
+P_LIMBS = [0x43e1f593f0000001, 0x2833e84879b97091, 0xb85045b68181585d, 0x30644e72e131a029]
+
+
+def add_p(cell, mont):
+    """A `mutate` for the sweeps: the stored cell m -> m + p, in place -- the same field value under another encoding (a
+    Montgomery cell is an encoding m < p; a canonical cell v + p is no cell at all)."""
+    import torch
+    limbs = [int(x) & 0xFFFFFFFFFFFFFFFF for x in cell.cpu().numpy().view(np.uint64)]
+    m = sum(x << (64 * i) for i, x in enumerate(limbs)) + sum(x << (64 * i) for i, x in enumerate(P_LIMBS))
+    assert m < 1 << 256
+    cell.copy_(torch.from_numpy(np.array([(m >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64).view(np.int64)))
+
+
+def _corrupt(cell, mont, limb, mutate):
+    """One corruption of the (4,) int64 view `cell`: mutate(cell, mont) where given, else canonical limb ^= 1, Montgomery
+    limb ^= 0x10 (any change of a limb moves the value)."""
+    if mutate is not None:
+        mutate(cell, mont)
+    else:
+        cell[limb] ^= 1 if not mont else 0x10
+
+
+def sweep(bits=8, ncols=2, mont=False, internals=True, limb=0, stride=1, seed=5, log=None, mutate=None):
     import torch
     hsw = importlib.import_module("halo2-dynamic-sha256_amd")
     N = hsw._native
@@ -49,7 +71,7 @@ def sweep(bits=8, ncols=2, mont=False, internals=True, limb=0, stride=1, seed=5,
         for k in range(0, count, stride):
             idx = index_of(k)
             saved = tensor[idx].clone()
-            tensor[idx][limb] ^= 1 if not mont else 0x10        # Montgomery: any change of the limb moves the value
+            _corrupt(tensor[idx], mont, limb, mutate)
             if verify()["violations"] == 0:
                 bad.append(k)
             tensor[idx] = saved
@@ -94,7 +116,7 @@ class _DevCells:
         self.__cuda_array_interface__ = {"shape": (n, 4), "typestr": "<i8", "data": (int(ptr), False), "version": 2}
 
 
-def sweep_frames(sizes=(128, 64), rc=True, mont=False, columns=None, limb=0, log=None):
+def sweep_frames(sizes=(128, 64), rc=True, mont=False, columns=None, limb=0, log=None, mutate=None):
     """The same for the digest frames (hsw_gadget_verify): every prologue / epilogue cell and the zero cell of a
     whole-digest context, every lookup-column entry of the frames.  Expected free: the one cell the reference
     itself leaves unconstrained (is_zero's inverse witness when its input IS zero -- any value satisfies the row)."""
@@ -124,7 +146,7 @@ def sweep_frames(sizes=(128, 64), rc=True, mont=False, columns=None, limb=0, log
                 col, row = cfg.cell_position(cell) if columns else (0, cell)
                 at = col * columns + row if columns else cell
                 saved = gate[at].clone()
-                gate[at][limb] ^= 1 if not mont else 0x10
+                _corrupt(gate[at], mont, limb, mutate)
                 if cfg.verify()["violations"] == 0:
                     missed["frame gate"].append((d, cell - (a if a == r.prologue_cell else r.epilogue_cell), "prologue" if a == r.prologue_cell else "epilogue"))
                 gate[at] = saved
@@ -132,7 +154,7 @@ def sweep_frames(sizes=(128, 64), rc=True, mont=False, columns=None, limb=0, log
         for a, b in [(r.prologue_lookup, r.block_lookup), (r.epilogue_lookup, r.epilogue_lookup + 64)]:
             for k in range(a, b):
                 saved = lookup[k].clone()
-                lookup[k][limb] ^= 1 if not mont else 0x10
+                _corrupt(lookup[k], mont, limb, mutate)
                 if cfg.verify()["violations"] == 0:
                     missed["frame lookup"].append((d, k - a))
                 lookup[k] = saved
@@ -279,7 +301,8 @@ class OwnedMemory:
         v = cfg.view()
         ncols = cfg.engine.ncols
         self.rows, cols = int(v.max_rows), int(v.columns)
-        assert self.rows, "a column image (set_columns)"
+        linear = not self.rows and not (cfg.context_images or cfg.n_contexts is not None)      # one stream: gate(0, 0, cell)
+        assert self.rows or linear, "a column image (set_columns)"
         self.image, self.look, self.dense, self.spread = [], [], [], []
         if cfg.context_images or cfg.n_contexts is not None:
             for c in range(contexts):
@@ -292,7 +315,7 @@ class OwnedMemory:
         else:
             assert contexts == 1
             rows = (int(v.num_limb_sum) + ncols - 1) // ncols
-            self.image.append(_dev_view(v.d_gate, cols * self.rows))
+            self.image.append(_dev_view(v.d_gate, int(v.gate_cells) if linear else cols * self.rows))
             self.look.append(_dev_view(v.d_lookup, int(v.lookup_cells)))
             self.dense.append([_dev_view(v.d_chip_dense + 32 * k * int(v.chip_col_stride), rows) for k in range(ncols)])
             self.spread.append([_dev_view(v.d_chip_spread + 32 * k * int(v.chip_col_stride), rows) for k in range(ncols)])
@@ -331,10 +354,10 @@ class CallerMemory:
         return [self.t]
 
 
-def sweep_layout(cfg, results, cells, mem, contexts=1, mont=False, limb=0, log=None, name="layout"):
+def sweep_layout(cfg, results, cells, mem, contexts=1, mont=False, limb=0, log=None, name="layout", mutate=None):
     """Corrupt the cells `cells` (select_cells' tuples) of a finished whole-digest pass one at a time, in place in device
     memory `mem` (OwnedMemory / CallerMemory), with hsw_gadget_verify after each: canonical limb ^= 1, Montgomery ^= 0x10
-    as in sweep().  A stream cell's place comes from cfg.cell_position.  Returns dict(tested, missed, misattributed,
+    as in sweep(), or mutate(cell, mont) where given.  A stream cell's place comes from cfg.cell_position.  Returns dict(tested, missed, misattributed,
     seconds): `missed` the cells whose corruption passed, `misattributed` (cell, report) where the report's first_block
     lies outside the owning digest's blocks or a chip / lookup cell was reported under another class.  Afterwards the
     region verifies again and every tensor of `mem` equals its snapshot from before the first flip."""
@@ -381,7 +404,7 @@ def sweep_layout(cfg, results, cells, mem, contexts=1, mont=False, limb=0, log=N
         c, d, section, _ = cell
         t, at = where(*cell)
         saved = t[at].clone()
-        t[at][limb] ^= 1 if not mont else 0x10
+        _corrupt(t[at], mont, limb, mutate)
         rep = cfg.verify()
         t[at] = saved
         out["tested"] += 1

@@ -31,7 +31,7 @@ import time
 
 import pytest
 
-from tests.flip_sweep import CallerMemory, OwnedMemory, free_witnesses, layout_facts, select_cells, sweep_layout
+from tests.flip_sweep import CallerMemory, OwnedMemory, add_p, free_witnesses, layout_facts, select_cells, sweep_layout
 from tests.test_gpu_bound_column_tables import CarvedAll
 from tests.test_gpu_bound_columns import Carved, interleaved
 from tests.test_gpu_bound_region import N17, Slabs, eng_int  # noqa: F401 (fixture)
@@ -156,8 +156,9 @@ def build(hsw, eng, case, mont):
     return cfg, res, mem, contexts, msgs, keep
 
 
-def run_case(hsw, eng, case, mont, log=None):
-    """One case, with what it asserts about itself; returns sweep_layout's counts (+ "expected": the free witnesses)."""
+def run_case(hsw, eng, case, mont, log=None, mutate=None):
+    """One case, with what it asserts about itself; returns sweep_layout's counts (+ "expected": the free witnesses).
+    mutate: sweep_layout's, instead of the limb flip."""
     spec = CASES[case]
     cfg, res, mem, contexts, msgs, keep = build(hsw, eng, case, mont)
     try:
@@ -185,7 +186,7 @@ def run_case(hsw, eng, case, mont, log=None):
         assert {c[0] for c in cells} == set(range(contexts))
         for c, ctx in enumerate(facts):                       # every Context assigns its zero cell here: it is in the sample
             assert ctx[0][0]["zero"] is not None and (c, 0, "prologue", ctx[0][0]["zero"]) in cells
-        out = sweep_layout(cfg, res, cells, mem, contexts, mont=mont, log=log, name="%s %s" % (case, "mont" if mont else "canon"))
+        out = sweep_layout(cfg, res, cells, mem, contexts, mont=mont, log=log, name="%s %s" % (case, "mont" if mont else "canon"), mutate=mutate)
         out["expected"] = free
         print("case %s %s: %d cells tried, %d missed, %.2f s" % (case, "montgomery" if mont else "canonical", out["tested"], len(out["missed"]), out["seconds"]))
         return out
@@ -201,6 +202,16 @@ def test_sampled_corruptions_leave_only_the_free_witnesses(hsw, eng_int, case, m
     assert out["misattributed"] == []
     assert sorted(out["missed"]) == sorted(out["expected"]), "missed, not free: %s; free, but reported: %s" % (
         sorted(set(out["missed"]) - set(out["expected"])), sorted(set(out["expected"]) - set(out["missed"])))
+
+
+@pytest.mark.parametrize("case", ["b", "h"])
+def test_non_canonical_montgomery_encodings_are_never_free(hsw, eng_int, case):
+    """The same sample with every cell stored as m + p instead of flipped: the value does not change, so no equality
+    sees it -- only the rule that a Montgomery cell is an encoding m < p.  b: the TABLE frame kernel, h: the WIDE one.
+    An encoding is never free: the free witnesses are reported too."""
+    out = run_case(hsw, eng_int, case, True, mutate=add_p)
+    assert out["misattributed"] == []
+    assert out["missed"] == [], "stored as m + p and accepted: %s" % out["missed"]
 
 
 def run_all(log=sys.stdout):

@@ -9,6 +9,7 @@ sentinel that is no table row, so a run that reached one cell too far would be s
 import numpy as np
 import pytest
 
+from tests.constraint_check import P_INT
 from tests.test_gpu_bound_column_tables import CarvedAll, geometry
 from tests.test_gpu_bound_columns import interleaved
 from tests.test_gpu_bound_region import MAX_ROWS, REPR, Slabs, interlude_after_digest0, make
@@ -242,11 +243,15 @@ def test_non_members_are_counted_apart(hsw, oracle, eng_int, mont):
     _, _, _, runs = check(cfg, exp)
     base = sl.t.data_ptr()
 
-    def poke(addr, value):
-        """the whole cell at a device address := value, in the gadget's representation"""
+    def poke(addr, value, plus_p=False):
+        """the whole cell at a device address := value, in the gadget's representation; plus_p: stored as m + p"""
         cell = np.array([[(value >> (64 * i)) & (2**64 - 1) for i in range(4)]], dtype=np.uint64)
         if mont:
             cell = oracle.to_montgomery(cell)
+        if plus_p:
+            m = sum(int(x) << (64 * i) for i, x in enumerate(cell[0])) + P_INT
+            assert mont and m < 1 << 256
+            cell = np.array([[(m >> (64 * i)) & (2**64 - 1) for i in range(4)]], dtype=np.uint64)
         assert (addr - base) % 32 == 0
         sl.t[(addr - base) // 32] = torch.from_numpy(cell.view(np.int64)[0]).cuda()
         torch.cuda.synchronize()
@@ -263,12 +268,23 @@ def test_non_members_are_counted_apart(hsw, oracle, eng_int, mont):
     d = int(exp[1][2]["dense"][1, 9, 0])
     poke(c1["d_spread"] + 32 * 9, spread_of(d) + 1)
     want[1][1][d] -= 1
+    bad = 3
+    if mont:
+        # A Montgomery cell is an encoding m < p.  Stored as m + p it reduces to the same value, but the whole 32-byte
+        # value is then no table row: proof 1, first range run, entry 200 and chip column 0, row 11, the spread cell.
+        poke(r1[0]["d_cells"] + 32 * 200, int(lk1[200]), plus_p=True)
+        want[1][0][lk1[200]] -= 1
+        c0 = [x for x in runs if x["context"] == 1 and x["table"] == 1 and x["column"] == 0][0]
+        d0 = int(exp[1][2]["dense"][0, 11, 0])
+        poke(c0["d_spread"] + 32 * 11, spread_of(d0), plus_p=True)
+        want[1][1][d0] -= 1
+        bad = 5
     r, s, rep = cfg.lookup_multiplicities()
-    assert rep["not_in_table"] == 3, rep
+    assert rep["not_in_table"] == bad, rep
     # the lowest in (context, table, column, entry) order: proof 1's range entry 100 of its first run
     assert (rep["first_context"], rep["first_table"], rep["first_column"], rep["first_entry"]) == (1, 0, 0, r1[0]["first"] + 100), rep
     rh, sh = r.cpu().numpy(), s.cpu().numpy()
     for c in range(G_K):
         assert np.array_equal(rh[c], want[c][0]) and np.array_equal(sh[c], want[c][1]), c
-        assert int(rh[c].sum() + sh[c].sum()) == int(exp[c][0].sum() + exp[c][1].sum()) - (3 if c == 1 else 0)
+        assert int(rh[c].sum() + sh[c].sum()) == int(exp[c][0].sum() + exp[c][1].sum()) - (bad if c == 1 else 0)
     cfg.close()

@@ -234,6 +234,23 @@ class LookupReport(C.Structure):
                 ("kernel_ms", C.c_float), ("reserved_", C.c_uint32)]
 
 
+HSW_PERMUTED_GIVEN_M, HSW_PERMUTED_THETA_ON_SPREAD = 1, 2
+
+
+class LookupPermuted(C.Structure):
+    """hsw_lookup_permuted: the A' and S' columns of every argument of one table (hsw_gadget_lookup_permuted)."""
+    _fields_ = [("table", C.c_uint32), ("flags", C.c_uint32), ("usable_rows", C.c_uint64), ("n_arguments", C.c_size_t),
+                ("d_input_columns", C.POINTER(C.c_void_p)), ("d_table_columns", C.POINTER(C.c_void_p)), ("thetas", C.c_void_p),
+                ("d_m", C.c_void_p), ("m_pitch", C.c_uint64)]
+
+
+class PermutedReport(C.Structure):
+    _fields_ = [("arguments", C.c_uint64), ("entries", C.c_uint64), ("written", C.c_uint64), ("not_in_table", C.c_uint64),
+                ("first_context", C.c_uint64), ("first_entry", C.c_uint64), ("first_table", C.c_uint32), ("first_column", C.c_uint32),
+                ("overflow_arguments", C.c_uint64), ("kernel_ms", C.c_float), ("prepare_ms", C.c_float), ("write_ms", C.c_float),
+                ("reserved_", C.c_uint32)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -255,7 +272,7 @@ SYMBOLS = (
     "hsw_gadget_bind_region", "hsw_gadget_region_binding", "hsw_gadget_bind_columns", "hsw_gadget_bind_column_tables",
     "hsw_gadget_digest_batch_device", "hsw_gadget_digest_levels_device",
     "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
-    "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities",
+    "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities", "hsw_gadget_lookup_permuted",
 )
 
 
@@ -351,6 +368,9 @@ def lib():
             L.hsw_gadget_lookup_runs.argtypes = [vp, C.POINTER(LookupRun), C.c_size_t, C.POINTER(C.c_size_t)]
             L.hsw_gadget_lookup_multiplicities.restype = C.c_int
             L.hsw_gadget_lookup_multiplicities.argtypes = [vp, C.POINTER(LookupCounts), C.POINTER(LookupReport)]
+        if hasattr(L, "hsw_gadget_lookup_permuted"):   # absent only in A/B builds of an earlier commit (HSW_LIB_OVERRIDE)
+            L.hsw_gadget_lookup_permuted.restype = C.c_int
+            L.hsw_gadget_lookup_permuted.argtypes = [vp, C.POINTER(LookupPermuted), C.POINTER(PermutedReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

@@ -295,6 +295,11 @@ int hsw_engine_set_option(hsw_engine *e, const char *name, int64_t value) try {
         e->lookup_lds = (int)value;
         return HSW_OK;
     }
+    if (std::strcmp(name, "permuted_scratch") == 0) {  // hsw_gadget_lookup_permuted: bytes of index and value arrays per group of arguments
+        if (value < 1 || value > ((int64_t)1 << 32)) return set_err(e, HSW_ERR_INVALID_ARG, "permuted_scratch must be 1 .. 2^32 bytes");
+        e->permuted_scratch = (size_t)value;
+        return HSW_OK;
+    }
     if (std::strcmp(name, "chunk_blocks") == 0) {      // blocks per launch of a long batch; tests shrink it to reach that loop
         if (value < 1 || value > (1 << 20)) return set_err(e, HSW_ERR_INVALID_ARG, "chunk_blocks must be 1 .. 2^20");
         e->chunk_blocks = (size_t)value;

@@ -17,10 +17,10 @@
 // HSW_GADGET_WHOLE_DIGEST (hsw_frame.hpp / hsw_frame_kernel, assumption A4);
 // without it only their *values* are produced (AssignedHashResult).
 //
-// Implemented in five translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
+// Implemented in six translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
 // call), hsw_gadget_context.cpp (Context: buffers, layouts, bind / unbind, the jump table), hsw_gadget_digest.cpp (the
-// digest paths and the ties), hsw_gadget_lookup.cpp (the lookup entries of a pass, listed and counted) and
-// hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
+// digest paths and the ties), hsw_gadget_lookup.cpp (the lookup entries of a pass, listed and counted),
+// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
 #ifndef HSW_GADGET_HPP
 #define HSW_GADGET_HPP
 
@@ -379,6 +379,8 @@ struct hsw_gadget {
     size_t pairs_cap = 0;                           // grown on demand, freed by hsw_gadget_destroy
     void *d_lookup_runs = nullptr;                  // hsw_gadget_lookup_multiplicities (hsw_gadget_lookup.cpp): its report, run
     size_t lookup_runs_cap = 0;                     // table and zero lists on the device, in bytes; grown and freed like d_pairs
+    void *d_permuted = nullptr;                     // hsw_gadget_lookup_permuted (hsw_gadget_permuted.cpp): its report, staging, index
+    size_t permuted_cap = 0;                        // and value arrays on the device, in bytes; grown and freed like d_pairs
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

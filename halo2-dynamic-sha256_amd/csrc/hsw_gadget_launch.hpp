@@ -16,6 +16,17 @@ namespace hsw {
 
 inline int hip_status(hipError_t he) { return he == hipSuccess ? HSW_OK : he == hipErrorOutOfMemory ? HSW_ERR_NOMEM : HSW_ERR_HIP; }
 
+// the representation every batch of the pass was written in (HSW_OK), or HSW_ERR_UNSUPPORTED if they differ: what the
+// calls that read the pass's cells back (hsw_gadget_lookup.cpp, hsw_gadget_permuted.cpp) decide membership in
+inline int pass_repr(const Context &c, uint32_t *repr) {
+    *repr = c.repr_flags;
+    for (size_t i = 0; i < c.batches.size(); i++) {
+        if (i == 0) *repr = c.batches[i].repr_flags;
+        else if (c.batches[i].repr_flags != *repr) return HSW_ERR_UNSUPPORTED;
+    }
+    return HSW_OK;
+}
+
 // Where the launches of a batch write -- or, for hsw_gadget_verify, read: the generator and the verifier build
 // their arguments here and nowhere else, so they agree in every kind of layout.  Made once per batch (what the
 // frame launches need too), then filled in per launch.  `a`, `tbl` and `period` point at each other: not copyable.

@@ -12,16 +12,6 @@
 
 namespace {
 
-// the representation every batch of the pass was written in (HSW_OK), or HSW_ERR_UNSUPPORTED if they differ
-int pass_repr(const hsw::Context &c, uint32_t *repr) {
-    *repr = c.repr_flags;
-    for (size_t i = 0; i < c.batches.size(); i++) {
-        if (i == 0) *repr = c.batches[i].repr_flags;
-        else if (c.batches[i].repr_flags != *repr) return HSW_ERR_UNSUPPORTED;
-    }
-    return HSW_OK;
-}
-
 int list_runs(const hsw_gadget *g, std::vector<hsw_lookup_run> &runs) {
     const hsw::Context &c = *g->ctx;
     runs.clear();
@@ -112,7 +102,7 @@ int hsw_gadget_lookup_multiplicities(hsw_gadget *g, const hsw_lookup_counts *out
         return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "a counter table that is not 4-byte aligned");
     if (out->d_range && !(c.whole && c.d_lookup)) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "this gadget has no lookup column");
     uint32_t repr = 0;
-    if (pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
+    if (hsw::pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
     if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "32-byte cells only");
     std::vector<hsw_lookup_run> runs;
     int rc = list_runs(g, runs);

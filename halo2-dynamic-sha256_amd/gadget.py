@@ -546,6 +546,67 @@ class Sha256DynamicConfig:
                           not_in_table=int(rep.not_in_table), first_context=int(rep.first_context), first_entry=int(rep.first_entry),
                           first_table=int(rep.first_table), first_column=int(rep.first_column), kernel_ms=float(rep.kernel_ms))
 
+    def lookup_permuted(self, table, usable_rows, thetas=None, m=None, out_input=None, out_table=None, theta_on_spread=False):
+        """hsw_gadget_lookup_permuted: halo2's permuted lookup columns A' and S' of every argument of `table`
+        (HSW_LOOKUP_RANGE: one argument per proof; HSW_LOOKUP_SPREAD: one per proof and chip column), written on the
+        device.  Returns (input, table, m, report): two uint64 device tensors of shape (arguments, usable_rows, 4), the
+        int32 multiplicities (arguments, pitch) and the report as a dict.  thetas (SPREAD): one field element per proof
+        AS STORED, i.e. in the representation of the cells (Montgomery cells: theta * 2^256 mod p) -- Python ints below p
+        or a (contexts, 4) uint64 numpy array / tensor of limbs.  m: the caller's own multiplicities, a contiguous
+        int32 tensor (arguments, pitch >= T) on the engine's device (HSW_PERMUTED_GIVEN_M); None: counted from the
+        pass.  out_input / out_table: the caller's own contiguous uint64 tensors of shape (arguments, rows >=
+        usable_rows, 4); rows from usable_rows on are never written.  report["written"] == 0: the device refused (an
+        entry that is no table row, multiplicities beyond usable_rows) and stored nothing."""
+        import numpy as np
+        import torch
+        dev = self.engine.device
+        spread = table == N.HSW_LOOKUP_SPREAD
+        if table not in (N.HSW_LOOKUP_RANGE, N.HSW_LOOKUP_SPREAD):
+            raise ValueError("lookup_permuted: table must be HSW_LOOKUP_RANGE or HSW_LOOKUP_SPREAD")
+        k = self._lookup_contexts()
+        n_args = k * int(self.engine.shape.num_advice_columns) if spread else k
+        rows = 1 << int(self.engine.shape.num_bits_lookup) if spread else 1 << 16
+        u = int(usable_rows)
+        if u < rows:
+            raise ValueError("usable_rows must be at least the table size %d" % rows)
+        cols = []
+        for name, t in (("out_input", out_input), ("out_table", out_table)):
+            if t is None:
+                t = torch.zeros((n_args, u, 4), dtype=torch.uint64, device=dev)
+            elif not isinstance(t, torch.Tensor) or t.dtype != torch.uint64 or t.device != dev:
+                raise ValueError("%s must be a uint64 tensor on %s" % (name, dev))
+            elif t.dim() != 3 or t.shape[0] != n_args or t.shape[1] < u or t.shape[2] != 4 or not t.is_contiguous():
+                raise ValueError("%s must be contiguous, of shape (%d, rows >= %d, 4)" % (name, n_args, u))
+            cols.append(t)
+        if m is not None:
+            if not isinstance(m, torch.Tensor) or m.dtype != torch.int32 or m.device != dev:
+                raise ValueError("m must be an int32 tensor on %s" % (dev,))
+            if m.dim() != 2 or m.shape[0] != n_args or m.shape[1] < rows or not m.is_contiguous():
+                raise ValueError("m must be contiguous, of shape (%d, pitch >= %d)" % (n_args, rows))
+        theta_buf = None
+        if spread:
+            if thetas is None:
+                raise ValueError("the spread argument needs one theta per proof")
+            if isinstance(thetas, torch.Tensor):
+                thetas = thetas.cpu().numpy()
+            if isinstance(thetas, np.ndarray):
+                theta_buf = np.ascontiguousarray(thetas, dtype=np.uint64)
+            else:
+                theta_buf = np.array([[(int(v) >> (64 * i)) & (2**64 - 1) for i in range(4)] for v in thetas], dtype=np.uint64)
+            if theta_buf.shape != (k, 4):
+                raise ValueError("thetas: one field element (4 x uint64) per proof, %d of them" % k)
+        elif thetas is not None:
+            raise ValueError("thetas given for the range argument")
+        counts = m if m is not None else torch.zeros((n_args, rows), dtype=torch.int32, device=dev)
+        ptrs = [(C.c_void_p * n_args)(*[t.data_ptr() + a * t.shape[1] * 32 for a in range(n_args)]) for t in cols]
+        flags = (N.HSW_PERMUTED_GIVEN_M if m is not None else 0) | (N.HSW_PERMUTED_THETA_ON_SPREAD if theta_on_spread else 0)
+        args = N.LookupPermuted(table, flags, u, n_args, ptrs[0], ptrs[1], theta_buf.ctypes.data if theta_buf is not None else None,
+                                counts.data_ptr(), counts.shape[1])
+        rep = N.PermutedReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the call runs on the engine's
+        self._ok(self.lib.hsw_gadget_lookup_permuted(self.h, C.byref(args), C.byref(rep)))
+        return cols[0], cols[1], counts, {f[0]: getattr(rep, f[0]) for f in N.PermutedReport._fields_ if f[0] != "reserved_"}
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

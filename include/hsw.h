@@ -1085,6 +1085,76 @@ typedef struct hsw_lookup_report {
     float kernel_ms; uint32_t reserved_;
 } hsw_lookup_report;
 int hsw_gadget_lookup_multiplicities(hsw_gadget *g, const hsw_lookup_counts *out, hsw_lookup_report *report);
+/* ---- halo2's permuted lookup columns A' and S', written on the device ----
+ * An ARGUMENT is one lookup of one proof (Context):
+ *   HSW_LOOKUP_RANGE   one per proof, a = c; T = 65536 table rows; the value of row t is val(t) = t;
+ *   HSW_LOOKUP_SPREAD  one per proof and chip column (the reference configures one lookup per (dense_k, spread_k) pair),
+ *                      a = c * num_advice_columns + k; T = 2^num_bits_lookup rows; val(t) = t * theta_c + spread(t) mod p,
+ *                      halo2's fold acc * theta + expr over [dense, spread] (DESIGN.md assumption A6) -- with
+ *                      HSW_PERMUTED_THETA_ON_SPREAD val(t) = t + spread(t) * theta_c.  thetas: HOST memory, contexts x 32
+ *                      bytes in the representation of the cells, the stored limbs below p (NULL for RANGE).
+ * d_input_columns / d_table_columns: HOST arrays (copied, not kept) of n_arguments DEVICE pointers, the A' and the S'
+ * column of argument a: usable_rows cells of 32 bytes each, 16-byte aligned, in any address order.  n_arguments must
+ * be contexts (RANGE) or contexts x num_advice_columns (SPREAD).  Cells are written in the representation of the pass (a
+ * Montgomery cell is val * 2^256 mod p, below p).
+ * With m[t] the argument's multiplicities, E = sum m and u = usable_rows: unassigned rows look row 0 up, m'[0] = m[0] +
+ * (u - E), m'[t] = m[t] otherwise; off[t] is the exclusive prefix sum of m'.  Then, so that the output is fixed bit for bit:
+ *   A'[i]      = val(t)  for off[t] <= i < off[t] + m'[t];
+ *   S'[off[t]] = val(t)  for every t with m'[t] > 0;
+ *   the remaining positions of S', ascending, take the leftover table rows in ascending row order: row 0 (u - T) +
+ *   [m'[0] = 0] times (the table column's padding rows repeat row 0), every t > 0 [m'[t] = 0] times.
+ * So A'[0] = S'[0] and A'[i] = S'[i] or A'[i] = A'[i-1] for i > 0, A' is a permutation of the padded input and S' of
+ * the padded table.  Rows at or beyond u of either column, and every other byte of the caller's, are never written:
+ * blinding rows are the prover's.  The order inside A' (by table row) is the library's; halo2's own is not pinned.
+ * Where m comes from:
+ *   counted (default)     from the argument's own runs as hsw_gadget_lookup_runs lists them (RANGE: the runs of the proof;
+ *                         SPREAD: the run of chip column k alone), membership decided as hsw_gadget_lookup_multiplicities
+ *                         decides it.  d_m (may be NULL) is an OUTPUT: the counted m, before the padding of row 0;
+ *   HSW_PERMUTED_GIVEN_M  d_m is an INPUT (required): the caller's counters, e.g. of a prover with lookup entries of its own.
+ * d_m: DEVICE memory, per-argument u32 tables [a * m_pitch + t], 4-byte aligned; m_pitch >= T, 0 = T.
+ * Decided on the device, all or nothing: an entry that is no table row (counted) or sum m > usable_rows (given) sets a
+ * flag in the first stage, and with the flag set the write stage stores nothing to any column: the status is HSW_OK,
+ * report->written = 0, and not_in_table / first_* (as in hsw_lookup_report) / overflow_arguments say why.  The host reads
+ * nothing between the stages.  An empty run list in counted mode is valid: every row is unassigned, A' is u x val(0) and
+ * S' the table with its padding (row 0 and its u - T copies first, as the leftover rule orders them, then rows 1 .. T-1).  Synchronous on the engine's stream.
+ * Refused before any launch -- HSW_ERR_INVALID_ARG: usable_rows < T, in counted mode an argument with more listed
+ * entries than usable_rows (hsw_last_error names it), a NULL or misaligned column pointer, a wrong n_arguments, unknown
+ * flags or table, d_m missing in given mode or misaligned, m_pitch below T, thetas missing for SPREAD or a theta >= p;
+ * HSW_ERR_TOO_LARGE: usable_rows above 2^31, or d_m NULL and 4 T bytes x n_arguments above half of "permuted_scratch"
+ * (pass d_m or raise the option); HSW_ERR_UNSUPPORTED: HSW_REPR_COMPACT64 cells, a pass whose batches differ
+ * in representation, RANGE on a gadget without a lookup column.
+ * Scratch (index arrays of 12 T bytes per argument, value tables of 32 T bytes per proof, and 4 T bytes per argument for
+ * m where d_m is NULL) is the gadget's: grown on demand, freed by hsw_gadget_destroy.  It is bounded by the engine option
+ * "permuted_scratch": m of ALL arguments (it cannot be grouped: the flag must be known for every argument before the
+ * first store) may take half of it at the most, and the arguments are processed in groups whose index and value arrays fit
+ * the rest -- a group being at least one proof, so the bound is max(permuted_scratch, m + one proof's arrays) plus the
+ * run table.
+ * kernel_ms: the whole call on the device; prepare_ms (count, index arrays, value tables) + write_ms (the stores) = kernel_ms.
+ * (The call came under HSW_ABI_MINOR 1: probe for the symbol.) */
+#define HSW_PERMUTED_GIVEN_M 1u
+#define HSW_PERMUTED_THETA_ON_SPREAD 2u
+typedef struct hsw_lookup_permuted {
+    uint32_t table;                  /* HSW_LOOKUP_RANGE | HSW_LOOKUP_SPREAD */
+    uint32_t flags;
+    uint64_t usable_rows;            /* u: T <= u <= 2^31 */
+    size_t n_arguments;
+    void *const *d_input_columns;    /* host array of n_arguments device pointers: A' */
+    void *const *d_table_columns;    /* host array of n_arguments device pointers: S' */
+    const void *thetas;              /* host, contexts x 32 bytes; SPREAD only */
+    uint32_t *d_m;                   /* device, n_arguments x m_pitch u32; counted: output or NULL; given: input */
+    uint64_t m_pitch;                /* >= T; 0 = T */
+} hsw_lookup_permuted;
+typedef struct hsw_permuted_report {
+    uint64_t arguments;                       /* arguments processed */
+    uint64_t entries;                         /* counted mode: lookup entries looked at */
+    uint64_t written;                         /* cells written: 2 * usable_rows * arguments, or 0 */
+    uint64_t not_in_table;                    /* counted mode: entries that are no row of their table */
+    uint64_t first_context, first_entry;      /* the lowest of them in (context, table, column, entry) order */
+    uint32_t first_table, first_column;
+    uint64_t overflow_arguments;              /* given mode: arguments with sum m > usable_rows */
+    float kernel_ms, prepare_ms, write_ms; uint32_t reserved_;
+} hsw_permuted_report;
+int hsw_gadget_lookup_permuted(hsw_gadget *g, const hsw_lookup_permuted *args, hsw_permuted_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */
@@ -1113,7 +1183,10 @@ int hsw_fill_calibrate(hsw_engine *e, void *d_buf, size_t bytes, float *ms);
  * instructions than the canonical kernel, but one wave per block), 2 = at emit time always (also internals mode).
  * "chunk_blocks": blocks per kernel launch of a long batch (default and maximum 2^20; a test knob).
  * "lookup_lds": hsw_gadget_lookup_multiplicities counts tables of up to 2^11 rows in LDS first (1, default) or every
- * table by global atomics (0; a measuring knob). */
+ * table by global atomics (0; a measuring knob).
+ * "permuted_scratch": bytes of scratch hsw_gadget_lookup_permuted holds at a time (default 256 MiB, 1 .. 2^32): the
+ * multiplicities where the caller passes no d_m (at most half of it, else HSW_ERR_TOO_LARGE) and the index arrays and value
+ * tables of a group of arguments; the arguments are processed in groups that fit, a group being at least one proof. */
 int hsw_engine_set_option(hsw_engine *e, const char *name, int64_t value);
 
 const char *hsw_strerror(int status);

@@ -316,6 +316,47 @@ pub struct hsw_lookup_report {
     pub reserved_: u32,
 }
 
+/// `hsw_lookup_permuted.flags`: `d_m` holds the caller's multiplicities instead of receiving the counted ones.
+pub const HSW_PERMUTED_GIVEN_M: u32 = 1;
+/// `hsw_lookup_permuted.flags`: the spread row is `t + spread(t) * theta` instead of `t * theta + spread(t)`.
+pub const HSW_PERMUTED_THETA_ON_SPREAD: u32 = 2;
+
+/// Arguments of `hsw_gadget_lookup_permuted`: one A' and one S' device column of `usable_rows` cells per argument
+/// (RANGE: per proof; SPREAD: per proof and chip column), host arrays of device pointers; `thetas` is host memory,
+/// `d_m` device memory.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_lookup_permuted {
+    pub table: u32,
+    pub flags: u32,
+    pub usable_rows: u64,
+    pub n_arguments: usize,
+    pub d_input_columns: *const *mut c_void,
+    pub d_table_columns: *const *mut c_void,
+    pub thetas: *const c_void,
+    pub d_m: *mut u32,
+    pub m_pitch: u64,
+}
+
+/// Result of `hsw_gadget_lookup_permuted`; `written == 0` with `HSW_OK` means the device refused (see the header).
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_permuted_report {
+    pub arguments: u64,
+    pub entries: u64,
+    pub written: u64,
+    pub not_in_table: u64,
+    pub first_context: u64,
+    pub first_entry: u64,
+    pub first_table: u32,
+    pub first_column: u32,
+    pub overflow_arguments: u64,
+    pub kernel_ms: f32,
+    pub prepare_ms: f32,
+    pub write_ms: f32,
+    pub reserved_: u32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -588,6 +629,9 @@ extern "C" {
     /// Counts the listed entries into the caller's per-proof multiplicity tables on the device; synchronous.
     pub fn hsw_gadget_lookup_multiplicities(g: *mut hsw_gadget, out: *const hsw_lookup_counts,
                                             report: *mut hsw_lookup_report) -> c_int;
+    /// halo2's permuted lookup columns A' and S' of every argument of one table, written on the device.
+    pub fn hsw_gadget_lookup_permuted(g: *mut hsw_gadget, args: *const hsw_lookup_permuted,
+                                      report: *mut hsw_permuted_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

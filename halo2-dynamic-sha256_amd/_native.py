@@ -251,6 +251,24 @@ class PermutedReport(C.Structure):
                 ("reserved_", C.c_uint32)]
 
 
+HSW_PRODUCT_OPEN, HSW_PRODUCT_ZERO_DENOM, HSW_PRODUCT_CELL_NOT_BELOW_P = 1, 2, 4
+
+
+class LookupProduct(C.Structure):
+    """hsw_lookup_product: the grand-product column Z of every argument of one table (hsw_gadget_lookup_product)."""
+    _fields_ = [("table", C.c_uint32), ("flags", C.c_uint32), ("usable_rows", C.c_uint64), ("n_arguments", C.c_size_t),
+                ("d_inputs", C.POINTER(C.c_void_p)), ("d_inputs_spread", C.POINTER(C.c_void_p)), ("input_rows", C.POINTER(C.c_uint64)),
+                ("d_permuted_inputs", C.POINTER(C.c_void_p)), ("d_permuted_tables", C.POINTER(C.c_void_p)),
+                ("d_products", C.POINTER(C.c_void_p)), ("thetas", C.c_void_p), ("betas", C.c_void_p), ("gammas", C.c_void_p),
+                ("status", C.POINTER(C.c_uint32))]
+
+
+class ProductReport(C.Structure):
+    _fields_ = [("arguments", C.c_uint64), ("written", C.c_uint64), ("open_arguments", C.c_uint64), ("first_open", C.c_uint64),
+                ("refused_arguments", C.c_uint64), ("first_refused", C.c_uint64), ("tile_rows", C.c_uint32), ("reserved_", C.c_uint32),
+                ("kernel_ms", C.c_float), ("tiles_ms", C.c_float), ("scan_ms", C.c_float), ("write_ms", C.c_float)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -273,6 +291,7 @@ SYMBOLS = (
     "hsw_gadget_digest_batch_device", "hsw_gadget_digest_levels_device",
     "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
     "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities", "hsw_gadget_lookup_permuted",
+    "hsw_gadget_lookup_product",
 )
 
 
@@ -371,6 +390,9 @@ def lib():
         if hasattr(L, "hsw_gadget_lookup_permuted"):   # absent only in A/B builds of an earlier commit (HSW_LIB_OVERRIDE)
             L.hsw_gadget_lookup_permuted.restype = C.c_int
             L.hsw_gadget_lookup_permuted.argtypes = [vp, C.POINTER(LookupPermuted), C.POINTER(PermutedReport)]
+        if hasattr(L, "hsw_gadget_lookup_product"):    # likewise
+            L.hsw_gadget_lookup_product.restype = C.c_int
+            L.hsw_gadget_lookup_product.argtypes = [vp, C.POINTER(LookupProduct), C.POINTER(ProductReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

@@ -607,6 +607,92 @@ class Sha256DynamicConfig:
         self._ok(self.lib.hsw_gadget_lookup_permuted(self.h, C.byref(args), C.byref(rep)))
         return cols[0], cols[1], counts, {f[0]: getattr(rep, f[0]) for f in N.PermutedReport._fields_ if f[0] != "reserved_"}
 
+    def lookup_product(self, table, usable_rows, betas, gammas, inputs, permuted_input, permuted_table, thetas=None,
+                       inputs_spread=None, input_rows=None, out=None, theta_on_spread=False):
+        """hsw_gadget_lookup_product: the grand-product column Z of every argument of `table`, written on the device:
+        Z[0] = 1, Z[i+1] = Z[i] (A[i] + beta)(S[i] + gamma) / ((A'[i] + beta)(S'[i] + gamma)).  Returns (z, status,
+        report): a uint64 device tensor (arguments, usable_rows + 1, 4), the uint32 numpy status array (HSW_PRODUCT_*
+        bits per argument) and the report as a dict.  inputs (RANGE: the lookup-advice column; SPREAD: the dense
+        column), inputs_spread (SPREAD only), permuted_input, permuted_table: either a contiguous uint64 tensor
+        (arguments, rows, 4) on the engine's device or a sequence of `arguments` device addresses (ints, 16-byte
+        aligned).  input_rows: per argument, the rows of its input that are assigned (the rest count as 0 and are not
+        read); None: all usable_rows.  betas, gammas, thetas (SPREAD only): one field element per proof AS STORED, as
+        lookup_permuted takes its thetas.  out: the caller's own contiguous uint64 tensor (arguments, rows >=
+        usable_rows + 1, 4); rows beyond usable_rows are never written.  A refused argument (status & 6) is not written."""
+        import numpy as np
+        import torch
+        dev = self.engine.device
+        spread = table == N.HSW_LOOKUP_SPREAD
+        if table not in (N.HSW_LOOKUP_RANGE, N.HSW_LOOKUP_SPREAD):
+            raise ValueError("lookup_product: table must be HSW_LOOKUP_RANGE or HSW_LOOKUP_SPREAD")
+        k = self._lookup_contexts()
+        n_args = k * int(self.engine.shape.num_advice_columns) if spread else k
+        rows = 1 << int(self.engine.shape.num_bits_lookup) if spread else 1 << 16
+        u = int(usable_rows)
+        if u < rows or u > 1 << 31:
+            raise ValueError("usable_rows must be at least the table size %d and at most 2^31" % rows)
+        if input_rows is None:
+            in_rows = [u] * n_args
+        else:
+            in_rows = [int(r) for r in input_rows]
+            if len(in_rows) != n_args or any(r < 0 or r > u for r in in_rows):
+                raise ValueError("input_rows: %d values between 0 and usable_rows" % n_args)
+        if spread != (inputs_spread is not None):
+            raise ValueError("inputs_spread is the spread argument's (and required there)")
+
+        def pointers(name, t, need):
+            if isinstance(t, torch.Tensor):
+                if t.dtype != torch.uint64 or t.device != dev:
+                    raise ValueError("%s must be a uint64 tensor on %s" % (name, dev))
+                if t.dim() != 3 or t.shape[0] != n_args or t.shape[1] < max(need) or t.shape[2] != 4 or not t.is_contiguous():
+                    raise ValueError("%s must be contiguous, of shape (%d, rows >= %d, 4)" % (name, n_args, max(need)))
+                return [t.data_ptr() + a * t.shape[1] * 32 for a in range(n_args)]
+            ptrs = [int(p) for p in t]
+            if len(ptrs) != n_args or any(p == 0 or p % 16 for p in ptrs):
+                raise ValueError("%s: %d device addresses, 16-byte aligned" % (name, n_args))
+            return ptrs
+
+        cols = [pointers("inputs", inputs, in_rows)]
+        cols.append(pointers("inputs_spread", inputs_spread, in_rows) if spread else None)
+        cols.append(pointers("permuted_input", permuted_input, [u]))
+        cols.append(pointers("permuted_table", permuted_table, [u]))
+        if out is None:
+            out = torch.zeros((n_args, u + 1, 4), dtype=torch.uint64, device=dev)
+        elif not isinstance(out, torch.Tensor):
+            raise ValueError("out must be a uint64 tensor on %s" % (dev,))
+        cols.append(pointers("out", out, [u + 1]))
+
+        def challenges(name, v):
+            if v is None:
+                raise ValueError("%s: one field element per proof" % name)
+            if isinstance(v, torch.Tensor):
+                v = v.cpu().numpy()
+            if isinstance(v, np.ndarray):
+                buf = np.ascontiguousarray(v, dtype=np.uint64)
+            else:
+                buf = np.array([[(int(x) >> (64 * i)) & (2**64 - 1) for i in range(4)] for x in v], dtype=np.uint64)
+            if buf.shape != (k, 4):
+                raise ValueError("%s: one field element (4 x uint64) per proof, %d of them" % (name, k))
+            return buf
+
+        b_buf, g_buf = challenges("betas", betas), challenges("gammas", gammas)
+        if spread:
+            t_buf = challenges("thetas", thetas)
+        elif thetas is not None:
+            raise ValueError("thetas given for the range argument")
+        else:
+            t_buf = None
+        arr = [(C.c_void_p * n_args)(*c) if c is not None else None for c in cols]
+        status = np.zeros(n_args, dtype=np.uint32)
+        args = N.LookupProduct(table, N.HSW_PERMUTED_THETA_ON_SPREAD if theta_on_spread else 0, u, n_args, arr[0], arr[1],
+                               (C.c_uint64 * n_args)(*in_rows), arr[2], arr[3], arr[4],
+                               t_buf.ctypes.data if t_buf is not None else None, b_buf.ctypes.data, g_buf.ctypes.data,
+                               status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        rep = N.ProductReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the call runs on the engine's
+        self._ok(self.lib.hsw_gadget_lookup_product(self.h, C.byref(args), C.byref(rep)))
+        return out, status, {f[0]: getattr(rep, f[0]) for f in N.ProductReport._fields_ if f[0] != "reserved_"}
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

@@ -1155,6 +1155,63 @@ typedef struct hsw_permuted_report {
     float kernel_ms, prepare_ms, write_ms; uint32_t reserved_;
 } hsw_permuted_report;
 int hsw_gadget_lookup_permuted(hsw_gadget *g, const hsw_lookup_permuted *args, hsw_permuted_report *report);
+/* ---- the lookup argument's grand-product column Z, written on the device ----
+ * The third column of halo2's lookup argument, committed right after the permuted pair.  Per argument a (numbered as in
+ * hsw_lookup_permuted) of proof c, over the usable rows, every value mod p:
+ *   Z[0] = 1,   Z[i+1] = Z[i] * (A[i] + beta_c)(S[i] + gamma_c) / ((A'[i] + beta_c)(S'[i] + gamma_c)),   0 <= i < u
+ *   A[i]   the unpermuted compressed input, READ from the caller's physical column(s): RANGE the cell of d_inputs[a];
+ *          SPREAD d_inputs[a][i] * theta_c + d_inputs_spread[a][i], with HSW_PERMUTED_THETA_ON_SPREAD d_inputs[a][i] +
+ *          d_inputs_spread[a][i] * theta_c (DESIGN.md assumption A6).  Rows i >= input_rows[a] are not read and count
+ *          as 0: unassigned;
+ *   S[i]   the unpermuted table column, NOT read: val(i) for i < T and val(0) for T <= i < u, val as in
+ *          hsw_gadget_lookup_permuted (the table column's padding rows repeat row 0);
+ *   A', S' d_permuted_inputs[a] / d_permuted_tables[a]: what hsw_gadget_lookup_permuted wrote, or any the caller has.
+ * d_products[a] receives Z[0 .. u], u + 1 cells in the representation of the pass.  Z is one field element per row, so the
+ * output is fixed bit for bit.  All pointer arrays are HOST arrays (copied, not kept) of n_arguments DEVICE pointers to
+ * 32-byte cells, 16-byte aligned, in any address order; thetas (SPREAD only), betas, gammas: HOST memory, contexts x 32
+ * bytes as stored (Montgomery cells: the challenge * 2^256 mod p), the stored limbs below p.
+ * Decided on the device, per ARGUMENT (status[a], a host array of n_arguments words, may be NULL):
+ *   HSW_PRODUCT_ZERO_DENOM        some (A'[i] + beta)(S'[i] + gamma) is 0;
+ *   HSW_PRODUCT_CELL_NOT_BELOW_P  a stored cell that was read (input, A', S') is not an encoding below p;
+ *                                 either one REFUSES the argument: none of its u + 1 cells is written;
+ *   HSW_PRODUCT_OPEN              Z[u] != 1: the argument is written, its Z is what the recurrence gives.
+ * The other arguments are written; the call returns HSW_OK in all these cases and the report counts them (first_open /
+ * first_refused: the lowest such argument, ~0 where there is none; written: (u + 1) x the arguments not refused).  Every
+ * row of every column is either fully written or untouched; nothing at or beyond row u + 1, no input cell and no other
+ * byte of the caller's is ever written.  Blinding rows and the commitment are the prover's.
+ * Refused before any launch -- HSW_ERR_INVALID_ARG: usable_rows < T, a wrong n_arguments, unknown flags or table, a
+ * pointer (array or column) that is NULL or not 16-byte aligned, input_rows[a] > usable_rows, a challenge that is missing
+ * or not below p, a Z column that overlaps a column read or another Z column (byte intervals; hsw_last_error names the
+ * argument); HSW_ERR_TOO_LARGE: usable_rows above 2^31, or more than 2^31 - 1 tiles in all; HSW_ERR_UNSUPPORTED:
+ * HSW_REPR_COMPACT64 cells, a pass whose batches differ in representation.
+ * Three launches on the engine's stream, the host reads nothing in between: tiles (products of tile_rows rows each, 64
+ * bytes of scratch per tile), scan (per argument: prefix and suffix over the tiles, ONE inversion), write.  The scratch is
+ * the gadget's: grown on demand, freed by hsw_gadget_destroy.  kernel_ms = tiles_ms + scan_ms + write_ms.  Synchronous.
+ * (The call came under HSW_ABI_MINOR 1: probe for the symbol.) */
+#define HSW_PRODUCT_OPEN          1u   /* Z[u] != 1 */
+#define HSW_PRODUCT_ZERO_DENOM    2u   /* some (A'[i]+beta)(S'[i]+gamma) == 0 */
+#define HSW_PRODUCT_CELL_NOT_BELOW_P 4u/* a stored cell that was read is not an encoding below p */
+typedef struct hsw_lookup_product {
+    uint32_t table, flags;                 /* HSW_LOOKUP_RANGE | HSW_LOOKUP_SPREAD; HSW_PERMUTED_THETA_ON_SPREAD */
+    uint64_t usable_rows;                  /* u: T <= u <= 2^31 */
+    size_t n_arguments;                    /* contexts (RANGE) or contexts x num_advice_columns (SPREAD), a as in hsw_lookup_permuted */
+    const void *const *d_inputs;           /* host array of device pointers: RANGE the lookup-advice column, SPREAD the dense column */
+    const void *const *d_inputs_spread;    /* SPREAD: the spread column; NULL for RANGE */
+    const uint64_t *input_rows;            /* host, per argument, <= u; NULL = u everywhere */
+    const void *const *d_permuted_inputs;  /* A', u cells */
+    const void *const *d_permuted_tables;  /* S', u cells */
+    void *const *d_products;               /* Z, u + 1 cells each */
+    const void *thetas, *betas, *gammas;   /* host, contexts x 32 bytes as stored, below p; thetas as in hsw_lookup_permuted */
+    uint32_t *status;                      /* host, n_arguments, output; may be NULL */
+} hsw_lookup_product;
+typedef struct hsw_product_report {
+    uint64_t arguments, written;           /* written: (u + 1) x arguments actually stored */
+    uint64_t open_arguments, first_open;
+    uint64_t refused_arguments, first_refused;   /* ZERO_DENOM or CELL_NOT_BELOW_P */
+    uint32_t tile_rows, reserved_;
+    float kernel_ms, tiles_ms, scan_ms, write_ms;
+} hsw_product_report;
+int hsw_gadget_lookup_product(hsw_gadget *g, const hsw_lookup_product *args, hsw_product_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */

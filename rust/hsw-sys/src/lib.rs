@@ -357,6 +357,53 @@ pub struct hsw_permuted_report {
     pub reserved_: u32,
 }
 
+/// `hsw_gadget_lookup_product` status bit: `Z[u] != 1`; the argument is written all the same.
+pub const HSW_PRODUCT_OPEN: u32 = 1;
+/// Status bit: some `(A'[i] + beta)(S'[i] + gamma)` is zero; the argument is not written.
+pub const HSW_PRODUCT_ZERO_DENOM: u32 = 2;
+/// Status bit: a stored cell that was read is not an encoding below p; the argument is not written.
+pub const HSW_PRODUCT_CELL_NOT_BELOW_P: u32 = 4;
+
+/// Arguments of `hsw_gadget_lookup_product`: per argument (numbered as in `hsw_lookup_permuted`) the unpermuted input
+/// column(s), the permuted pair and the Z column of `usable_rows + 1` cells, as host arrays of device pointers; the
+/// challenges are host memory, one 32-byte element per proof as stored.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_lookup_product {
+    pub table: u32,
+    pub flags: u32,
+    pub usable_rows: u64,
+    pub n_arguments: usize,
+    pub d_inputs: *const *const c_void,
+    pub d_inputs_spread: *const *const c_void,
+    pub input_rows: *const u64,
+    pub d_permuted_inputs: *const *const c_void,
+    pub d_permuted_tables: *const *const c_void,
+    pub d_products: *const *mut c_void,
+    pub thetas: *const c_void,
+    pub betas: *const c_void,
+    pub gammas: *const c_void,
+    pub status: *mut u32,
+}
+
+/// Result of `hsw_gadget_lookup_product`; `first_open` / `first_refused` are `u64::MAX` where there is none.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_product_report {
+    pub arguments: u64,
+    pub written: u64,
+    pub open_arguments: u64,
+    pub first_open: u64,
+    pub refused_arguments: u64,
+    pub first_refused: u64,
+    pub tile_rows: u32,
+    pub reserved_: u32,
+    pub kernel_ms: f32,
+    pub tiles_ms: f32,
+    pub scan_ms: f32,
+    pub write_ms: f32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -632,6 +679,9 @@ extern "C" {
     /// halo2's permuted lookup columns A' and S' of every argument of one table, written on the device.
     pub fn hsw_gadget_lookup_permuted(g: *mut hsw_gadget, args: *const hsw_lookup_permuted,
                                       report: *mut hsw_permuted_report) -> c_int;
+    /// The grand-product column Z of every argument of one table, written on the device; synchronous.
+    pub fn hsw_gadget_lookup_product(g: *mut hsw_gadget, args: *const hsw_lookup_product,
+                                     report: *mut hsw_product_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

@@ -269,6 +269,20 @@ class ProductReport(C.Structure):
                 ("kernel_ms", C.c_float), ("tiles_ms", C.c_float), ("scan_ms", C.c_float), ("write_ms", C.c_float)]
 
 
+class PermutationProduct(C.Structure):
+    """hsw_permutation_product: the permutation argument's grand products of every proof (hsw_gadget_permutation_product)."""
+    _fields_ = [("flags", C.c_uint32), ("chunk_columns", C.c_uint32), ("usable_rows", C.c_uint64), ("n_columns", C.c_size_t),
+                ("d_columns", C.POINTER(C.c_void_p)), ("column_rows", C.POINTER(C.c_uint64)), ("d_sigmas", C.POINTER(C.c_void_p)),
+                ("d_products", C.POINTER(C.c_void_p)), ("betas", C.c_void_p), ("gammas", C.c_void_p), ("omega", C.c_void_p),
+                ("delta", C.c_void_p), ("status", C.POINTER(C.c_uint32))]
+
+
+class PermutationReport(C.Structure):
+    _fields_ = [("proofs", C.c_uint64), ("products", C.c_uint64), ("written", C.c_uint64), ("open_proofs", C.c_uint64),
+                ("first_open", C.c_uint64), ("refused_proofs", C.c_uint64), ("first_refused", C.c_uint64), ("tile_rows", C.c_uint32),
+                ("reserved_", C.c_uint32), ("kernel_ms", C.c_float), ("tiles_ms", C.c_float), ("scan_ms", C.c_float), ("write_ms", C.c_float)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -291,7 +305,7 @@ SYMBOLS = (
     "hsw_gadget_digest_batch_device", "hsw_gadget_digest_levels_device",
     "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
     "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities", "hsw_gadget_lookup_permuted",
-    "hsw_gadget_lookup_product",
+    "hsw_gadget_lookup_product", "hsw_gadget_permutation_product",
 )
 
 
@@ -393,6 +407,9 @@ def lib():
         if hasattr(L, "hsw_gadget_lookup_product"):    # likewise
             L.hsw_gadget_lookup_product.restype = C.c_int
             L.hsw_gadget_lookup_product.argtypes = [vp, C.POINTER(LookupProduct), C.POINTER(ProductReport)]
+        if hasattr(L, "hsw_gadget_permutation_product"):   # likewise
+            L.hsw_gadget_permutation_product.restype = C.c_int
+            L.hsw_gadget_permutation_product.argtypes = [vp, C.POINTER(PermutationProduct), C.POINTER(PermutationReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

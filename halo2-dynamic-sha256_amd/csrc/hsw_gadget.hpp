@@ -17,10 +17,10 @@
 // HSW_GADGET_WHOLE_DIGEST (hsw_frame.hpp / hsw_frame_kernel, assumption A4);
 // without it only their *values* are produced (AssignedHashResult).
 //
-// Implemented in seven translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
+// Implemented in eight translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
 // call), hsw_gadget_context.cpp (Context: buffers, layouts, bind / unbind, the jump table), hsw_gadget_digest.cpp (the
 // digest paths and the ties), hsw_gadget_lookup.cpp (the lookup entries of a pass, listed and counted),
-// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
+// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z), hsw_gadget_permutation.cpp (the permutation argument's grand products) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
 #ifndef HSW_GADGET_HPP
 #define HSW_GADGET_HPP
 
@@ -383,6 +383,8 @@ struct hsw_gadget {
     size_t permuted_cap = 0;                        // and value arrays on the device, in bytes; grown and freed like d_pairs
     void *d_product = nullptr;                      // hsw_gadget_lookup_product (hsw_gadget_product.cpp): status words, arguments,
     size_t product_cap = 0;                         // challenges and tile products on the device, in bytes; grown and freed like d_pairs
+    void *d_permutation = nullptr;                  // hsw_gadget_permutation_product (hsw_gadget_permutation.cpp): status words, columns,
+    size_t permutation_cap = 0;                     // staged constants and tile products on the device, in bytes; grown and freed like d_pairs
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

@@ -693,6 +693,86 @@ class Sha256DynamicConfig:
         self._ok(self.lib.hsw_gadget_lookup_product(self.h, C.byref(args), C.byref(rep)))
         return out, status, {f[0]: getattr(rep, f[0]) for f in N.ProductReport._fields_ if f[0] != "reserved_"}
 
+    def permutation_product(self, usable_rows, chunk_columns, betas, gammas, omega, delta, columns, sigmas, column_rows=None,
+                            out=None):
+        """hsw_gadget_permutation_product: the permutation argument's grand products of every proof, written on the
+        device: per chunk s of chunk_columns columns Z_s[i+1] = Z_s[i] prod_j (v_j[i] + beta delta^j omega^i + gamma) /
+        prod_j (v_j[i] + beta sigma_j[i] + gamma), Z_0[0] = 1, Z_s[0] = Z_{s-1}[usable_rows].  Returns (z, status,
+        report): a uint64 device tensor (proofs, S, usable_rows + 1, 4), the uint32 numpy status array (HSW_PRODUCT_*
+        bits per proof) and the report as a dict.  sigmas: the m permutation columns of the key, shared by the proofs: a
+        contiguous uint64 tensor (m, rows >= usable_rows, 4) on the engine's device or a sequence of m device addresses
+        (ints, 16-byte aligned).  columns: the value columns in the permutation's order: a contiguous uint64 tensor
+        (proofs, m, rows, 4) or a sequence of proofs * m device addresses, [c * m + j].  column_rows: proofs * m values,
+        the rows of each column that are assigned (the rest count as 0 and are not read); None: all usable_rows.
+        betas, gammas: one field element per proof AS STORED, as lookup_product takes them; omega, delta: one element
+        each, as stored.  out: the caller's own contiguous uint64 tensor (proofs, S, rows >= usable_rows + 1, 4); rows
+        beyond usable_rows are never written.  A refused proof (status & 6) is not written."""
+        import numpy as np
+        import torch
+        dev = self.engine.device
+        k, u, chunk = self._lookup_contexts(), int(usable_rows), int(chunk_columns)
+        if u < 1 or u > 1 << 31:
+            raise ValueError("usable_rows must be at least 1 and at most 2^31")
+        if chunk < 1 or chunk > 0xffffffff:
+            raise ValueError("chunk_columns must be at least 1")
+
+        def pointers(name, t, lead, need):
+            """device addresses of the prod(lead) columns of t, which must hold `need` rows"""
+            n = int(np.prod(lead))
+            if isinstance(t, torch.Tensor):
+                if t.dtype != torch.uint64 or t.device != dev:
+                    raise ValueError("%s must be a uint64 tensor on %s" % (name, dev))
+                if t.dim() != len(lead) + 2 or tuple(t.shape[:len(lead)]) != tuple(lead) or t.shape[-2] < need or t.shape[-1] != 4 or not t.is_contiguous():
+                    raise ValueError("%s must be contiguous, of shape (%s, rows >= %d, 4)" % (name, ", ".join(map(str, lead)), need))
+                return [t.data_ptr() + a * t.shape[-2] * 32 for a in range(n)]
+            ptrs = [int(p) for p in t]
+            if len(ptrs) != n or any(p == 0 or p % 16 for p in ptrs):
+                raise ValueError("%s: %d device addresses, 16-byte aligned" % (name, n))
+            return ptrs
+
+        m = int(sigmas.shape[0]) if isinstance(sigmas, torch.Tensor) and sigmas.dim() else len(sigmas)
+        if m < 1:
+            raise ValueError("sigmas: at least one column")
+        s_chunks = (m + chunk - 1) // chunk
+        if column_rows is None:
+            rows = [u] * (k * m)
+        else:
+            rows = [int(r) for r in column_rows]
+            if len(rows) != k * m or any(r < 0 or r > u for r in rows):
+                raise ValueError("column_rows: %d values between 0 and usable_rows" % (k * m))
+        sig = pointers("sigmas", sigmas, (m,), u)
+        cols = pointers("columns", columns, (k, m), max(rows))
+        if out is None:
+            out = torch.zeros((k, s_chunks, u + 1, 4), dtype=torch.uint64, device=dev)
+        elif not isinstance(out, torch.Tensor):
+            raise ValueError("out must be a uint64 tensor on %s" % (dev,))
+        zs = pointers("out", out, (k, s_chunks), u + 1)
+
+        def elements(name, v, n):
+            if v is None:
+                raise ValueError("%s: %d field element(s)" % (name, n))
+            if isinstance(v, torch.Tensor):
+                v = v.cpu().numpy()
+            if isinstance(v, np.ndarray):
+                buf = np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4) if v.size == 4 * n else np.zeros((0, 4), dtype=np.uint64)
+            else:
+                v = [v] if isinstance(v, int) else list(v)
+                buf = np.array([[(int(x) >> (64 * i)) & (2**64 - 1) for i in range(4)] for x in v], dtype=np.uint64).reshape(-1, 4)
+            if buf.shape != (n, 4):
+                raise ValueError("%s: %d field element(s) of 4 x uint64" % (name, n))
+            return buf
+
+        b_buf, g_buf = elements("betas", betas, k), elements("gammas", gammas, k)
+        o_buf, d_buf = elements("omega", omega, 1), elements("delta", delta, 1)
+        status = np.zeros(k, dtype=np.uint32)
+        args = N.PermutationProduct(0, chunk, u, m, (C.c_void_p * (k * m))(*cols), (C.c_uint64 * (k * m))(*rows), (C.c_void_p * m)(*sig),
+                                    (C.c_void_p * (k * s_chunks))(*zs), b_buf.ctypes.data, g_buf.ctypes.data, o_buf.ctypes.data,
+                                    d_buf.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        rep = N.PermutationReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the call runs on the engine's
+        self._ok(self.lib.hsw_gadget_permutation_product(self.h, C.byref(args), C.byref(rep)))
+        return out, status, {f[0]: getattr(rep, f[0]) for f in N.PermutationReport._fields_ if f[0] != "reserved_"}
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

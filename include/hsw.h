@@ -1212,6 +1212,63 @@ typedef struct hsw_product_report {
     float kernel_ms, tiles_ms, scan_ms, write_ms;
 } hsw_product_report;
 int hsw_gadget_lookup_product(hsw_gadget *g, const hsw_lookup_product *args, hsw_product_report *report);
+/* ---- the permutation argument's grand products Z, written on the device ----
+ * What halo2 commits after the lookup permuted pairs and before the lookup Z (permutation::prover): the columns that
+ * enforce the copy constraints, those hsw_gadget_ties lists among them.  The permutation has m = n_columns columns in its
+ * own order, in S = ceil(m / L) chunks of L = chunk_columns (halo2's cs_degree - 2; the last chunk may be shorter).  For
+ * proof c of contexts, over the u = usable_rows rows, every value mod p, chunk s holding the columns j with
+ * s L <= j < min(m, (s + 1) L):
+ *   num_s[i] = prod_j (v_{c,j}[i] + beta_c * delta^j * omega^i + gamma_c)
+ *   den_s[i] = prod_j (v_{c,j}[i] + beta_c * sigma_j[i]         + gamma_c)
+ *   Z_{c,0}[0] = 1,   Z_{c,s}[0] = Z_{c,s-1}[u]  (s > 0),   Z_{c,s}[i+1] = Z_{c,s}[i] * num_s[i] / den_s[i],   0 <= i < u
+ *   v_{c,j}  the caller's physical column d_columns[c*m + j], 32-byte cells in the representation of the pass.  Rows
+ *            i >= column_rows[c*m + j] are not read and count as 0 (a gadget's image columns are shorter than u);
+ *   sigma_j  the key's permutation column d_sigmas[j], u cells in the representation of the pass, all read, SHARED by
+ *            the proofs (K proofs of one circuit have one proving key).  Building it from copy constraints is keygen
+ *            and stays the caller's;
+ *   omega, delta  the caller's: the library does not check that omega is a root of unity and pins no constant of halo2's.
+ * d_products[c*S + s] receives Z_{c,s}[0 .. u], u + 1 cells in the representation of the pass.  Z is one field element
+ * per cell, so the output is fixed bit for bit.  All pointer arrays are HOST arrays (copied, not kept) of DEVICE pointers,
+ * 16-byte aligned, in any address order; betas, gammas: HOST memory, contexts x 32 bytes as stored (Montgomery cells: the
+ * challenge * 2^256 mod p); omega, delta: HOST memory, 32 bytes each as stored; all stored limbs below p.
+ * Decided on the device, per PROOF, because the chunks of a proof chain (status[c], a host array of contexts words, may
+ * be NULL), with the bits of hsw_gadget_lookup_product:
+ *   HSW_PRODUCT_ZERO_DENOM        some den_s[i] is 0;
+ *   HSW_PRODUCT_CELL_NOT_BELOW_P  a stored cell that was read (value or sigma) is not an encoding below p;
+ *                                 either one REFUSES the proof: none of its S columns is written;
+ *   HSW_PRODUCT_OPEN              Z_{c,S-1}[u] != 1: the proof is written, its Z is what the recurrence gives.
+ * The other proofs are written; the call returns HSW_OK in all these cases and the report counts them (first_open /
+ * first_refused: the lowest such proof, ~0 where there is none).  Every row of every Z column is either fully written or
+ * untouched; nothing at or beyond row u + 1, no input cell and no other byte of the caller's is ever written.  Blinding
+ * rows and the commitment are the prover's.
+ * Refused before any launch -- HSW_ERR_INVALID_ARG: usable_rows, n_columns or chunk_columns 0, unknown flags, a pointer
+ * (array or column) that is NULL or not 16-byte aligned, column_rows[k] > usable_rows, a challenge, omega or delta that is
+ * missing or not below p, a Z column that overlaps a column read or another Z column (byte intervals; hsw_last_error
+ * names the proof); HSW_ERR_TOO_LARGE: usable_rows above 2^31, or more than 2^31 - 1 tiles (or columns) in all;
+ * HSW_ERR_UNSUPPORTED: HSW_REPR_COMPACT64 cells, a pass whose batches differ in representation.
+ * Three launches on the engine's stream, the host reads nothing in between: tiles (per proof, chunk and tile_rows rows:
+ * two products, 64 bytes of scratch), scan (per proof over the tiles of all its chunks, ONE inversion), write.  The
+ * scratch is the gadget's: grown on demand, freed by hsw_gadget_destroy.  kernel_ms = tiles_ms + scan_ms + write_ms.
+ * Synchronous.  (The call came under HSW_ABI_MINOR 1: probe for the symbol.) */
+typedef struct hsw_permutation_product {
+    uint32_t flags, chunk_columns;         /* flags: 0; chunk_columns: cs_degree - 2, >= 1 */
+    uint64_t usable_rows;                  /* u: 1 <= u <= 2^31 */
+    size_t n_columns;                      /* m, per proof, in the permutation's column order */
+    const void *const *d_columns;          /* host array, contexts x m device pointers, [c*m + j] */
+    const uint64_t *column_rows;           /* host, contexts x m, <= u; NULL = u everywhere */
+    const void *const *d_sigmas;           /* host array, m device pointers, u cells each, shared by the proofs */
+    void *const *d_products;               /* host array, contexts x S device pointers, [c*S + s], u + 1 cells each */
+    const void *betas, *gammas;            /* host, contexts x 32 bytes as stored, below p */
+    const void *omega, *delta;             /* host, 32 bytes each as stored, below p */
+    uint32_t *status;                      /* host, contexts words, output; may be NULL */
+} hsw_permutation_product;
+typedef struct hsw_permutation_report {
+    uint64_t proofs, products, written;    /* products = contexts x S; written = (u + 1) x S x proofs not refused */
+    uint64_t open_proofs, first_open, refused_proofs, first_refused;   /* first_*: ~0 where there is none */
+    uint32_t tile_rows, reserved_;
+    float kernel_ms, tiles_ms, scan_ms, write_ms;
+} hsw_permutation_report;
+int hsw_gadget_permutation_product(hsw_gadget *g, const hsw_permutation_product *args, hsw_permutation_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */

@@ -404,6 +404,47 @@ pub struct hsw_product_report {
     pub write_ms: f32,
 }
 
+/// Arguments of `hsw_gadget_permutation_product`: per proof `n_columns` value columns in the permutation's order (host
+/// array of device pointers, `[c * m + j]`), the key's `n_columns` sigma columns shared by the proofs, and per proof
+/// `S = ceil(n_columns / chunk_columns)` Z columns of `usable_rows + 1` cells; challenges, `omega` and `delta` are host
+/// memory, 32 bytes per element as stored.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_permutation_product {
+    pub flags: u32,
+    pub chunk_columns: u32,
+    pub usable_rows: u64,
+    pub n_columns: usize,
+    pub d_columns: *const *const c_void,
+    pub column_rows: *const u64,
+    pub d_sigmas: *const *const c_void,
+    pub d_products: *const *mut c_void,
+    pub betas: *const c_void,
+    pub gammas: *const c_void,
+    pub omega: *const c_void,
+    pub delta: *const c_void,
+    pub status: *mut u32,
+}
+
+/// Result of `hsw_gadget_permutation_product`; `first_open` / `first_refused` are `u64::MAX` where there is none.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_permutation_report {
+    pub proofs: u64,
+    pub products: u64,
+    pub written: u64,
+    pub open_proofs: u64,
+    pub first_open: u64,
+    pub refused_proofs: u64,
+    pub first_refused: u64,
+    pub tile_rows: u32,
+    pub reserved_: u32,
+    pub kernel_ms: f32,
+    pub tiles_ms: f32,
+    pub scan_ms: f32,
+    pub write_ms: f32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -682,6 +723,10 @@ extern "C" {
     /// The grand-product column Z of every argument of one table, written on the device; synchronous.
     pub fn hsw_gadget_lookup_product(g: *mut hsw_gadget, args: *const hsw_lookup_product,
                                      report: *mut hsw_product_report) -> c_int;
+    /// The permutation argument's grand products Z of every proof, written on the device; synchronous.  Status bits
+    /// per proof: `HSW_PRODUCT_*`.
+    pub fn hsw_gadget_permutation_product(g: *mut hsw_gadget, args: *const hsw_permutation_product,
+                                          report: *mut hsw_permutation_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

@@ -283,6 +283,22 @@ class PermutationReport(C.Structure):
                 ("reserved_", C.c_uint32), ("kernel_ms", C.c_float), ("tiles_ms", C.c_float), ("scan_ms", C.c_float), ("write_ms", C.c_float)]
 
 
+HSW_NTT_SHIFT_AFTER, HSW_NTT_CELL_NOT_BELOW_P = 1, 4
+
+
+class Ntt(C.Structure):
+    """hsw_ntt: the Fr NTT of device columns (hsw_gadget_ntt)."""
+    _fields_ = [("flags", C.c_uint32), ("log_n", C.c_uint32), ("pass_log", C.c_uint32), ("reserved_", C.c_uint32), ("n_columns", C.c_size_t),
+                ("d_inputs", C.POINTER(C.c_void_p)), ("input_rows", C.POINTER(C.c_uint64)), ("d_outputs", C.POINTER(C.c_void_p)),
+                ("omega", C.c_void_p), ("shift", C.c_void_p), ("scale", C.c_void_p), ("status", C.POINTER(C.c_uint32))]
+
+
+class NttReport(C.Structure):
+    _fields_ = [("columns", C.c_uint64), ("written", C.c_uint64), ("refused_columns", C.c_uint64), ("first_refused", C.c_uint64),
+                ("twiddle_bytes", C.c_uint64), ("scratch_bytes", C.c_uint64), ("launches", C.c_uint32), ("pass_log", C.c_uint32),
+                ("kernel_ms", C.c_float), ("twiddle_ms", C.c_float)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -305,7 +321,7 @@ SYMBOLS = (
     "hsw_gadget_digest_batch_device", "hsw_gadget_digest_levels_device",
     "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
     "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities", "hsw_gadget_lookup_permuted",
-    "hsw_gadget_lookup_product", "hsw_gadget_permutation_product",
+    "hsw_gadget_lookup_product", "hsw_gadget_permutation_product", "hsw_gadget_ntt",
 )
 
 
@@ -410,6 +426,9 @@ def lib():
         if hasattr(L, "hsw_gadget_permutation_product"):   # likewise
             L.hsw_gadget_permutation_product.restype = C.c_int
             L.hsw_gadget_permutation_product.argtypes = [vp, C.POINTER(PermutationProduct), C.POINTER(PermutationReport)]
+        if hasattr(L, "hsw_gadget_ntt"):   # likewise
+            L.hsw_gadget_ntt.restype = C.c_int
+            L.hsw_gadget_ntt.argtypes = [vp, C.POINTER(Ntt), C.POINTER(NttReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

@@ -17,10 +17,10 @@
 // HSW_GADGET_WHOLE_DIGEST (hsw_frame.hpp / hsw_frame_kernel, assumption A4);
 // without it only their *values* are produced (AssignedHashResult).
 //
-// Implemented in eight translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
+// Implemented in nine translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
 // call), hsw_gadget_context.cpp (Context: buffers, layouts, bind / unbind, the jump table), hsw_gadget_digest.cpp (the
 // digest paths and the ties), hsw_gadget_lookup.cpp (the lookup entries of a pass, listed and counted),
-// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z), hsw_gadget_permutation.cpp (the permutation argument's grand products) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
+// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z), hsw_gadget_permutation.cpp (the permutation argument's grand products), hsw_gadget_ntt.cpp (the Fr NTT of device columns) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
 #ifndef HSW_GADGET_HPP
 #define HSW_GADGET_HPP
 
@@ -385,6 +385,13 @@ struct hsw_gadget {
     size_t product_cap = 0;                         // challenges and tile products on the device, in bytes; grown and freed like d_pairs
     void *d_permutation = nullptr;                  // hsw_gadget_permutation_product (hsw_gadget_permutation.cpp): status words, columns,
     size_t permutation_cap = 0;                     // staged constants and tile products on the device, in bytes; grown and freed like d_pairs
+    void *d_ntt = nullptr;                          // hsw_gadget_ntt (hsw_gadget_ntt.cpp): status words, columns, staged constants and
+    size_t ntt_cap = 0;                             // the points between launches, in bytes; grown and freed like d_pairs
+    // the tables of the powers of the roots hsw_gadget_ntt was last called with: root in Montgomery form, log_n, the
+    // device table (2^(log_n - 1) cells); stamp orders them by last use (0: free).  Freed by hsw_gadget_destroy
+    struct NttTable { uint32_t root[8]; uint32_t log_n; void *d_table; size_t bytes; uint64_t stamp; };
+    NttTable ntt_tables[4] = {};
+    uint64_t ntt_stamp = 0;
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

@@ -1,0 +1,220 @@
+// hsw_gadget_ntt.cpp -- the Fr NTT of device columns (include/hsw.h, "the Fr NTT of device columns"): every refusal
+// decided on the host, omega, shift and scale brought into Montgomery form and staged as windows and tile tables
+// (hsw_ntt_value.hpp), the table of omega's powers built or found in the gadget's cache, then the launches of
+// hsw_ntt.hip, group of columns by group.  A translation unit of its own: only the entry point below refers to those
+// kernels.
+#include "hsw_gadget_launch.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "hsw_nounwind.hpp"
+#include "hsw_ntt.h"
+
+namespace {
+
+const size_t NTT_SCRATCH_BYTES = (size_t)1 << 30;              // the points of a group of columns between launches
+const size_t NTT_GRID_COLUMNS = 65535;                         // blockIdx.y
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct Events {                                     // the stage boundaries of one call
+    std::vector<hipEvent_t> ev;
+    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+    hipError_t record(hipStream_t s) {
+        hipEvent_t e = nullptr;
+        hipError_t he = hipEventCreate(&e);
+        if (he != hipSuccess) return he;
+        ev.push_back(e);
+        return hipEventRecord(e, s);
+    }
+};
+
+struct Interval { uintptr_t lo, hi; size_t column; bool out; };   // bytes [lo, hi) that a column writes or reads
+
+int fail_column(hsw_engine *e, int status, const char *what, size_t b) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "column %zu: %s", b, what);
+    return hsw_engine_fail(e, status, buf);
+}
+
+bool load_below_p(hsw::PFe &x, const void *stored) {
+    std::memcpy(&x, stored, 32);
+    return hsw::pfe_below_p(x);
+}
+
+}  // namespace
+
+extern "C" int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report *report) try {
+    if (!g || !args || !report) return HSW_ERR_INVALID_ARG;
+    std::memset(report, 0, sizeof *report);
+    report->first_refused = ~0ull;
+    hsw::Context &c = *g->ctx;
+    hsw_engine *e = c.engine;
+    const size_t n = args->n_columns;
+    const uint32_t L = args->log_n;
+    if (n == 0) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "n_columns is at least 1");
+    if (args->flags & ~HSW_NTT_SHIFT_AFTER) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "unknown flag");
+    if (L < 1 || L > hsw::NTT_MAX_LOG) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "log_n is 1 .. 28");
+    hsw::NttPlan plan;
+    if (!hsw::ntt_plan(L, args->pass_log, plan)) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "pass_log is 0 .. 10");
+    if (!args->d_inputs || !args->d_outputs) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "a column pointer array is NULL");
+    const uint64_t N = 1ull << L;
+    std::vector<Interval> iv;
+    iv.reserve(2 * n);
+    for (size_t b = 0; b < n; b++) {
+        const uint64_t rows = args->input_rows ? args->input_rows[b] : N;
+        if (rows > N) return fail_column(e, HSW_ERR_INVALID_ARG, "input_rows above 2^log_n", b);
+        const uintptr_t in = reinterpret_cast<uintptr_t>(args->d_inputs[b]), out = reinterpret_cast<uintptr_t>(args->d_outputs[b]);
+        if (!in || (in & 15u)) return fail_column(e, HSW_ERR_INVALID_ARG, "an input pointer that is NULL or not 16-byte aligned", b);
+        if (!out || (out & 15u)) return fail_column(e, HSW_ERR_INVALID_ARG, "an output pointer that is NULL or not 16-byte aligned", b);
+        iv.push_back(Interval{out, out + (uintptr_t)N * HSW_CELL_BYTES, b, true});
+        if (rows && in != out) iv.push_back(Interval{in, in + (uintptr_t)rows * HSW_CELL_BYTES, b, false});   // (in place: the output's interval stands for both)
+    }
+    // an output may overlap neither another output nor an input that is not its own in place: one sweep in address
+    // order, with the furthest end of the outputs (and whose it is) and of all intervals seen so far
+    std::sort(iv.begin(), iv.end(), [](const Interval &x, const Interval &y) { return x.lo < y.lo; });
+    uintptr_t end_out = 0, end_any = 0;
+    size_t out_column = 0;
+    for (const Interval &x : iv) {
+        if (x.out ? x.lo < end_any : x.lo < end_out)
+            return fail_column(e, HSW_ERR_INVALID_ARG, "its output overlaps an input that is not its own in place, or another output", x.out ? x.column : out_column);
+        if (x.out && x.hi > end_out) { end_out = x.hi; out_column = x.column; }
+        end_any = std::max(end_any, x.hi);
+    }
+    if (!args->omega) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "omega is NULL");
+    uint32_t repr = 0;
+    if (hsw::pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
+    if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "32-byte cells only");
+    const bool mont = (repr & HSW_REPR_MONTGOMERY) != 0;
+    hsw::PFe omega, shift = hsw::fr_zero(), scale = hsw::fr_zero();
+    if (!load_below_p(omega, args->omega) || (args->shift && !load_below_p(shift, args->shift)) || (args->scale && !load_below_p(scale, args->scale)))
+        return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "omega, shift or scale whose stored limbs are not below p");
+    omega = hsw::ntt_to_mont(omega, mont);
+    if (!hsw::ntt_root_is_primitive(omega, L)) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "omega is not a primitive 2^log_n-th root of unity");
+    if (args->shift) shift = hsw::ntt_to_mont(shift, mont);
+    if (args->scale) scale = hsw::ntt_to_mont(scale, mont);
+    const bool shift_in = args->shift && !(args->flags & HSW_NTT_SHIFT_AFTER);
+    const uint32_t out_mode = args->shift && (args->flags & HSW_NTT_SHIFT_AFTER) ? hsw::NTT_OUT_TABLE : args->scale ? hsw::NTT_OUT_SCALE : hsw::NTT_OUT_PLAIN;
+    const uint32_t n_pass = plan.n_pass;
+    const hsw::NttPass pass0 = hsw::ntt_pass(plan, 0), pass_last = hsw::ntt_pass(plan, n_pass - 1);
+    // columns in groups whose points between launches fit the scratch
+    const size_t column_bytes = (size_t)N * HSW_CELL_BYTES;
+    size_t group = std::min(n, NTT_GRID_COLUMNS);
+    if (n_pass > 1) group = std::min(group, std::max<size_t>(1, NTT_SCRATCH_BYTES / column_bytes));
+    // device staging: [status words][columns][shift's windows][tile table in][tile table out][omega's windows][points]
+    const size_t tile = (size_t)1 << hsw::NTT_TILE_LOG;
+    const size_t off_cols = align256(n * sizeof(uint32_t)), off_win = align256(off_cols + n * sizeof(hsw::NttColumn));
+    const size_t off_in = align256(off_win + sizeof(hsw::NttWindows)), off_out = align256(off_in + tile * sizeof(hsw::PFe));
+    const size_t off_tw = align256(off_out + tile * sizeof(hsw::PFe)), off_points = align256(off_tw + sizeof(hsw::NttWindows));
+    const size_t scratch_bytes = n_pass > 1 ? group * column_bytes : 0, bytes = off_points + scratch_bytes;
+    EngineScope es(e);
+    if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
+    if (bytes > g->ntt_cap) {                                // (every earlier call has been waited for: nothing reads the old one)
+        void *p = nullptr;
+        const hipError_t he = hipMalloc(&p, bytes);
+        if (he != hipSuccess) return hsw::hip_status(he);
+        (void)hipFree(g->d_ntt);
+        g->d_ntt = p; g->ntt_cap = bytes;
+    }
+    // the table of omega's powers: the cache's, or a new one in the slot that is free or was used longest ago
+    const size_t table_cells = (size_t)1 << (L - 1);
+    hsw_gadget::NttTable *table = nullptr;
+    for (hsw_gadget::NttTable &t : g->ntt_tables)
+        if (t.stamp && t.log_n == L && std::memcmp(t.root, omega.l, 32) == 0) table = &t;
+    const bool cached = table != nullptr;
+    if (!cached) {
+        table = &g->ntt_tables[0];
+        for (hsw_gadget::NttTable &t : g->ntt_tables)
+            if (t.stamp < table->stamp) table = &t;
+        void *p = nullptr;                                   // (first the new one: a failure loses no table that is still good)
+        const hipError_t he = hipMalloc(&p, table_cells * sizeof(hsw::PFe));
+        if (he != hipSuccess) return hsw::hip_status(he);
+        (void)hipFree(table->d_table);
+        *table = hsw_gadget::NttTable{};
+        table->d_table = p; table->bytes = table_cells * sizeof(hsw::PFe); table->log_n = L;
+        std::memcpy(table->root, omega.l, 32);
+    }
+    table->stamp = ++g->ntt_stamp;
+    uint8_t *d = static_cast<uint8_t *>(g->d_ntt);
+    std::vector<uint8_t> host(off_points, 0);                // (the status words start at 0)
+    for (size_t b = 0; b < n; b++) {
+        hsw::NttColumn nc{};
+        nc.in = static_cast<const uint4 *>(args->d_inputs[b]);
+        nc.out = static_cast<uint4 *>(args->d_outputs[b]);
+        nc.scratch = reinterpret_cast<uint4 *>(d + off_points + (b % group) * column_bytes);
+        nc.rows = (uint32_t)(args->input_rows ? args->input_rows[b] : N);
+        std::memcpy(host.data() + off_cols + b * sizeof nc, &nc, sizeof nc);
+    }
+    if (shift_in || out_mode == hsw::NTT_OUT_TABLE) {
+        hsw::NttWindows win;
+        hsw::ntt_stage_windows(shift, win);
+        std::memcpy(host.data() + off_win, &win, sizeof win);
+        // g^(offset) of every place of a tile: where launch 0 loads from, or where the last launch stores to (times c)
+        std::vector<hsw::PFe> tab(tile);
+        for (uint32_t l = 0; l < tile; l++) {
+            if (shift_in) tab[l] = hsw::ntt_power(win, hsw::ntt_offset(pass0, l));
+            else {
+                const uint32_t i = hsw::ntt_out_index(plan, hsw::ntt_offset(pass_last, hsw::ntt_store_local(pass_last, l)));
+                tab[l] = hsw::ntt_power(win, i & (uint32_t)(N - 1));
+                if (args->scale) tab[l] = hsw::fr_mont_mul(tab[l], scale);
+            }
+        }
+        std::memcpy(host.data() + (shift_in ? off_in : off_out), tab.data(), tile * sizeof(hsw::PFe));
+    }
+    if (!cached) {
+        hsw::NttWindows win;
+        hsw::ntt_stage_windows(omega, win);
+        std::memcpy(host.data() + off_tw, &win, sizeof win);
+    }
+    hsw::NttParams p{};
+    p.plan = plan;
+    p.twiddle = static_cast<const hsw::PFe *>(table->d_table);
+    p.shift = reinterpret_cast<const hsw::NttWindows *>(d + off_win);
+    p.tile_in = reinterpret_cast<const hsw::PFe *>(d + off_in);
+    p.tile_out = reinterpret_cast<const hsw::PFe *>(d + off_out);
+    p.scale = scale;
+    p.shift_in = shift_in ? 1u : 0u;
+    p.out_mode = out_mode;
+    const hipStream_t stream = es.stream;
+    Events ev;
+    hipError_t he = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess) he = ev.record(stream);
+    if (he == hipSuccess && !cached)
+        he = hsw::launch_ntt_twiddles(static_cast<hsw::PFe *>(table->d_table), reinterpret_cast<const hsw::NttWindows *>(d + off_tw), (uint32_t)table_cells, stream);
+    if (he == hipSuccess) he = ev.record(stream);
+    for (size_t b0 = 0; he == hipSuccess && b0 < n; b0 += group) {
+        p.cols = reinterpret_cast<const hsw::NttColumn *>(d + off_cols) + b0;
+        p.status = reinterpret_cast<uint32_t *>(d) + b0;
+        for (uint32_t k = 0; he == hipSuccess && k < n_pass; k++) {
+            p.pass = hsw::ntt_pass(plan, k);
+            he = hsw::launch_ntt_pass(p, (uint32_t)std::min(group, n - b0), stream);
+        }
+    }
+    if (he == hipSuccess) he = ev.record(stream);
+    std::vector<uint32_t> status(n, 0);
+    if (he == hipSuccess) he = hipMemcpyAsync(status.data(), d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    float ms[2] = {0, 0};
+    for (size_t i = 0; he == hipSuccess && i < 2; i++) he = hipEventElapsedTime(&ms[i], ev.ev[i], ev.ev[i + 1]);
+    e->timed = false;
+    if (he != hipSuccess) {
+        if (!cached) table->stamp = 0;                       // (the table may not have been built: not to be found again)
+        return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+    }
+    report->twiddle_ms = cached ? 0.0f : ms[0];
+    report->kernel_ms = ms[1];
+    report->columns = n;
+    report->twiddle_bytes = table->bytes;
+    report->scratch_bytes = scratch_bytes;
+    report->launches = n_pass;
+    report->pass_log = args->pass_log ? args->pass_log : (uint32_t)hsw::NTT_TILE_LOG;
+    for (size_t b = 0; b < n; b++) {
+        status[b] &= hsw::NTT_CELL_NOT_BELOW_P;
+        if (status[b]) { if (!report->refused_columns++) report->first_refused = b; }
+        else report->written += N;
+    }
+    if (args->status) std::memcpy(args->status, status.data(), n * sizeof(uint32_t));
+    return HSW_OK;
+} HSW_NO_UNWIND

@@ -773,6 +773,81 @@ class Sha256DynamicConfig:
         self._ok(self.lib.hsw_gadget_permutation_product(self.h, C.byref(args), C.byref(rep)))
         return out, status, {f[0]: getattr(rep, f[0]) for f in N.PermutationReport._fields_ if f[0] != "reserved_"}
 
+    def ntt(self, log_n, omega, columns, out=None, input_rows=None, shift=None, scale=None, shift_after=False, pass_log=0):
+        """hsw_gadget_ntt: the Fr NTT of size N = 2^log_n of device columns, natural order in and out:
+        out[i] = scale * sum_j a[j] shift^j omega^(i j), or with shift_after scale * shift^i * sum_j a[j] omega^(i j).
+        Returns (out, status, report): a uint64 device tensor (columns, N, 4), the uint32 numpy status array
+        (HSW_NTT_CELL_NOT_BELOW_P per column: that column was not written) and the report as a dict.  columns: a
+        contiguous uint64 tensor (columns, rows, 4) on the engine's device or a sequence of device addresses (ints,
+        16-byte aligned).  input_rows: per column, the rows that are read (the rest count as 0); None: all N.  omega,
+        shift, scale: one field element each AS STORED, as permutation_product takes its omega; shift, scale None: 1.
+        halo2's lagrange_to_coeff: omega^-1, scale 1/n; coeff_to_extended: omega_ext, shift zeta, input_rows n;
+        extended_to_coeff: omega_ext^-1, scale 1/N, shift 1/zeta, shift_after.  out: the caller's own contiguous uint64
+        tensor (columns, rows >= N, 4) -- `columns` itself transforms in place -- or a sequence of device addresses
+        (then None is returned in its place); rows beyond N are never written.  pass_log: 0, or the most points
+        (log2, 1 .. 10) a launch transforms at a time."""
+        import numpy as np
+        import torch
+        dev = self.engine.device
+        log_n, pass_log = int(log_n), int(pass_log)
+        if log_n < 1 or log_n > 28:
+            raise ValueError("log_n must be 1 .. 28")
+        if pass_log < 0 or pass_log > 10:
+            raise ValueError("pass_log must be 0 .. 10")
+        n_rows = 1 << log_n
+        n = int(columns.shape[0]) if isinstance(columns, torch.Tensor) and columns.dim() else len(columns)
+        if n < 1:
+            raise ValueError("columns: at least one")
+        if input_rows is None:
+            rows = [n_rows] * n
+        else:
+            rows = [int(r) for r in input_rows]
+            if len(rows) != n or any(r < 0 or r > n_rows for r in rows):
+                raise ValueError("input_rows: %d values between 0 and 2^log_n" % n)
+
+        def pointers(name, t, need):
+            if isinstance(t, torch.Tensor):
+                if t.dtype != torch.uint64 or t.device != dev:
+                    raise ValueError("%s must be a uint64 tensor on %s" % (name, dev))
+                if t.dim() != 3 or t.shape[0] != n or t.shape[1] < need or t.shape[2] != 4 or not t.is_contiguous():
+                    raise ValueError("%s must be contiguous, of shape (%d, rows >= %d, 4)" % (name, n, need))
+                return [t.data_ptr() + a * t.shape[1] * 32 for a in range(n)]
+            ptrs = [int(p) for p in t]
+            if len(ptrs) != n or any(p == 0 or p % 16 for p in ptrs):
+                raise ValueError("%s: %d device addresses, 16-byte aligned" % (name, n))
+            return ptrs
+
+        ins = pointers("columns", columns, max(rows))
+        if out is None:
+            out = torch.zeros((n, n_rows, 4), dtype=torch.uint64, device=dev)
+        outs = pointers("out", out, n_rows)
+
+        def element(name, v, required):
+            if v is None:
+                if required:
+                    raise ValueError("%s: one field element" % name)
+                return None
+            if isinstance(v, torch.Tensor):
+                v = v.cpu().numpy()
+            if isinstance(v, np.ndarray):
+                buf = np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4) if v.size == 4 else np.zeros((0, 4), dtype=np.uint64)
+            else:
+                v = [v] if isinstance(v, int) else list(v)
+                buf = np.array([[(int(x) >> (64 * i)) & (2**64 - 1) for i in range(4)] for x in v], dtype=np.uint64).reshape(-1, 4)
+            if buf.shape != (1, 4):
+                raise ValueError("%s: one field element of 4 x uint64" % name)
+            return buf
+
+        o_buf, g_buf, c_buf = element("omega", omega, True), element("shift", shift, False), element("scale", scale, False)
+        status = np.zeros(n, dtype=np.uint32)
+        args = N.Ntt(N.HSW_NTT_SHIFT_AFTER if shift_after else 0, log_n, pass_log, 0, n, (C.c_void_p * n)(*ins), (C.c_uint64 * n)(*rows),
+                     (C.c_void_p * n)(*outs), o_buf.ctypes.data, g_buf.ctypes.data if g_buf is not None else None,
+                     c_buf.ctypes.data if c_buf is not None else None, status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        rep = N.NttReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the call runs on the engine's
+        self._ok(self.lib.hsw_gadget_ntt(self.h, C.byref(args), C.byref(rep)))
+        return out if isinstance(out, torch.Tensor) else None, status, {f[0]: getattr(rep, f[0]) for f in N.NttReport._fields_}
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

@@ -1269,6 +1269,61 @@ typedef struct hsw_permutation_report {
     float kernel_ms, tiles_ms, scan_ms, write_ms;
 } hsw_permutation_report;
 int hsw_gadget_permutation_product(hsw_gadget *g, const hsw_permutation_product *args, hsw_permutation_report *report);
+/* ---- the Fr NTT of device columns: Lagrange, coefficient and coset form ----
+ * What halo2 does next with every column above: lagrange_to_coeff, coeff_to_extended, extended_to_coeff.  For column b,
+ * with a[j] the field element stored in cell j of d_inputs[b] for j < input_rows[b] and 0 from there on, every value mod
+ * p, N = 2^log_n, natural order in and out:
+ *   flags = 0:                    out[i] = c * sum_{j<N} a[j] * g^j * w^(i j)      0 <= i < N
+ *   flags = HSW_NTT_SHIFT_AFTER:  out[i] = c * g^i * sum_{j<N} a[j] * w^(i j)
+ * w = omega, g = shift (NULL: 1) and c = scale (NULL: 1) are the caller's: HOST memory, 32 bytes each as stored in the
+ * representation of the pass, below p.  The library pins no constant of halo2's; it does check that w^(N/2) = p - 1, so
+ * that w is a primitive N-th root of unity.  The three calls of halo2:
+ *   lagrange_to_coeff   w = omega^-1,      c = n^-1, flags 0
+ *   coeff_to_extended   w = omega_ext,     g = zeta, flags 0, input_rows = n, log_n = k + e
+ *   extended_to_coeff   w = omega_ext^-1,  c = N^-1, g = zeta^-1, HSW_NTT_SHIFT_AFTER (the caller ignores the rows it truncates)
+ * Cells are 32 bytes in the representation of the pass; the transform is linear and every constant is held in Montgomery
+ * form, so canonical and Montgomery cells take the same kernel and the output is exact bit for bit in both.
+ * d_inputs, d_outputs: HOST arrays (copied, not kept) of DEVICE pointers, 16-byte aligned, in any address order;
+ * d_outputs[b] receives N cells.  Rows of an input at and beyond input_rows[b] are NOT READ.  d_outputs[b] ==
+ * d_inputs[b] (in place) is allowed, and several columns may read one input; any other overlap of an output with an
+ * input or with another output is refused.
+ * Decided on the device, per column (status[b], a host array of n_columns words, may be NULL):
+ *   HSW_NTT_CELL_NOT_BELOW_P  a stored cell that was read is not an encoding below p: the column is REFUSED, not one
+ *                             byte of its output is written.
+ * The other columns are written; the call returns HSW_OK and the report counts them (first_refused: the lowest such
+ * column, ~0 where there is none).  input_rows[b] = 0 is legal: N zero cells, nothing of the input is read.  Nothing
+ * outside rows [0, N) of the outputs of the columns not refused is ever written.
+ * Refused before any launch -- HSW_ERR_INVALID_ARG: n_columns 0, log_n 0 or above 28, pass_log above 10, unknown flags, a
+ * pointer (array or column) that is NULL or not 16-byte aligned, input_rows[b] > N, omega missing, not below p or not
+ * primitive of order N, shift or scale not below p, an overlap as above (hsw_last_error names the column);
+ * HSW_ERR_UNSUPPORTED: HSW_REPR_COMPACT64 cells, a pass whose batches differ in representation.
+ * The bits of the index go in digits, a launch per digit: one launch up to log_n = pass_log (0: 10, the points a
+ * workgroup holds), else digits of at most max(1, pass_log - 2) bits, because a launch that reads or writes at a stride
+ * keeps runs of four cells -- 2 launches up to log_n 16, 3 up to 24, 4 up to 28 by default.  Only a column's last launch
+ * writes d_outputs[b]; before it the points live in the gadget's scratch (N cells per column; columns go in groups that
+ * hold at most 1 GiB of it, a group being at least one column), grown on demand and freed by hsw_gadget_destroy.  The
+ * table of the N / 2 powers of w is built on the device from O(log N) staged powers and cached by (w as a value,
+ * log_n): four tables, the least recently used one evicted, all freed by hsw_gadget_destroy.  The host reads nothing
+ * between launches.  Synchronous.  (The call came under HSW_ABI_MINOR 1: probe for the symbol.) */
+#define HSW_NTT_SHIFT_AFTER 1u
+#define HSW_NTT_CELL_NOT_BELOW_P 4u    /* status bit, the value of HSW_PRODUCT_CELL_NOT_BELOW_P */
+typedef struct hsw_ntt {
+    uint32_t flags, log_n;                 /* flags: 0 or HSW_NTT_SHIFT_AFTER; 1 <= log_n <= 28 */
+    uint32_t pass_log, reserved_;          /* 0: the library's choice (10); else no launch transforms more than 2^pass_log points at a time, 1 .. 10 */
+    size_t n_columns;
+    const void *const *d_inputs;           /* host array, n_columns device pointers */
+    const uint64_t *input_rows;            /* host, per column, 0 .. N; NULL = N everywhere */
+    void *const *d_outputs;                /* host array, n_columns device pointers, N cells each */
+    const void *omega, *shift, *scale;     /* host, 32 bytes each as stored, below p; shift, scale may be NULL */
+    uint32_t *status;                      /* host, n_columns words, output; may be NULL */
+} hsw_ntt;
+typedef struct hsw_ntt_report {
+    uint64_t columns, written, refused_columns, first_refused;   /* written = N x columns not refused; first_refused: ~0 where there is none */
+    uint64_t twiddle_bytes, scratch_bytes; /* the table of this call's root; the points' scratch of a group */
+    uint32_t launches, pass_log;           /* launches per column group; the pass_log used */
+    float kernel_ms, twiddle_ms;           /* twiddle_ms: 0 when the table was cached */
+} hsw_ntt_report;
+int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */

@@ -445,6 +445,45 @@ pub struct hsw_permutation_report {
     pub write_ms: f32,
 }
 
+pub const HSW_NTT_SHIFT_AFTER: u32 = 1;
+pub const HSW_NTT_CELL_NOT_BELOW_P: u32 = 4;
+
+/// Arguments of `hsw_gadget_ntt`: `n_columns` columns of `2^log_n` cells (host arrays of device pointers; an output may
+/// be its own input), `input_rows` per column (NULL: all), and `omega`, `shift`, `scale` in host memory, 32 bytes each
+/// as stored (`shift`, `scale` may be NULL: 1).
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_ntt {
+    pub flags: u32,
+    pub log_n: u32,
+    pub pass_log: u32,
+    pub reserved_: u32,
+    pub n_columns: usize,
+    pub d_inputs: *const *const c_void,
+    pub input_rows: *const u64,
+    pub d_outputs: *const *mut c_void,
+    pub omega: *const c_void,
+    pub shift: *const c_void,
+    pub scale: *const c_void,
+    pub status: *mut u32,
+}
+
+/// Result of `hsw_gadget_ntt`; `first_refused` is `u64::MAX` where there is none.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_ntt_report {
+    pub columns: u64,
+    pub written: u64,
+    pub refused_columns: u64,
+    pub first_refused: u64,
+    pub twiddle_bytes: u64,
+    pub scratch_bytes: u64,
+    pub launches: u32,
+    pub pass_log: u32,
+    pub kernel_ms: f32,
+    pub twiddle_ms: f32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -727,6 +766,9 @@ extern "C" {
     /// per proof: `HSW_PRODUCT_*`.
     pub fn hsw_gadget_permutation_product(g: *mut hsw_gadget, args: *const hsw_permutation_product,
                                           report: *mut hsw_permutation_report) -> c_int;
+    /// The Fr NTT of device columns, natural order in and out; synchronous.  Status bit per column:
+    /// `HSW_NTT_CELL_NOT_BELOW_P` (the column is not written).
+    pub fn hsw_gadget_ntt(g: *mut hsw_gadget, args: *const hsw_ntt, report: *mut hsw_ntt_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

@@ -299,6 +299,23 @@ class NttReport(C.Structure):
                 ("kernel_ms", C.c_float), ("twiddle_ms", C.c_float)]
 
 
+HSW_MSM_CELL_NOT_BELOW_P, HSW_MSM_BASE_NOT_BELOW_Q, HSW_MSM_MAX_WINDOW_BITS = 4, 8, 8
+
+
+class Msm(C.Structure):
+    """hsw_msm: the commitments of device columns, the BN254 G1 MSM (hsw_gadget_msm)."""
+    _fields_ = [("flags", C.c_uint32), ("window_bits", C.c_uint32), ("slice_rows", C.c_uint32), ("reserved_", C.c_uint32), ("n_columns", C.c_size_t),
+                ("n_bases", C.c_uint64), ("d_bases", C.c_void_p), ("d_scalars", C.POINTER(C.c_void_p)), ("input_rows", C.POINTER(C.c_uint64)),
+                ("out_points", C.c_void_p), ("status", C.POINTER(C.c_uint32))]
+
+
+class MsmReport(C.Structure):
+    _fields_ = [("columns", C.c_uint64), ("refused_columns", C.c_uint64), ("first_refused", C.c_uint64), ("bad_bases", C.c_uint64),
+                ("first_bad_base", C.c_uint64), ("scratch_bytes", C.c_uint64), ("window_bits", C.c_uint32), ("windows", C.c_uint32),
+                ("slice_rows", C.c_uint32), ("slices", C.c_uint32), ("launches", C.c_uint32), ("reserved_", C.c_uint32),
+                ("kernel_ms", C.c_float), ("finish_ms", C.c_float)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -322,6 +339,7 @@ SYMBOLS = (
     "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
     "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities", "hsw_gadget_lookup_permuted",
     "hsw_gadget_lookup_product", "hsw_gadget_permutation_product", "hsw_gadget_ntt",
+    "hsw_gadget_msm",
 )
 
 
@@ -429,6 +447,9 @@ def lib():
         if hasattr(L, "hsw_gadget_ntt"):   # likewise
             L.hsw_gadget_ntt.restype = C.c_int
             L.hsw_gadget_ntt.argtypes = [vp, C.POINTER(Ntt), C.POINTER(NttReport)]
+        if hasattr(L, "hsw_gadget_msm"):   # likewise
+            L.hsw_gadget_msm.restype = C.c_int
+            L.hsw_gadget_msm.argtypes = [vp, C.POINTER(Msm), C.POINTER(MsmReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

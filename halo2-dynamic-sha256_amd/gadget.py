@@ -848,6 +848,69 @@ class Sha256DynamicConfig:
         self._ok(self.lib.hsw_gadget_ntt(self.h, C.byref(args), C.byref(rep)))
         return out if isinstance(out, torch.Tensor) else None, status, {f[0]: getattr(rep, f[0]) for f in N.NttReport._fields_}
 
+    def msm(self, bases, columns, input_rows=None, window_bits=0, slice_rows=0, n_bases=None):
+        """hsw_gadget_msm: the commitments of device columns, points[b] = sum_{j < input_rows[b]} a[j] * G[j] in BN254 G1.
+        Returns (points, status, report): a (columns, 8) uint64 numpy array -- x then y, four words each, Montgomery form
+        mod q, all zero for the identity, as a base is stored -- the uint32 numpy status array (HSW_MSM_CELL_NOT_BELOW_P:
+        that column's row of `points` is left zero; HSW_MSM_BASE_NOT_BELOW_Q: every row is) and the report as a dict.
+        bases: a contiguous uint64 tensor (n_bases, 8) on the engine's device, or a device address (int, 16-byte
+        aligned) with n_bases.  columns: a contiguous uint64 tensor (columns, rows, 4) on the engine's device or a
+        sequence of device addresses, as ntt takes them.  input_rows: per column, the rows that are read (0 .. n_bases);
+        None: all n_bases.  window_bits: 0 or 1 .. 8; slice_rows: 0 or a power of two, 64 .. 2^28."""
+        import numpy as np
+        import torch
+        dev = self.engine.device
+        window_bits, slice_rows = int(window_bits), int(slice_rows)
+        if window_bits < 0 or window_bits > N.HSW_MSM_MAX_WINDOW_BITS:
+            raise ValueError("window_bits must be 0 .. %d" % N.HSW_MSM_MAX_WINDOW_BITS)
+        if slice_rows and (slice_rows < 64 or slice_rows > 1 << 28 or slice_rows & (slice_rows - 1)):
+            raise ValueError("slice_rows must be 0 or a power of two, 64 .. 2^28")
+        if isinstance(bases, (tuple, list)) and len(bases) == 2:          # (address, n_bases)
+            bases, n_bases = bases
+        if isinstance(bases, torch.Tensor):
+            if bases.dtype != torch.uint64 or bases.device != dev:
+                raise ValueError("bases must be a uint64 tensor on %s" % (dev,))
+            if bases.dim() != 2 or bases.shape[1] != 8 or not bases.is_contiguous():
+                raise ValueError("bases must be contiguous, of shape (n_bases, 8)")
+            if n_bases is not None and int(n_bases) != bases.shape[0]:
+                raise ValueError("n_bases is the tensor's")
+            nb, base_ptr = int(bases.shape[0]), bases.data_ptr() if bases.shape[0] else 0
+        else:
+            if n_bases is None:
+                raise ValueError("bases given as an address need n_bases")
+            nb, base_ptr = int(n_bases), int(bases)
+            if base_ptr == 0 or base_ptr % 16:
+                raise ValueError("bases: a device address, 16-byte aligned")
+        if nb < 1 or nb > 1 << 28:
+            raise ValueError("n_bases must be 1 .. 2^28")
+        n = int(columns.shape[0]) if isinstance(columns, torch.Tensor) and columns.dim() else len(columns)
+        if n < 1:
+            raise ValueError("columns: at least one")
+        if input_rows is None:
+            rows = [nb] * n
+        else:
+            rows = [int(r) for r in input_rows]
+            if len(rows) != n or any(r < 0 or r > nb for r in rows):
+                raise ValueError("input_rows: %d values between 0 and n_bases" % n)
+        if isinstance(columns, torch.Tensor):
+            if columns.dtype != torch.uint64 or columns.device != dev:
+                raise ValueError("columns must be a uint64 tensor on %s" % (dev,))
+            if columns.dim() != 3 or columns.shape[1] < max(rows) or columns.shape[2] != 4 or not columns.is_contiguous():
+                raise ValueError("columns must be contiguous, of shape (%d, rows >= %d, 4)" % (n, max(rows)))
+            ptrs = [columns.data_ptr() + a * columns.shape[1] * 32 for a in range(n)]
+        else:
+            ptrs = [int(p) for p in columns]
+            if any(p == 0 or p % 16 for p in ptrs):
+                raise ValueError("columns: %d device addresses, 16-byte aligned" % n)
+        points = np.zeros((n, 8), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint32)
+        args = N.Msm(0, window_bits, slice_rows, 0, n, nb, base_ptr, (C.c_void_p * n)(*ptrs), (C.c_uint64 * n)(*rows),
+                     points.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        rep = N.MsmReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the call runs on the engine's
+        self._ok(self.lib.hsw_gadget_msm(self.h, C.byref(args), C.byref(rep)))
+        return points, status, {f[0]: getattr(rep, f[0]) for f in N.MsmReport._fields_ if f[0] != "reserved_"}
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

@@ -1178,7 +1178,7 @@ int hsw_gadget_lookup_permuted(hsw_gadget *g, const hsw_lookup_permuted *args, h
  * The other arguments are written; the call returns HSW_OK in all these cases and the report counts them (first_open /
  * first_refused: the lowest such argument, ~0 where there is none; written: (u + 1) x the arguments not refused).  Every
  * row of every column is either fully written or untouched; nothing at or beyond row u + 1, no input cell and no other
- * byte of the caller's is ever written.  Blinding rows and the commitment are the prover's.
+ * byte of the caller's is ever written.  Blinding rows are the prover's; the commitment is hsw_gadget_msm.
  * Refused before any launch -- HSW_ERR_INVALID_ARG: usable_rows < T, a wrong n_arguments, unknown flags or table, a
  * pointer (array or column) that is NULL or not 16-byte aligned, input_rows[a] > usable_rows, a challenge that is missing
  * or not below p, a Z column that overlaps a column read or another Z column (byte intervals; hsw_last_error names the
@@ -1240,7 +1240,7 @@ int hsw_gadget_lookup_product(hsw_gadget *g, const hsw_lookup_product *args, hsw
  * The other proofs are written; the call returns HSW_OK in all these cases and the report counts them (first_open /
  * first_refused: the lowest such proof, ~0 where there is none).  Every row of every Z column is either fully written or
  * untouched; nothing at or beyond row u + 1, no input cell and no other byte of the caller's is ever written.  Blinding
- * rows and the commitment are the prover's.
+ * rows are the prover's; the commitment is hsw_gadget_msm.
  * Refused before any launch -- HSW_ERR_INVALID_ARG: usable_rows, n_columns or chunk_columns 0, unknown flags, a pointer
  * (array or column) that is NULL or not 16-byte aligned, column_rows[k] > usable_rows, a challenge, omega or delta that is
  * missing or not below p, a Z column that overlaps a column read or another Z column (byte intervals; hsw_last_error
@@ -1324,6 +1324,69 @@ typedef struct hsw_ntt_report {
     float kernel_ms, twiddle_ms;           /* twiddle_ms: 0 when the table was cached */
 } hsw_ntt_report;
 int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report *report);
+/* ---- commit device columns: the BN254 G1 multi-scalar multiplication on the device ----
+ * What halo2 does between any two of the calls above: commit_lagrange (advice, A', S', Z) and commit (the pieces of h).
+ * For column b, with a[j] the field element stored in cell j of d_scalars[b] for j < input_rows[b] and 0 from there on
+ * -- the cell in the representation of the pass, canonical or Montgomery; the kernel reduces both to the canonical
+ * integer below r -- and G[j] the point stored at d_bases + 64 j:
+ *   out_points[b] = sum_{j < input_rows[b]} a[j] * G[j]      in BN254 G1 (y^2 = x^3 + 3 over Fq, prime order r = the Fr modulus)
+ * Bases: ONE device array of n_bases affine points, 16-byte aligned, 64 bytes each: x then y, eight 32-bit limbs each,
+ * little-endian, in MONTGOMERY form mod q whatever the representation of the pass, (0, 0) for the identity -- assumed to
+ * be the in-memory form of halo2curves' G1Affine (assumption A7).  The caller uploads params.g_lagrange /
+ * params.g once and reuses them across calls.  A (0, 0) base contributes nothing.  The library does not check that a
+ * base is on the curve (the setup is the caller's); it does check that both coordinates of every base in rows
+ * [0, max_b input_rows[b]) are below q.
+ * Scalars: d_scalars is a HOST array (copied, not kept) of DEVICE pointers, 16-byte aligned, 32-byte cells; input_rows a
+ * host array, NULL = n_bases everywhere.  Rows of a column at and beyond input_rows[b] are NOT READ.  input_rows[b] = 0
+ * is legal and gives the identity.  Several columns may share one input.
+ * Output: out_points is a HOST array of n_columns x 64 bytes in the stored form of a base; the identity is 64 zero
+ * bytes.  The bytes are a function of the group element alone, hence the same whatever the schedule.  Nothing in
+ * device memory other than the gadget's own scratch is written.
+ * Decided on the device, per column (status[b], a host array of n_columns words, may be NULL); the call returns HSW_OK
+ * in all of these cases:
+ *   HSW_MSM_CELL_NOT_BELOW_P  a stored cell that was read is not an encoding below r: the column is REFUSED, not one
+ *                             byte of out_points[b] is written; the other columns are.
+ *   HSW_MSM_BASE_NOT_BELOW_Q  some base in the checked rows has a coordinate not below q: every column carries the bit
+ *                             and nothing is written.  The report carries bad_bases and first_bad_base (~0 where
+ *                             none).  Bases beyond the checked rows are not read.
+ * Refused before any launch -- HSW_ERR_INVALID_ARG (hsw_last_error names the column): n_columns 0, n_bases 0 or above
+ * 2^28, a pointer (array, column, bases, out_points) that is NULL or not 16-byte aligned (out_points: NULL), input_rows[b]
+ * > n_bases, unknown flags, a window_bits or slice_rows outside its range; HSW_ERR_UNSUPPORTED: HSW_REPR_COMPACT64
+ * cells, a pass whose batches differ in representation.
+ * The method is Pippenger's with unsigned digits of window_bits bits: W = ceil(254 / window_bits) windows, the rows in
+ * slices of slice_rows rows; one launch checks the bases, then per group of columns one launch fills the 2^window_bits - 1
+ * buckets of every (slice, window, column) and one sums the slices and forms a point per (window, column).  The host
+ * copies W x 96 bytes per column, runs the Horner over the windows and the one inversion, and writes out_points.  Two
+ * knobs exist so that small inputs reach every path: window_bits (0: the library's choice, 8; else 1 ..
+ * HSW_MSM_MAX_WINDOW_BITS) and slice_rows (0: the library's choice, 4096, doubled until a column has at most 1024
+ * slices; else a power of two from 64 to 2^28), the rows one workgroup accumulates; the report says what was used.
+ * The partial buckets live in the gadget's scratch (columns go in groups that hold at most 1 GiB of them, a group being
+ * at least one column), grown on demand and freed by hsw_gadget_destroy; nothing is allocated between the launches of a
+ * group.  The blinding term blind * W is a one-point addition and stays the prover's, as does the transcript.
+ * Synchronous, on the engine's stream.  (The call came under HSW_ABI_MINOR 1: probe for the symbol.) */
+#define HSW_MSM_CELL_NOT_BELOW_P 4u    /* status bit, the value of HSW_NTT_CELL_NOT_BELOW_P */
+#define HSW_MSM_BASE_NOT_BELOW_Q 8u    /* status bit */
+#define HSW_MSM_MAX_WINDOW_BITS 8u
+typedef struct hsw_msm {
+    uint32_t flags, window_bits;           /* flags: 0; window_bits: 0 or 1 .. HSW_MSM_MAX_WINDOW_BITS */
+    uint32_t slice_rows, reserved_;        /* 0 or a power of two, 64 .. 2^28 */
+    size_t n_columns;
+    uint64_t n_bases;                      /* 1 .. 2^28 */
+    const void *d_bases;                   /* device, n_bases x 64 bytes */
+    const void *const *d_scalars;          /* host array, n_columns device pointers */
+    const uint64_t *input_rows;            /* host, per column, 0 .. n_bases; NULL = n_bases everywhere */
+    void *out_points;                      /* host, n_columns x 64 bytes, output */
+    uint32_t *status;                      /* host, n_columns words, output; may be NULL */
+} hsw_msm;
+typedef struct hsw_msm_report {
+    uint64_t columns, refused_columns, first_refused;   /* refused: either bit; first_refused: ~0 where there is none */
+    uint64_t bad_bases, first_bad_base;    /* bases of the checked rows not below q; first_bad_base: ~0 where there is none */
+    uint64_t scratch_bytes;                /* the partial buckets of a group */
+    uint32_t window_bits, windows, slice_rows, slices;   /* what was used; slices: of the tallest column */
+    uint32_t launches, reserved_;          /* the check (none when no row is read), and two per group of columns */
+    float kernel_ms, finish_ms;            /* device: the launches; host: the Horner and the inversion of every column */
+} hsw_msm_report;
+int hsw_gadget_msm(hsw_gadget *g, const hsw_msm *args, hsw_msm_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */

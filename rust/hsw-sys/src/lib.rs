@@ -484,6 +484,49 @@ pub struct hsw_ntt_report {
     pub twiddle_ms: f32,
 }
 
+pub const HSW_MSM_CELL_NOT_BELOW_P: u32 = 4;
+pub const HSW_MSM_BASE_NOT_BELOW_Q: u32 = 8;
+pub const HSW_MSM_MAX_WINDOW_BITS: u32 = 8;
+
+/// Arguments of `hsw_gadget_msm`: `n_columns` columns of 32-byte cells (a host array of device pointers), `input_rows`
+/// per column (NULL: `n_bases`), against `n_bases` affine G1 points in device memory (64 bytes each, Montgomery form
+/// mod q, `(0, 0)` the identity); `out_points` is host memory, 64 bytes per column.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_msm {
+    pub flags: u32,
+    pub window_bits: u32,
+    pub slice_rows: u32,
+    pub reserved_: u32,
+    pub n_columns: usize,
+    pub n_bases: u64,
+    pub d_bases: *const c_void,
+    pub d_scalars: *const *const c_void,
+    pub input_rows: *const u64,
+    pub out_points: *mut c_void,
+    pub status: *mut u32,
+}
+
+/// Result of `hsw_gadget_msm`; `first_refused` and `first_bad_base` are `u64::MAX` where there is none.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_msm_report {
+    pub columns: u64,
+    pub refused_columns: u64,
+    pub first_refused: u64,
+    pub bad_bases: u64,
+    pub first_bad_base: u64,
+    pub scratch_bytes: u64,
+    pub window_bits: u32,
+    pub windows: u32,
+    pub slice_rows: u32,
+    pub slices: u32,
+    pub launches: u32,
+    pub reserved_: u32,
+    pub kernel_ms: f32,
+    pub finish_ms: f32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -769,6 +812,10 @@ extern "C" {
     /// The Fr NTT of device columns, natural order in and out; synchronous.  Status bit per column:
     /// `HSW_NTT_CELL_NOT_BELOW_P` (the column is not written).
     pub fn hsw_gadget_ntt(g: *mut hsw_gadget, args: *const hsw_ntt, report: *mut hsw_ntt_report) -> c_int;
+    /// The commitments of device columns: `out_points[b] = sum_j a[j] * G[j]` in BN254 G1, one affine point per column in
+    /// host memory.  Per column `status[b]` carries `HSW_MSM_CELL_NOT_BELOW_P` (that column is not written) or
+    /// `HSW_MSM_BASE_NOT_BELOW_Q` (nothing is written).
+    pub fn hsw_gadget_msm(g: *mut hsw_gadget, args: *const hsw_msm, report: *mut hsw_msm_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

@@ -316,6 +316,37 @@ class MsmReport(C.Structure):
                 ("kernel_ms", C.c_float), ("finish_ms", C.c_float)]
 
 
+HSW_OPEN_CELL_NOT_BELOW_P, HSW_OPEN_MIN_TILE_ROWS, HSW_OPEN_THREAD_ROWS = 4, 256, 8
+
+
+class Evaluate(C.Structure):
+    """hsw_evaluate: device columns evaluated at points (hsw_gadget_evaluate)."""
+    _fields_ = [("flags", C.c_uint32), ("tile_rows", C.c_uint32), ("rows", C.c_uint64), ("n_columns", C.c_size_t),
+                ("d_columns", C.POINTER(C.c_void_p)), ("input_rows", C.POINTER(C.c_uint64)), ("n_points", C.c_size_t), ("points", C.c_void_p),
+                ("n_queries", C.c_size_t), ("query_column", C.POINTER(C.c_uint32)), ("query_point", C.POINTER(C.c_uint32)),
+                ("out_evals", C.c_void_p), ("status", C.POINTER(C.c_uint32))]
+
+
+class EvaluateReport(C.Structure):
+    _fields_ = [("columns", C.c_uint64), ("queries", C.c_uint64), ("refused_columns", C.c_uint64), ("refused_queries", C.c_uint64),
+                ("first_refused", C.c_uint64), ("scratch_bytes", C.c_uint64), ("tile_rows", C.c_uint32), ("tiles", C.c_uint32),
+                ("thread_rows", C.c_uint32), ("launches", C.c_uint32), ("kernel_ms", C.c_float), ("reserved_", C.c_uint32)]
+
+
+class Open(C.Structure):
+    """hsw_open: groups of device columns opened at a point each, the quotients of GWC (hsw_gadget_open)."""
+    _fields_ = [("flags", C.c_uint32), ("tile_rows", C.c_uint32), ("rows", C.c_uint64), ("n_columns", C.c_size_t),
+                ("d_columns", C.POINTER(C.c_void_p)), ("input_rows", C.POINTER(C.c_uint64)), ("n_groups", C.c_size_t),
+                ("group_first", C.POINTER(C.c_uint64)), ("group_columns", C.POINTER(C.c_uint32)), ("points", C.c_void_p),
+                ("challenges", C.c_void_p), ("d_quotients", C.POINTER(C.c_void_p)), ("out_evals", C.c_void_p), ("status", C.POINTER(C.c_uint32))]
+
+
+class OpenReport(C.Structure):
+    _fields_ = [("groups", C.c_uint64), ("written", C.c_uint64), ("refused_groups", C.c_uint64), ("first_refused", C.c_uint64),
+                ("scratch_bytes", C.c_uint64), ("tile_rows", C.c_uint32), ("tiles", C.c_uint32), ("thread_rows", C.c_uint32),
+                ("launches", C.c_uint32), ("batches", C.c_uint32), ("reserved_", C.c_uint32), ("kernel_ms", C.c_float), ("reserved2_", C.c_float)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -339,7 +370,7 @@ SYMBOLS = (
     "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
     "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities", "hsw_gadget_lookup_permuted",
     "hsw_gadget_lookup_product", "hsw_gadget_permutation_product", "hsw_gadget_ntt",
-    "hsw_gadget_msm",
+    "hsw_gadget_msm", "hsw_gadget_evaluate", "hsw_gadget_open",
 )
 
 
@@ -450,6 +481,12 @@ def lib():
         if hasattr(L, "hsw_gadget_msm"):   # likewise
             L.hsw_gadget_msm.restype = C.c_int
             L.hsw_gadget_msm.argtypes = [vp, C.POINTER(Msm), C.POINTER(MsmReport)]
+        if hasattr(L, "hsw_gadget_evaluate"):   # likewise
+            L.hsw_gadget_evaluate.restype = C.c_int
+            L.hsw_gadget_evaluate.argtypes = [vp, C.POINTER(Evaluate), C.POINTER(EvaluateReport)]
+        if hasattr(L, "hsw_gadget_open"):   # likewise
+            L.hsw_gadget_open.restype = C.c_int
+            L.hsw_gadget_open.argtypes = [vp, C.POINTER(Open), C.POINTER(OpenReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

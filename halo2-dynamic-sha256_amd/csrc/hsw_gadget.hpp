@@ -17,10 +17,10 @@
 // HSW_GADGET_WHOLE_DIGEST (hsw_frame.hpp / hsw_frame_kernel, assumption A4);
 // without it only their *values* are produced (AssignedHashResult).
 //
-// Implemented in ten translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
+// Implemented in several translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
 // call), hsw_gadget_context.cpp (Context: buffers, layouts, bind / unbind, the jump table), hsw_gadget_digest.cpp (the
 // digest paths and the ties), hsw_gadget_lookup.cpp (the lookup entries of a pass, listed and counted),
-// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z), hsw_gadget_permutation.cpp (the permutation argument's grand products), hsw_gadget_ntt.cpp (the Fr NTT of device columns), hsw_gadget_msm.cpp (their commitments: the G1 MSM) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
+// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z), hsw_gadget_permutation.cpp (the permutation argument's grand products), hsw_gadget_ntt.cpp (the Fr NTT of device columns), hsw_gadget_msm.cpp (their commitments: the G1 MSM), hsw_gadget_open.cpp (their evaluations and opening quotients) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
 #ifndef HSW_GADGET_HPP
 #define HSW_GADGET_HPP
 
@@ -394,6 +394,8 @@ struct hsw_gadget {
     uint64_t ntt_stamp = 0;
     void *d_msm = nullptr;                          // hsw_gadget_msm (hsw_gadget_msm.cpp): status words, the bases' check, columns, window points and
     size_t msm_cap = 0;                             // the partial buckets of a group of columns, in bytes; grown and freed like d_pairs
+    void *d_open = nullptr;                         // hsw_gadget_evaluate / _open (hsw_gadget_open.cpp): status words, evaluations, columns, groups,
+    size_t open_cap = 0;                            // staged powers and the scratch of a batch, in bytes; grown and freed like d_pairs
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

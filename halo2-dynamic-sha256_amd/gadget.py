@@ -911,6 +911,136 @@ class Sha256DynamicConfig:
         self._ok(self.lib.hsw_gadget_msm(self.h, C.byref(args), C.byref(rep)))
         return points, status, {f[0]: getattr(rep, f[0]) for f in N.MsmReport._fields_ if f[0] != "reserved_"}
 
+    def _open_columns(self, rows, columns, input_rows, tile_rows):
+        """What evaluate and open share: (rows, tile_rows, n, per-column heights, per-column addresses)."""
+        import torch
+        dev = self.engine.device
+        rows, tile_rows = int(rows), int(tile_rows)
+        if rows < 1 or rows > 1 << 28:
+            raise ValueError("rows must be 1 .. 2^28")
+        if tile_rows and (tile_rows < N.HSW_OPEN_MIN_TILE_ROWS or tile_rows > 1 << 20 or tile_rows & (tile_rows - 1)):
+            raise ValueError("tile_rows must be 0 or a power of two, %d .. 2^20" % N.HSW_OPEN_MIN_TILE_ROWS)
+        n = int(columns.shape[0]) if isinstance(columns, torch.Tensor) and columns.dim() else len(columns)
+        if n < 1:
+            raise ValueError("columns: at least one")
+        if input_rows is None:
+            heights = [rows] * n
+        else:
+            heights = [int(r) for r in input_rows]
+            if len(heights) != n or any(r < 0 or r > rows for r in heights):
+                raise ValueError("input_rows: %d values between 0 and rows" % n)
+        if isinstance(columns, torch.Tensor):
+            if columns.dtype != torch.uint64 or columns.device != dev:
+                raise ValueError("columns must be a uint64 tensor on %s" % (dev,))
+            if columns.dim() != 3 or columns.shape[1] < max(heights) or columns.shape[2] != 4 or not columns.is_contiguous():
+                raise ValueError("columns must be contiguous, of shape (%d, rows >= %d, 4)" % (n, max(heights)))
+            ptrs = [columns.data_ptr() + a * columns.shape[1] * 32 for a in range(n)]
+        else:
+            ptrs = [int(p) for p in columns]
+            if any(p == 0 or p % 16 for p in ptrs):
+                raise ValueError("columns: %d device addresses, 16-byte aligned" % n)
+        return rows, tile_rows, n, heights, ptrs
+
+    @staticmethod
+    def _field_elements(name, v, n):
+        """n field elements AS STORED as an (n, 4) uint64 numpy array: ints, or a tensor / array of 4 n words."""
+        import numpy as np
+        import torch
+        if v is None:
+            raise ValueError("%s: %d field element(s)" % (name, n))
+        if isinstance(v, torch.Tensor):
+            v = v.cpu().numpy()
+        if isinstance(v, np.ndarray):
+            buf = np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 4) if v.size == 4 * n else np.zeros((0, 4), dtype=np.uint64)
+        else:
+            v = [v] if isinstance(v, int) else list(v)
+            if any(int(x) < 0 or int(x) >> 256 for x in v):
+                raise ValueError("%s: field elements of 256 bits" % name)
+            buf = np.array([[(int(x) >> (64 * i)) & (2**64 - 1) for i in range(4)] for x in v], dtype=np.uint64).reshape(-1, 4)
+        if buf.shape != (n, 4):
+            raise ValueError("%s: %d field element(s) of 4 x uint64" % (name, n))
+        return buf
+
+    def evaluate(self, rows, columns, points, queries, input_rows=None, tile_rows=0):
+        """hsw_gadget_evaluate: evals[i] = sum_{j < rows} a_b[j] z_t^j for every query i = (b, t), a column index and a
+        point index.  Returns (evals, status, report): a (queries, 4) uint64 numpy array AS STORED in the representation
+        of the pass, the uint32 numpy status array per COLUMN (HSW_OPEN_CELL_NOT_BELOW_P: the rows of `evals` of every
+        query of that column are left zero) and the report as a dict.  columns: a contiguous uint64 tensor (columns,
+        rows, 4) on the engine's device or a sequence of device addresses, as ntt takes them.  points: field elements as
+        stored (ints, or an array of 4 words each).  queries: a sequence of (column, point) pairs; duplicates are
+        allowed, and a column is read once for all its points.  input_rows: per column, the rows that are read (the rest
+        count as 0); None: all.  tile_rows: 0, or the rows of a workgroup's tile (a power of two, 256 .. 2^20)."""
+        import numpy as np
+        import torch
+        rows, tile_rows, n, heights, ptrs = self._open_columns(rows, columns, input_rows, tile_rows)
+        if isinstance(points, (np.ndarray, torch.Tensor)):
+            size = int(np.prod(points.shape))
+            n_points = size // 4 if size % 4 == 0 else 0
+        else:
+            n_points = 1 if isinstance(points, int) else len(points)
+        if n_points < 1:
+            raise ValueError("points: at least one field element of 4 x uint64")
+        z_buf = self._field_elements("points", points, n_points)
+        qs = [(int(b), int(t)) for b, t in queries]
+        if not qs or any(b < 0 or b >= n or t < 0 or t >= n_points for b, t in qs):
+            raise ValueError("queries: at least one (column, point) pair of indices in range")
+        nq = len(qs)
+        evals = np.zeros((nq, 4), dtype=np.uint64)
+        status = np.zeros(n, dtype=np.uint32)
+        args = N.Evaluate(0, tile_rows, rows, n, (C.c_void_p * n)(*ptrs), (C.c_uint64 * n)(*heights), n_points, z_buf.ctypes.data, nq,
+                          (C.c_uint32 * nq)(*[b for b, _ in qs]), (C.c_uint32 * nq)(*[t for _, t in qs]), evals.ctypes.data,
+                          status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        rep = N.EvaluateReport()
+        torch.cuda.synchronize(self.engine.device)         # the tensors were made on torch's stream, the call runs on the engine's
+        self._ok(self.lib.hsw_gadget_evaluate(self.h, C.byref(args), C.byref(rep)))
+        return evals, status, {f[0]: getattr(rep, f[0]) for f in N.EvaluateReport._fields_ if f[0] != "reserved_"}
+
+    def open(self, rows, columns, groups, points, challenges, out=None, input_rows=None, tile_rows=0):
+        """hsw_gadget_open: the opening quotients of GWC.  Group g = a sequence of column indices b_0 .. b_{m-1}, folded
+        as halo2 folds (acc * v + a: c = sum_i v^(m-1-i) a_{b_i}, the first column the highest power of v =
+        challenges[g]) and divided by (X - z), z = points[g]: q[j] = sum_{i>j} c[i] z^(i-j-1).  Returns (quotients, evals,
+        status, report): a uint64 device tensor (groups, rows, 4) whose last row is zero -- msm commits it as it lies --
+        the (groups, 4) uint64 numpy array of c(z) AS STORED, the uint32 numpy status array per GROUP
+        (HSW_OPEN_CELL_NOT_BELOW_P: that group's quotient and its row of `evals` were not written) and the report as a
+        dict.  columns, input_rows, tile_rows: as evaluate takes them.  points, challenges: one field element per group
+        as stored.  out: the caller's own contiguous uint64 tensor (groups, rows' >= rows, 4), rows beyond `rows` are
+        never written, or a sequence of device addresses (then None is returned in its place)."""
+        import numpy as np
+        import torch
+        dev = self.engine.device
+        rows, tile_rows, n, heights, ptrs = self._open_columns(rows, columns, input_rows, tile_rows)
+        gs = [[int(b) for b in grp] for grp in groups]
+        if not gs or any(not grp or any(b < 0 or b >= n for b in grp) for grp in gs):
+            raise ValueError("groups: at least one, each of at least one column index below %d" % n)
+        ng = len(gs)
+        z_buf, v_buf = self._field_elements("points", points, ng), self._field_elements("challenges", challenges, ng)
+        if out is None:
+            out = torch.zeros((ng, rows, 4), dtype=torch.uint64, device=dev)
+        if isinstance(out, torch.Tensor):
+            if out.dtype != torch.uint64 or out.device != dev:
+                raise ValueError("out must be a uint64 tensor on %s" % (dev,))
+            if out.dim() != 3 or out.shape[0] != ng or out.shape[1] < rows or out.shape[2] != 4 or not out.is_contiguous():
+                raise ValueError("out must be contiguous, of shape (%d, rows >= %d, 4)" % (ng, rows))
+            qs = [out.data_ptr() + a * out.shape[1] * 32 for a in range(ng)]
+        else:
+            qs = [int(p) for p in out]
+            if len(qs) != ng or any(p == 0 or p % 16 for p in qs):
+                raise ValueError("out: %d device addresses, 16-byte aligned" % ng)
+        first = [0]
+        for grp in gs:
+            first.append(first[-1] + len(grp))
+        flat = [b for grp in gs for b in grp]
+        evals = np.zeros((ng, 4), dtype=np.uint64)
+        status = np.zeros(ng, dtype=np.uint32)
+        args = N.Open(0, tile_rows, rows, n, (C.c_void_p * n)(*ptrs), (C.c_uint64 * n)(*heights), ng, (C.c_uint64 * (ng + 1))(*first),
+                      (C.c_uint32 * len(flat))(*flat), z_buf.ctypes.data, v_buf.ctypes.data, (C.c_void_p * ng)(*qs), evals.ctypes.data,
+                      status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        rep = N.OpenReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the call runs on the engine's
+        self._ok(self.lib.hsw_gadget_open(self.h, C.byref(args), C.byref(rep)))
+        return (out if isinstance(out, torch.Tensor) else None, evals, status,
+                {f[0]: getattr(rep, f[0]) for f in N.OpenReport._fields_ if not f[0].startswith("reserved")})
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

@@ -1387,6 +1387,100 @@ typedef struct hsw_msm_report {
     float kernel_ms, finish_ms;            /* device: the launches; host: the Horner and the inversion of every column */
 } hsw_msm_report;
 int hsw_gadget_msm(hsw_gadget *g, const hsw_msm *args, hsw_msm_report *report);
+/* ---- evaluate device columns at points, and open them: the quotients of the GWC multi-opening ----
+ * What halo2 does after the last commitment with every polynomial in coefficient form (hsw_gadget_ntt's
+ * lagrange_to_coeff leaves it on the device): eval_polynomial(p, x * omega^rot) for every query, and per distinct
+ * opening point z of ProverGWC the fold of that point's polynomials with v, kate_division by (X - z), and the commitment
+ * of the quotient (hsw_gadget_msm with n_bases = rows commits d_quotients[g] as it lies).  Every value mod p; column b
+ * holds a_b[j] in cell j for j < input_rows[b] and 0 from there to `rows`; rows is 1 .. 2^28 and need not be a power of
+ * two.
+ *   hsw_gadget_evaluate, query i = (b, t) = (query_column[i], query_point[i]):
+ *       out_evals[i] = sum_{j<rows} a_b[j] * z_t^j
+ *   hsw_gadget_open, group g with columns b_0 .. b_{m-1} = group_columns[group_first[g] .. group_first[g+1]) in the
+ *   caller's order, point z = points[g] and challenge v = challenges[g]:
+ *       c[j] = sum_{i<m} v^(m-1-i) * a_{b_i}[j]         the fold acc * v + a: the FIRST column gets the highest power
+ *       q[j] = sum_{j<i<rows} c[i] * z^(i-j-1)           0 <= j < rows, hence q[rows-1] = 0
+ *       out_evals[g] = c(z) = c[0] + z * q[0]
+ *   so that c(X) - c(z) = (X - z) * q(X).  Subtracting the evaluation from c changes c[0] alone, which q never reads:
+ *   the quotient needs no evaluation first.
+ * d_columns: a HOST array (copied, not kept) of DEVICE pointers, 16-byte aligned, 32-byte cells; input_rows a host
+ * array, NULL = rows everywhere; input_rows[b] = 0 is legal.  Rows of a column at and beyond input_rows[b] are NOT
+ * READ.  points, challenges: HOST memory, 32 bytes each as stored in the representation of the pass, below p.  A column
+ * may sit in several groups and in several queries; duplicate queries are allowed; evaluate reads a column once for all
+ * its points.  d_quotients: a host array of n_groups device pointers; d_quotients[g] receives exactly `rows` cells, the
+ * last one zero.  out_evals: HOST, n_queries (n_groups) x 32 bytes as stored; for hsw_gadget_open it may be NULL.
+ * Nothing in device memory but the gadget's scratch and, for open, the quotients is written.
+ * Cells are in the representation of the pass; every constant is held in Montgomery form, so canonical and Montgomery
+ * cells take the same kernel and the outputs are exact bit for bit in both.
+ * Decided on the device (status: a host array of n_columns words for evaluate, of n_groups words for open; may be NULL):
+ *   HSW_OPEN_CELL_NOT_BELOW_P  a stored cell that was read is not an encoding below p: the column with every query of
+ *                              it, or the group, is REFUSED -- not one byte of its quotient or of its out_evals entries
+ *                              is written.
+ * The others are written; the call returns HSW_OK and the report counts the refusals (first_refused: the lowest such
+ * column or group, ~0 where there is none).
+ * Refused before any launch -- HSW_ERR_INVALID_ARG (hsw_last_error names the culprit): rows 0 or above 2^28; zero
+ * columns, points, queries or groups, an empty group; an index out of range; a pointer (array, column, quotient,
+ * out_evals of evaluate) that is NULL or a device pointer not 16-byte aligned; input_rows[b] > rows; a point or
+ * challenge not below p; unknown flags; a tile_rows outside its range; a quotient that overlaps the `rows` cells of any
+ * column (read or not), or another quotient; HSW_ERR_UNSUPPORTED: HSW_REPR_COMPACT64 cells, a pass whose batches differ in
+ * representation.
+ * Three launches: tiles (a workgroup per tile of tile_rows rows folds, checks, and sums its rows by Horner's rule),
+ * scan (the suffix over the tiles' sums: every tile's carry-in, and c(z)), write (open only: q, one multiply per row).
+ * Every thread owns HSW_OPEN_THREAD_ROWS consecutive rows.  tile_rows: 0, the library's choice (2048), or a power of two
+ * from HSW_OPEN_MIN_TILE_ROWS to 2^20 -- it exists so that small inputs reach the multi-tile and chunked-scan paths; the
+ * output bytes do not depend on it, the report says what was used.  The folded column (groups of two columns or more),
+ * a cell per thread and a cell per tile live in the gadget's scratch: groups (columns of evaluate) go in batches that
+ * hold at most 1 GiB of it, a batch being at least one group, three (two) launches per batch; grown on demand and
+ * freed by hsw_gadget_destroy.  The host reads nothing between the launches of a call.  SHPLONK's multi-point quotient,
+ * the transcript, the blinding terms and h(X) stay the prover's.  Synchronous, on the engine's stream.  (The calls came
+ * under HSW_ABI_MINOR 1: probe for the symbols.) */
+#define HSW_OPEN_CELL_NOT_BELOW_P 4u   /* status bit, the value of HSW_NTT_CELL_NOT_BELOW_P */
+#define HSW_OPEN_MIN_TILE_ROWS 256u
+#define HSW_OPEN_THREAD_ROWS 8u
+typedef struct hsw_evaluate {
+    uint32_t flags, tile_rows;             /* flags: 0; tile_rows: 0 or a power of two, HSW_OPEN_MIN_TILE_ROWS .. 2^20 */
+    uint64_t rows;                         /* 1 .. 2^28 */
+    size_t n_columns;
+    const void *const *d_columns;          /* host array, n_columns device pointers */
+    const uint64_t *input_rows;            /* host, per column, 0 .. rows; NULL = rows everywhere */
+    size_t n_points;
+    const void *points;                    /* host, n_points x 32 bytes as stored, below p */
+    size_t n_queries;
+    const uint32_t *query_column;          /* host, n_queries indices below n_columns */
+    const uint32_t *query_point;           /* host, n_queries indices below n_points */
+    void *out_evals;                       /* host, n_queries x 32 bytes, output */
+    uint32_t *status;                      /* host, n_columns words, output; may be NULL */
+} hsw_evaluate;
+typedef struct hsw_evaluate_report {
+    uint64_t columns, queries, refused_columns, refused_queries, first_refused;   /* first_refused: a column; ~0 where there is none */
+    uint64_t scratch_bytes;                /* the tiles' sums of a batch of columns */
+    uint32_t tile_rows, tiles, thread_rows, launches;   /* what was used; launches: two per batch */
+    float kernel_ms;
+    uint32_t reserved_;
+} hsw_evaluate_report;
+int hsw_gadget_evaluate(hsw_gadget *g, const hsw_evaluate *args, hsw_evaluate_report *report);
+typedef struct hsw_open {
+    uint32_t flags, tile_rows;             /* flags: 0; tile_rows: 0 or a power of two, HSW_OPEN_MIN_TILE_ROWS .. 2^20 */
+    uint64_t rows;                         /* 1 .. 2^28 */
+    size_t n_columns;
+    const void *const *d_columns;          /* host array, n_columns device pointers */
+    const uint64_t *input_rows;            /* host, per column, 0 .. rows; NULL = rows everywhere */
+    size_t n_groups;
+    const uint64_t *group_first;           /* host, n_groups + 1 offsets into group_columns, increasing */
+    const uint32_t *group_columns;         /* host, group_first[n_groups] indices below n_columns */
+    const void *points, *challenges;       /* host, n_groups x 32 bytes each as stored, below p */
+    void *const *d_quotients;              /* host array, n_groups device pointers, rows cells each */
+    void *out_evals;                       /* host, n_groups x 32 bytes, output; may be NULL */
+    uint32_t *status;                      /* host, n_groups words, output; may be NULL */
+} hsw_open;
+typedef struct hsw_open_report {
+    uint64_t groups, written, refused_groups, first_refused;   /* written = rows x groups not refused; first_refused: ~0 where there is none */
+    uint64_t scratch_bytes;                /* of the largest batch of groups */
+    uint32_t tile_rows, tiles, thread_rows, launches;   /* what was used; launches: three per batch */
+    uint32_t batches, reserved_;
+    float kernel_ms, reserved2_;
+} hsw_open_report;
+int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */

@@ -527,6 +527,90 @@ pub struct hsw_msm_report {
     pub finish_ms: f32,
 }
 
+pub const HSW_OPEN_CELL_NOT_BELOW_P: u32 = 4;
+pub const HSW_OPEN_MIN_TILE_ROWS: u32 = 256;
+pub const HSW_OPEN_THREAD_ROWS: u32 = 8;
+
+/// Arguments of `hsw_gadget_evaluate`: `n_columns` columns of 32-byte cells (a host array of device pointers),
+/// `input_rows` per column (NULL: `rows`), `n_points` points in host memory (32 bytes each as stored, below p) and
+/// `n_queries` (column, point) index pairs; `out_evals` is host memory, 32 bytes per query.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_evaluate {
+    pub flags: u32,
+    pub tile_rows: u32,
+    pub rows: u64,
+    pub n_columns: usize,
+    pub d_columns: *const *const c_void,
+    pub input_rows: *const u64,
+    pub n_points: usize,
+    pub points: *const c_void,
+    pub n_queries: usize,
+    pub query_column: *const u32,
+    pub query_point: *const u32,
+    pub out_evals: *mut c_void,
+    pub status: *mut u32,
+}
+
+/// Result of `hsw_gadget_evaluate`; `first_refused` (a column) is `u64::MAX` where there is none.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_evaluate_report {
+    pub columns: u64,
+    pub queries: u64,
+    pub refused_columns: u64,
+    pub refused_queries: u64,
+    pub first_refused: u64,
+    pub scratch_bytes: u64,
+    pub tile_rows: u32,
+    pub tiles: u32,
+    pub thread_rows: u32,
+    pub launches: u32,
+    pub kernel_ms: f32,
+    pub reserved_: u32,
+}
+
+/// Arguments of `hsw_gadget_open`: group `g` folds the columns `group_columns[group_first[g] .. group_first[g + 1])` with
+/// `challenges[g]` (the first column the highest power) and divides by `(X - points[g])`; `d_quotients[g]` receives
+/// `rows` cells, `out_evals` (may be NULL) the value of the folded column at the point.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_open {
+    pub flags: u32,
+    pub tile_rows: u32,
+    pub rows: u64,
+    pub n_columns: usize,
+    pub d_columns: *const *const c_void,
+    pub input_rows: *const u64,
+    pub n_groups: usize,
+    pub group_first: *const u64,
+    pub group_columns: *const u32,
+    pub points: *const c_void,
+    pub challenges: *const c_void,
+    pub d_quotients: *const *mut c_void,
+    pub out_evals: *mut c_void,
+    pub status: *mut u32,
+}
+
+/// Result of `hsw_gadget_open`; `first_refused` (a group) is `u64::MAX` where there is none.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_open_report {
+    pub groups: u64,
+    pub written: u64,
+    pub refused_groups: u64,
+    pub first_refused: u64,
+    pub scratch_bytes: u64,
+    pub tile_rows: u32,
+    pub tiles: u32,
+    pub thread_rows: u32,
+    pub launches: u32,
+    pub batches: u32,
+    pub reserved_: u32,
+    pub kernel_ms: f32,
+    pub reserved2_: f32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -816,6 +900,12 @@ extern "C" {
     /// host memory.  Per column `status[b]` carries `HSW_MSM_CELL_NOT_BELOW_P` (that column is not written) or
     /// `HSW_MSM_BASE_NOT_BELOW_Q` (nothing is written).
     pub fn hsw_gadget_msm(g: *mut hsw_gadget, args: *const hsw_msm, report: *mut hsw_msm_report) -> c_int;
+    /// Device columns evaluated at points: `out_evals[i] = sum_j a[j] * z^j` per (column, point) query, in host memory.
+    /// Per column `status[b]` carries `HSW_OPEN_CELL_NOT_BELOW_P` (no query of that column is written).
+    pub fn hsw_gadget_evaluate(g: *mut hsw_gadget, args: *const hsw_evaluate, report: *mut hsw_evaluate_report) -> c_int;
+    /// The opening quotients of GWC, written on the device: per group the fold with v and the division by `(X - z)`.
+    /// Per group `status[g]` carries `HSW_OPEN_CELL_NOT_BELOW_P` (that group is not written).
+    pub fn hsw_gadget_open(g: *mut hsw_gadget, args: *const hsw_open, report: *mut hsw_open_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

@@ -347,6 +347,41 @@ class OpenReport(C.Structure):
                 ("launches", C.c_uint32), ("batches", C.c_uint32), ("reserved_", C.c_uint32), ("kernel_ms", C.c_float), ("reserved2_", C.c_float)]
 
 
+HSW_QUOTIENT_CELL_NOT_BELOW_P, HSW_QUOTIENT_MAX_FACTORS, HSW_QUOTIENT_MAX_EXTENSION = 4, 8, 8
+
+
+class QuotientGates(C.Structure):
+    """hsw_quotient_gates: the gates as sums of monomials."""
+    _fields_ = [("n_gates", C.c_size_t), ("n_terms", C.c_size_t), ("n_factors", C.c_size_t), ("gate_first_term", C.POINTER(C.c_uint32)),
+                ("term_coeffs", C.c_void_p), ("term_first_factor", C.POINTER(C.c_uint32)), ("factor_column", C.POINTER(C.c_uint32)),
+                ("factor_rotation", C.POINTER(C.c_int32))]
+
+
+class QuotientLookups(C.Structure):
+    """hsw_quotient_lookups: the lookup arguments, their columns folded with theta."""
+    _fields_ = [("n_lookups", C.c_size_t), ("first_input", C.POINTER(C.c_uint32)), ("inputs", C.POINTER(C.c_uint32)),
+                ("first_table", C.POINTER(C.c_uint32)), ("tables", C.POINTER(C.c_uint32)), ("d_permuted_inputs", C.POINTER(C.c_void_p)),
+                ("d_permuted_tables", C.POINTER(C.c_void_p)), ("d_products", C.POINTER(C.c_void_p)), ("thetas", C.c_void_p)]
+
+
+class Quotient(C.Structure):
+    """hsw_quotient: the quotient h(X) of device columns on the extended coset (hsw_gadget_quotient)."""
+    _fields_ = [("flags", C.c_uint32), ("log_rows", C.c_uint32), ("log_n", C.c_uint32), ("chunk_columns", C.c_uint32),
+                ("usable_rows", C.c_uint64), ("n_proofs", C.c_size_t), ("n_columns", C.c_size_t), ("n_fixed", C.c_size_t),
+                ("d_columns", C.POINTER(C.c_void_p)), ("d_fixed", C.POINTER(C.c_void_p)), ("d_l0", C.c_void_p), ("d_l_last", C.c_void_p),
+                ("d_l_active", C.c_void_p), ("gates", QuotientGates), ("n_perm_columns", C.c_size_t), ("perm_columns", C.POINTER(C.c_uint32)),
+                ("d_sigmas", C.POINTER(C.c_void_p)), ("d_perm_products", C.POINTER(C.c_void_p)), ("lookups", QuotientLookups),
+                ("betas", C.c_void_p), ("gammas", C.c_void_p), ("ys", C.c_void_p), ("omega_ext", C.c_void_p), ("zeta", C.c_void_p),
+                ("delta", C.c_void_p), ("d_h", C.POINTER(C.c_void_p)), ("status", C.POINTER(C.c_uint32))]
+
+
+class QuotientReport(C.Structure):
+    _fields_ = [("proofs", C.c_uint64), ("written", C.c_uint64), ("refused_proofs", C.c_uint64), ("first_refused", C.c_uint64),
+                ("expressions", C.c_uint64), ("scratch_bytes", C.c_uint64), ("launches", C.c_uint32), ("rows_per_thread", C.c_uint32),
+                ("kernel_ms", C.c_float), ("gates_ms", C.c_float), ("permutation_ms", C.c_float), ("lookups_ms", C.c_float),
+                ("finish_ms", C.c_float)]
+
+
 # every symbol include/hsw.h declares (tests check the library exports them all)
 SYMBOLS = (
     "hsw_shape_query", "hsw_chip_rows", "hsw_engine_create", "hsw_engine_destroy",
@@ -370,7 +405,7 @@ SYMBOLS = (
     "hsw_gadget_ties", "hsw_gadget_cell_address", "hsw_gadget_verify_ties", "hsw_gadget_verify_equal",
     "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities", "hsw_gadget_lookup_permuted",
     "hsw_gadget_lookup_product", "hsw_gadget_permutation_product", "hsw_gadget_ntt",
-    "hsw_gadget_msm", "hsw_gadget_evaluate", "hsw_gadget_open",
+    "hsw_gadget_msm", "hsw_gadget_evaluate", "hsw_gadget_open", "hsw_gadget_quotient",
 )
 
 
@@ -487,6 +522,9 @@ def lib():
         if hasattr(L, "hsw_gadget_open"):   # likewise
             L.hsw_gadget_open.restype = C.c_int
             L.hsw_gadget_open.argtypes = [vp, C.POINTER(Open), C.POINTER(OpenReport)]
+        if hasattr(L, "hsw_gadget_quotient"):   # likewise
+            L.hsw_gadget_quotient.restype = C.c_int
+            L.hsw_gadget_quotient.argtypes = [vp, C.POINTER(Quotient), C.POINTER(QuotientReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

@@ -300,6 +300,11 @@ int hsw_engine_set_option(hsw_engine *e, const char *name, int64_t value) try {
         e->permuted_scratch = (size_t)value;
         return HSW_OK;
     }
+    if (std::strcmp(name, "quotient_scratch") == 0) {  // hsw_gadget_quotient: bytes of accumulators per batch of proofs; tests shrink it to reach batches
+        if (value < 1 || value > ((int64_t)1 << 30)) return set_err(e, HSW_ERR_INVALID_ARG, "quotient_scratch must be 1 .. 2^30 bytes");
+        e->quotient_scratch = (size_t)value;
+        return HSW_OK;
+    }
     if (std::strcmp(name, "chunk_blocks") == 0) {      // blocks per launch of a long batch; tests shrink it to reach that loop
         if (value < 1 || value > (1 << 20)) return set_err(e, HSW_ERR_INVALID_ARG, "chunk_blocks must be 1 .. 2^20");
         e->chunk_blocks = (size_t)value;

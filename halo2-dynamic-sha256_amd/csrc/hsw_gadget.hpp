@@ -20,7 +20,7 @@
 // Implemented in several translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
 // call), hsw_gadget_context.cpp (Context: buffers, layouts, bind / unbind, the jump table), hsw_gadget_digest.cpp (the
 // digest paths and the ties), hsw_gadget_lookup.cpp (the lookup entries of a pass, listed and counted),
-// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z), hsw_gadget_permutation.cpp (the permutation argument's grand products), hsw_gadget_ntt.cpp (the Fr NTT of device columns), hsw_gadget_msm.cpp (their commitments: the G1 MSM), hsw_gadget_open.cpp (their evaluations and opening quotients) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
+// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z), hsw_gadget_permutation.cpp (the permutation argument's grand products), hsw_gadget_ntt.cpp (the Fr NTT of device columns), hsw_gadget_msm.cpp (their commitments: the G1 MSM), hsw_gadget_open.cpp (their evaluations and opening quotients), hsw_gadget_quotient.cpp (the quotient h(X) on the extended coset) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
 #ifndef HSW_GADGET_HPP
 #define HSW_GADGET_HPP
 
@@ -396,6 +396,8 @@ struct hsw_gadget {
     size_t msm_cap = 0;                             // the partial buckets of a group of columns, in bytes; grown and freed like d_pairs
     void *d_open = nullptr;                         // hsw_gadget_evaluate / _open (hsw_gadget_open.cpp): status words, evaluations, columns, groups,
     size_t open_cap = 0;                            // staged powers and the scratch of a batch, in bytes; grown and freed like d_pairs
+    void *d_quotient = nullptr;                     // hsw_gadget_quotient (hsw_gadget_quotient.cpp): status words, descriptor tables, staged constants
+    size_t quotient_cap = 0;                        // and the accumulators V of a batch, in bytes; grown and freed like d_pairs
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

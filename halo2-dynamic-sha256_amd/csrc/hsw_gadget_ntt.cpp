@@ -17,31 +17,15 @@ namespace {
 const size_t NTT_SCRATCH_BYTES = (size_t)1 << 30;              // the points of a group of columns between launches
 const size_t NTT_GRID_COLUMNS = 65535;                         // blockIdx.y
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Events {                                     // the stage boundaries of one call
-    std::vector<hipEvent_t> ev;
-    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    hipError_t record(hipStream_t s) {
-        hipEvent_t e = nullptr;
-        hipError_t he = hipEventCreate(&e);
-        if (he != hipSuccess) return he;
-        ev.push_back(e);
-        return hipEventRecord(e, s);
-    }
-};
-
-struct Interval { uintptr_t lo, hi; size_t column; bool out; };   // bytes [lo, hi) that a column writes or reads
+using hsw::align256;
+using hsw::Events;
+using hsw::Interval;
+using hsw::load_below_p;
 
 int fail_column(hsw_engine *e, int status, const char *what, size_t b) {
     char buf[200];
     std::snprintf(buf, sizeof buf, "column %zu: %s", b, what);
     return hsw_engine_fail(e, status, buf);
-}
-
-bool load_below_p(hsw::PFe &x, const void *stored) {
-    std::memcpy(&x, stored, 32);
-    return hsw::pfe_below_p(x);
 }
 
 }  // namespace
@@ -69,25 +53,17 @@ extern "C" int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report
         const uintptr_t in = reinterpret_cast<uintptr_t>(args->d_inputs[b]), out = reinterpret_cast<uintptr_t>(args->d_outputs[b]);
         if (!in || (in & 15u)) return fail_column(e, HSW_ERR_INVALID_ARG, "an input pointer that is NULL or not 16-byte aligned", b);
         if (!out || (out & 15u)) return fail_column(e, HSW_ERR_INVALID_ARG, "an output pointer that is NULL or not 16-byte aligned", b);
-        iv.push_back(Interval{out, out + (uintptr_t)N * HSW_CELL_BYTES, b, true});
-        if (rows && in != out) iv.push_back(Interval{in, in + (uintptr_t)rows * HSW_CELL_BYTES, b, false});   // (in place: the output's interval stands for both)
+        iv.push_back(Interval{out, out + (uintptr_t)N * HSW_CELL_BYTES, b, true, 0});
+        if (rows && in != out) iv.push_back(Interval{in, in + (uintptr_t)rows * HSW_CELL_BYTES, b, false, 0});   // (in place: the output's interval stands for both)
     }
-    // an output may overlap neither another output nor an input that is not its own in place: one sweep in address
-    // order, with the furthest end of the outputs (and whose it is) and of all intervals seen so far
-    std::sort(iv.begin(), iv.end(), [](const Interval &x, const Interval &y) { return x.lo < y.lo; });
-    uintptr_t end_out = 0, end_any = 0;
-    size_t out_column = 0;
-    for (const Interval &x : iv) {
-        if (x.out ? x.lo < end_any : x.lo < end_out)
-            return fail_column(e, HSW_ERR_INVALID_ARG, "its output overlaps an input that is not its own in place, or another output", x.out ? x.column : out_column);
-        if (x.out && x.hi > end_out) { end_out = x.hi; out_column = x.column; }
-        end_any = std::max(end_any, x.hi);
-    }
+    // an output may overlap neither another output nor an input that is not its own in place
+    Interval writer{}, with{};
+    if (hsw::output_overlaps(iv, &writer, &with))
+        return fail_column(e, HSW_ERR_INVALID_ARG, "its output overlaps an input that is not its own in place, or another output", writer.index);
     if (!args->omega) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "omega is NULL");
-    uint32_t repr = 0;
-    if (hsw::pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
-    if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "32-byte cells only");
-    const bool mont = (repr & HSW_REPR_MONTGOMERY) != 0;
+    bool mont = false;
+    const int prc = hsw::pass_cells(c, &mont);
+    if (prc != HSW_OK) return prc;
     hsw::PFe omega, shift = hsw::fr_zero(), scale = hsw::fr_zero();
     if (!load_below_p(omega, args->omega) || (args->shift && !load_below_p(shift, args->shift)) || (args->scale && !load_below_p(scale, args->scale)))
         return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "omega, shift or scale whose stored limbs are not below p");

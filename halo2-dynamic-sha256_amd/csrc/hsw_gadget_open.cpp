@@ -17,31 +17,15 @@ namespace {
 const size_t OPEN_SCRATCH_BYTES = (size_t)1 << 30;             // the scratch of a batch
 const size_t OPEN_GRID_Y = 65535;                              // blockIdx.y
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Events {                                     // the stage boundaries of one call
-    std::vector<hipEvent_t> ev;
-    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    hipError_t record(hipStream_t s) {
-        hipEvent_t e = nullptr;
-        hipError_t he = hipEventCreate(&e);
-        if (he != hipSuccess) return he;
-        ev.push_back(e);
-        return hipEventRecord(e, s);
-    }
-};
-
-struct Interval { uintptr_t lo, hi; size_t index; bool out; };    // bytes [lo, hi) that a quotient writes or a column reads
+using hsw::align256;
+using hsw::Events;
+using hsw::Interval;
+using hsw::load_below_p;
 
 int fail_at(hsw_engine *e, const char *kind, size_t i, const char *what) {
     char buf[200];
     std::snprintf(buf, sizeof buf, "%s %zu: %s", kind, i, what);
     return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, buf);
-}
-
-bool load_below_p(hsw::PFe &x, const void *stored) {
-    std::memcpy(&x, stored, 32);
-    return hsw::pfe_below_p(x);
 }
 
 // what both calls ask of rows, tile_rows, the columns and the representation; 0 or the status to return
@@ -58,11 +42,7 @@ int check_common(hsw_engine *e, hsw::Context &c, uint32_t flags, uint64_t rows, 
         const uintptr_t in = reinterpret_cast<uintptr_t>(d_columns[b]);
         if (!in || (in & 15u)) return fail_at(e, "column", b, "a pointer that is NULL or not 16-byte aligned");
     }
-    uint32_t repr = 0;
-    if (hsw::pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
-    if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "32-byte cells only");
-    mont = (repr & HSW_REPR_MONTGOMERY) != 0;
-    return HSW_OK;
+    return hsw::pass_cells(c, &mont);
 }
 
 int grow(hsw_gadget *g, size_t bytes) {                        // (every earlier call has been waited for: nothing reads the old one)
@@ -224,7 +204,7 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
     iv.reserve(n + n_groups);
     for (size_t b = 0; b < n; b++) {                             // (a column counts with all its `rows` cells, read or not)
         const uintptr_t in = reinterpret_cast<uintptr_t>(args->d_columns[b]);
-        iv.push_back(Interval{in, in + (uintptr_t)rows * HSW_CELL_BYTES, b, false});
+        iv.push_back(Interval{in, in + (uintptr_t)rows * HSW_CELL_BYTES, b, false, 0});
     }
     for (size_t k = 0; k < n_groups; k++) {
         const uint64_t f0 = args->group_first[k], f1 = args->group_first[k + 1];
@@ -236,19 +216,11 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
         if (!load_below_p(v[k], static_cast<const uint8_t *>(args->challenges) + 32 * k)) return fail_at(e, "group", k, "a challenge whose stored limbs are not below p");
         const uintptr_t q = reinterpret_cast<uintptr_t>(args->d_quotients[k]);
         if (!q || (q & 15u)) return fail_at(e, "group", k, "a quotient pointer that is NULL or not 16-byte aligned");
-        iv.push_back(Interval{q, q + (uintptr_t)rows * HSW_CELL_BYTES, k, true});
+        iv.push_back(Interval{q, q + (uintptr_t)rows * HSW_CELL_BYTES, k, true, 0});
     }
-    // a quotient may overlap neither the `rows` cells of a column nor another quotient: one sweep in address order, with
-    // the furthest end of the quotients (and whose it is) and of all intervals seen so far
-    std::sort(iv.begin(), iv.end(), [](const Interval &x, const Interval &y) { return x.lo < y.lo; });
-    uintptr_t end_out = 0, end_any = 0;
-    size_t out_group = 0;
-    for (const Interval &x : iv) {
-        if (x.out ? x.lo < end_any : x.lo < end_out)
-            return fail_at(e, "group", x.out ? x.index : out_group, "its quotient overlaps a column or another quotient");
-        if (x.out && x.hi > end_out) { end_out = x.hi; out_group = x.index; }
-        end_any = std::max(end_any, x.hi);
-    }
+    // a quotient may overlap neither the `rows` cells of a column nor another quotient
+    Interval writer{}, with{};
+    if (hsw::output_overlaps(iv, &writer, &with)) return fail_at(e, "group", writer.index, "its quotient overlaps a column or another quotient");
     // batches of groups whose scratch fits: per group the tiles' sums, a cell per thread and, for two columns or more, c
     const size_t n_refs = (size_t)args->group_first[n_groups];
     const size_t tile_bytes = (size_t)geo.n_tiles * sizeof(hsw::PFe), seed_bytes = align256((size_t)geo.seeds * sizeof(hsw::PFe));

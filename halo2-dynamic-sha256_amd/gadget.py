@@ -1041,6 +1041,152 @@ class Sha256DynamicConfig:
         return (out if isinstance(out, torch.Tensor) else None, evals, status,
                 {f[0]: getattr(rep, f[0]) for f in N.OpenReport._fields_ if not f[0].startswith("reserved")})
 
+    def quotient(self, log_rows, log_n, usable_rows, columns, ys, omega_ext, zeta, fixed=None, gates=(), l0=None, l_last=None,
+                 l_active=None, perm_columns=(), chunk_columns=0, sigmas=None, perm_products=None, delta=None, betas=None, gammas=None,
+                 lookups=(), permuted_inputs=None, permuted_tables=None, lookup_products=None, thetas=None, out=None):
+        """hsw_gadget_quotient: h(X) on the extended coset for K independent proofs of one circuit -- every gate,
+        permutation and lookup expression folded with y (V = V y + expr, in the order of include/hsw.h) and divided by
+        the vanishing polynomial.  Returns (h, status, report): a uint64 device tensor (K, N, 4), the uint32 numpy
+        status array per proof (HSW_QUOTIENT_CELL_NOT_BELOW_P: that proof's h was not written) and the report as a dict.
+        Every column holds N = 2^log_n cells in extended form.  columns: a contiguous uint64 tensor (K, m, rows >= N, 4)
+        on the engine's device, or K sequences of m device addresses (16-byte aligned), as ntt takes them; fixed: the
+        shared columns, a tensor (F, rows, 4) or F addresses -- column index m + j.  gates: a list of gates, each a list
+        of monomials (coeff, [(column, rotation), ...]) with coeff a field element AS STORED and the rotation in base
+        rows.  l0, l_last, l_active: a tensor (rows, 4) or an address each, needed with a permutation or a lookup.
+        perm_columns: the permutation's column indices in its order, chunk_columns at a time; sigmas: (n_perm, rows, 4) or
+        addresses; perm_products: (K, S, rows, 4) or K sequences of S addresses.  lookups: a list of (input column
+        indices, table column indices), folded with theta, the first listed the highest power; permuted_inputs,
+        permuted_tables, lookup_products: (K, n_lookups, rows, 4) or K sequences of addresses.  ys, betas, gammas,
+        thetas: K field elements as stored; omega_ext, zeta, delta: one each.  out: the caller's own contiguous uint64
+        tensor (K, rows >= N, 4), rows beyond N are never written, or K device addresses (then None is returned)."""
+        import numpy as np
+        import torch
+        dev = self.engine.device
+        log_rows, log_n, u, chunk = int(log_rows), int(log_n), int(usable_rows), int(chunk_columns)
+        if log_n > 28 or log_rows < 0 or not 1 <= log_n - log_rows <= N.HSW_QUOTIENT_MAX_EXTENSION:
+            raise ValueError("log_n at most 28 and log_n - log_rows 1 .. %d" % N.HSW_QUOTIENT_MAX_EXTENSION)
+        n, n_ext = 1 << log_rows, 1 << log_n
+        if u < 1 or u >= n:
+            raise ValueError("usable_rows must be 1 .. 2^log_rows - 1")
+
+        def grid(name, t, shape):
+            """the device addresses of a grid of columns of N cells, row-major: a tensor shape + (rows >= N, 4) or nested addresses"""
+            count = int(np.prod(shape)) if shape else 1
+            if isinstance(t, torch.Tensor):
+                if t.dtype != torch.uint64 or t.device != dev:
+                    raise ValueError("%s must be a uint64 tensor on %s" % (name, dev))
+                if t.dim() != len(shape) + 2 or tuple(t.shape[:len(shape)]) != tuple(shape) or t.shape[-2] < n_ext or t.shape[-1] != 4 or not t.is_contiguous():
+                    raise ValueError("%s must be contiguous, of shape %s + (rows >= %d, 4)" % (name, tuple(shape), n_ext))
+                return [t.data_ptr() + a * t.shape[-2] * 32 for a in range(count)]
+            if t is None:
+                raise ValueError("%s: %d column(s)" % (name, count))
+            def flatten(v):
+                return [int(v)] if isinstance(v, (int, np.integer)) else [p for row in v for p in flatten(row)]
+            ptrs = flatten(t)
+            if len(ptrs) != count or any(p <= 0 for p in ptrs):      # (alignment: the library's refusal names the column)
+                raise ValueError("%s: %d device addresses" % (name, count))
+            return ptrs
+
+        if isinstance(columns, torch.Tensor):
+            if columns.dim() != 4:
+                raise ValueError("columns must be of shape (K, m, rows, 4)")
+            k, m = int(columns.shape[0]), int(columns.shape[1])
+        else:
+            columns = [list(row) for row in columns]
+            k, m = len(columns), len(columns[0]) if columns else 0
+        if k < 1:
+            raise ValueError("columns: at least one proof")
+        cols = grid("columns", columns, (k, m)) if m else []
+        if fixed is None:
+            n_fixed, fix = 0, []
+        else:
+            n_fixed = int(fixed.shape[0]) if isinstance(fixed, torch.Tensor) and fixed.dim() else len(fixed)
+            fix = grid("fixed", fixed, (n_fixed,)) if n_fixed else []
+        width = m + n_fixed
+        # the gates
+        first_term, coeffs, first_factor, f_col, f_rot = [0], [], [0], [], []
+        for gate in gates:
+            for coeff, factors in gate:
+                factors = [(int(cj), int(r)) for cj, r in factors]
+                if len(factors) > N.HSW_QUOTIENT_MAX_FACTORS:
+                    raise ValueError("gates: a monomial has at most %d factors" % N.HSW_QUOTIENT_MAX_FACTORS)
+                if any(cj < 0 or cj >= width for cj, _ in factors):
+                    raise ValueError("gates: a column index is not below %d" % width)
+                if any(abs(r) >= n for _, r in factors):
+                    raise ValueError("gates: a rotation is not below 2^log_rows in size")
+                coeffs.append(int(coeff))
+                f_col += [cj for cj, _ in factors]
+                f_rot += [r for _, r in factors]
+                first_factor.append(len(f_col))
+            first_term.append(len(coeffs))
+        n_gates = len(first_term) - 1
+        perm = [int(j) for j in perm_columns]
+        lks = [([int(j) for j in ins], [int(j) for j in tabs]) for ins, tabs in lookups]
+        if not n_gates and not perm and not lks:
+            raise ValueError("no gate, no permutation and no lookup: nothing to fold")
+        if any(j < 0 or j >= width for j in perm):
+            raise ValueError("perm_columns: a column index is not below %d" % width)
+        if any(j < 0 or j >= width for ins, tabs in lks for j in ins + tabs):
+            raise ValueError("lookups: a column index is not below %d" % width)
+        if any(not ins or not tabs for ins, tabs in lks):
+            raise ValueError("lookups: at least one input and one table column each")
+        fe = self._field_elements
+        y_buf, w_buf, z_buf = fe("ys", ys, k), fe("omega_ext", omega_ext, 1), fe("zeta", zeta, 1)
+        c_buf = fe("gates: coefficients", coeffs, len(coeffs)) if coeffs else np.zeros((0, 4), dtype=np.uint64)
+        args = N.Quotient()
+        args.log_rows, args.log_n, args.chunk_columns, args.usable_rows = log_rows, log_n, chunk, u
+        args.n_proofs, args.n_columns, args.n_fixed = k, m, n_fixed
+        keep = [y_buf, w_buf, z_buf, c_buf]                  # what the struct points into
+
+        def u32(v):
+            a = (C.c_uint32 * max(len(v), 1))(*v)
+            keep.append(a)
+            return a
+
+        def table(v):
+            a = (C.c_void_p * max(len(v), 1))(*v)
+            keep.append(a)
+            return a
+        args.d_columns, args.d_fixed = table(cols), table(fix) if n_fixed else None
+        args.ys, args.omega_ext, args.zeta = y_buf.ctypes.data, w_buf.ctypes.data, z_buf.ctypes.data
+        if n_gates:
+            rot = (C.c_int32 * max(len(f_rot), 1))(*f_rot)
+            keep.append(rot)
+            args.gates = N.QuotientGates(n_gates, len(coeffs), len(f_col), u32(first_term), c_buf.ctypes.data, u32(first_factor), u32(f_col), rot)
+        if perm or lks:
+            b_buf, g_buf = fe("betas", betas, k), fe("gammas", gammas, k)
+            keep += [b_buf, g_buf]
+            args.betas, args.gammas = b_buf.ctypes.data, g_buf.ctypes.data
+            args.d_l0, args.d_l_last, args.d_l_active = grid("l0", l0, ())[0], grid("l_last", l_last, ())[0], grid("l_active", l_active, ())[0]
+        if perm:
+            if chunk < 1:
+                raise ValueError("chunk_columns is at least 1")
+            sets = (len(perm) + min(chunk, len(perm)) - 1) // min(chunk, len(perm))
+            d_buf = fe("delta", delta, 1)
+            keep.append(d_buf)
+            args.n_perm_columns, args.perm_columns, args.delta = len(perm), u32(perm), d_buf.ctypes.data
+            args.d_sigmas, args.d_perm_products = table(grid("sigmas", sigmas, (len(perm),))), table(grid("perm_products", perm_products, (k, sets)))
+        if lks:
+            t_buf = fe("thetas", thetas, k)
+            keep.append(t_buf)
+            fi, ft = [0], [0]
+            for ins, tabs in lks:
+                fi.append(fi[-1] + len(ins))
+                ft.append(ft[-1] + len(tabs))
+            args.lookups = N.QuotientLookups(len(lks), u32(fi), u32([j for ins, _ in lks for j in ins]), u32(ft), u32([j for _, tabs in lks for j in tabs]),
+                                             table(grid("permuted_inputs", permuted_inputs, (k, len(lks)))),
+                                             table(grid("permuted_tables", permuted_tables, (k, len(lks)))),
+                                             table(grid("lookup_products", lookup_products, (k, len(lks)))), t_buf.ctypes.data)
+        if out is None:
+            out = torch.zeros((k, n_ext, 4), dtype=torch.uint64, device=dev)
+        args.d_h = table(grid("out", out, (k,)))
+        status = np.zeros(k, dtype=np.uint32)
+        args.status = status.ctypes.data_as(C.POINTER(C.c_uint32))
+        rep = N.QuotientReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the call runs on the engine's
+        self._ok(self.lib.hsw_gadget_quotient(self.h, C.byref(args), C.byref(rep)))
+        return out if isinstance(out, torch.Tensor) else None, status, {f[0]: getattr(rep, f[0]) for f in N.QuotientReport._fields_}
+
     def seek(self, hash_idx):
         """Continue at digest #hash_idx as if the earlier ones had been assigned (their positions
         follow from max_variable_byte_sizes alone): lets several GPUs share one circuit's digests."""

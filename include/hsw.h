@@ -1481,6 +1481,104 @@ typedef struct hsw_open_report {
     float kernel_ms, reserved2_;
 } hsw_open_report;
 int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_report *report);
+/* ---- the quotient h(X) of device columns on the extended coset ----
+ * What halo2's evaluate_h and vanishing argument do between the last grand product and the commitments of h: the
+ * numerator -- every gate, permutation and lookup expression folded with y -- divided by the vanishing polynomial, row
+ * by row on the extended coset, for K independent proofs of one circuit.  Every column already lies in device memory
+ * in extended form (hsw_gadget_ntt's coeff_to_extended leaves it there); the caller brings h back with
+ * extended_to_coeff, cuts it into n-row pieces and commits them with hsw_gadget_msm.
+ * n = 2^log_rows, N = 2^log_n, e = log_n - log_rows, w = omega_ext, X_i = zeta * w^i; every value mod p.  Rotation r of
+ * a base-domain query reads extended row (i + r * 2^e) mod N; u = usable_rows, and the last rotation -(blinding + 1) is
+ * the shift +u in base rows.  Per proof c with its own theta, beta, gamma, y: V starts at 0 and every expression below
+ * folds as V = V * y + expr, in exactly this order (assumption A9, DESIGN.md 5.5e: a fork that orders the gates or the
+ * lookups differently changes only the order of the lists the caller passes):
+ *   1. gates, in the listed order: gate_g[i] = sum_t coeff_t * prod_f col_{t,f}[(i + rot_{t,f} * 2^e) mod N]; a monomial
+ *      with no factor is the constant coeff.  Columns share one index space: 0 .. m-1 the proof's own d_columns[c*m + j],
+ *      m .. m+F-1 the shared d_fixed[j - m].  (The FlexGate gate q (a + b c - d) is the three monomials +1 q a(0),
+ *      +1 q b(1) c(2), (p - 1) q d(3).)
+ *   2. permutation (n_perm_columns > 0), S = ceil(n_perm_columns / L) sets:
+ *        l0 * (1 - Z_0);   l_last * (Z_{S-1}^2 - Z_{S-1});   s = 1 .. S-1: l0 * (Z_s - Z_{s-1}[(i + u * 2^e) mod N]);
+ *        s = 0 .. S-1: l_active * (Z_s[(i + 2^e) mod N] * prod_j (v_j + beta * sigma_j + gamma)
+ *                                  - Z_s * prod_j (v_j + beta * delta^j * X_i + gamma))
+ *      j over the set's columns, the exponent of delta the column's position in the whole permutation.
+ *   3. lookups, in the listed order; A the fold acc * theta + col over the input columns, Sv over the table columns
+ *      (the first listed column gets the highest power):
+ *        l0 * (1 - Z);   l_last * (Z^2 - Z);
+ *        l_active * (Z[(i + 2^e) mod N] * (A' + beta) * (S' + gamma) - Z * (A + beta) * (Sv + gamma));
+ *        l0 * (A' - S');   l_active * (A' - S') * (A' - A'[(i - 2^e) mod N])
+ *   h[i] = V[i] * t_inv[i mod 2^e],  t_inv[r] = (zeta^n * (w^n)^r - 1)^-1: 2^e constants, inverted on the host.
+ * Every array of indices, offsets, coefficients and challenges is HOST memory (copied, not kept); d_columns, d_fixed,
+ * d_sigmas, d_perm_products, the three lookup tables of pointers and d_h are HOST arrays of DEVICE pointers, 16-byte
+ * aligned, N 32-byte cells each in the representation of the pass.  Coefficients and challenges: 32 bytes as stored in
+ * that representation, below p.  V is held in the representation of the cells; the R factors that products of
+ * canonical cells lose are absorbed into staged constants (coeff * R^d per monomial, one scaled l0 / l_last / l_active
+ * per row), so the output is exact bit for bit in both forms.  Nothing in device memory but the gadget's scratch and
+ * d_h is written.
+ * Decided on the device (status: a host array of K words; may be NULL):
+ *   HSW_QUOTIENT_CELL_NOT_BELOW_P  a stored cell that the proof read is not an encoding below p: the proof is REFUSED --
+ *                                  not one byte of its d_h[c] is written.
+ * The others are written; the call returns HSW_OK and the report counts the refusals.  Nothing outside rows [0, N) of
+ * the d_h of written proofs is ever written.
+ * Refused before any launch -- HSW_ERR_INVALID_ARG (hsw_last_error names the item): n_proofs 0; all three families
+ * empty; log_n above 28; e outside 1 .. HSW_QUOTIENT_MAX_EXTENSION; usable_rows 0 or >= n; unknown flags; an offset
+ * array that is not ascending or does not end at its count; a monomial of more than HSW_QUOTIENT_MAX_FACTORS factors; a
+ * column index >= m + F; |rotation| >= n; a lookup without an input or a table column; a pointer (array or column) that
+ * is NULL where it is needed or not 16-byte aligned; a coefficient, challenge, zeta or delta that is missing where
+ * needed or not below p; omega_ext with w^(N/2) != p - 1; a zeta for which some zeta^n (w^n)^r - 1 is 0; a d_h[c]
+ * whose N cells overlap any column the call reads or another d_h.  HSW_ERR_TOO_LARGE: counts that do not fit 32 bits.
+ * HSW_ERR_UNSUPPORTED: HSW_REPR_COMPACT64 cells, a pass whose batches differ in representation.
+ * One launch per family that is present (all gates; all sets; all lookups) and the finish, per batch of proofs; a
+ * thread owns rows_per_thread consecutive rows.  V lives in the gadget's scratch, N cells per proof: proofs go in
+ * batches whose scratch stays under 1 GiB (the engine option "quotient_scratch", 1 .. 2^30 bytes, lowers it: a test
+ * knob), a batch being at least one proof; grown on demand and freed by hsw_gadget_destroy.  The host reads nothing
+ * between the launches.  Synchronous, on the engine's stream.
+ * Not built: lookup inputs and tables that are expressions (q * a) rather than single columns folded with theta;
+ * halo2's fold of several circuit instances into one h under one transcript (K means K independent proofs); the domain
+ * constants, l0 / l_last / l_active in extended form, the blinding rows, the split of h into pieces and the transcript
+ * stay the prover's.  (The call came under HSW_ABI_MINOR 1: probe for the symbol.) */
+#define HSW_QUOTIENT_CELL_NOT_BELOW_P 4u   /* status bit, the value of HSW_NTT_CELL_NOT_BELOW_P */
+#define HSW_QUOTIENT_MAX_FACTORS 8u        /* factors of one monomial */
+#define HSW_QUOTIENT_MAX_EXTENSION 8u      /* e = log_n - log_rows, 1 .. 8 */
+typedef struct hsw_quotient_gates {        /* all HOST arrays, copied, not kept; n_gates 0: no gate */
+    size_t n_gates, n_terms, n_factors;
+    const uint32_t *gate_first_term;       /* n_gates + 1, ascending, [n_gates] == n_terms */
+    const void *term_coeffs;               /* n_terms x 32 bytes as stored, below p */
+    const uint32_t *term_first_factor;     /* n_terms + 1, ascending, [n_terms] == n_factors, <= MAX_FACTORS per term */
+    const uint32_t *factor_column;         /* n_factors, < m + F */
+    const int32_t *factor_rotation;        /* n_factors, |r| < n */
+} hsw_quotient_gates;
+typedef struct hsw_quotient_lookups {      /* n_lookups 0: none */
+    size_t n_lookups;
+    const uint32_t *first_input, *inputs;  /* n_lookups + 1 offsets; column indices < m + F, at least one per lookup */
+    const uint32_t *first_table, *tables;  /* likewise */
+    const void *const *d_permuted_inputs, *const *d_permuted_tables, *const *d_products;  /* contexts x n_lookups, [c*n_lookups + l], N cells, extended form */
+    const void *thetas;                    /* host, contexts x 32 bytes */
+} hsw_quotient_lookups;
+typedef struct hsw_quotient {
+    uint32_t flags, log_rows, log_n, chunk_columns;   /* flags 0; chunk_columns: L, >= 1 when n_perm_columns > 0 */
+    uint64_t usable_rows;                  /* u, 1 <= u < n */
+    size_t n_proofs, n_columns, n_fixed;   /* K, m, F */
+    const void *const *d_columns;          /* host array, K x m device pointers, N cells each, extended form */
+    const void *const *d_fixed;            /* host array, F device pointers, shared by the proofs; NULL when F == 0 */
+    const void *d_l0, *d_l_last, *d_l_active;   /* device, N cells each, shared; required when a permutation or a lookup is listed */
+    hsw_quotient_gates gates;
+    size_t n_perm_columns;                 /* 0: no permutation argument */
+    const uint32_t *perm_columns;          /* host, column indices < m + F in the permutation's order */
+    const void *const *d_sigmas;           /* host array, n_perm_columns device pointers, N cells, shared */
+    const void *const *d_perm_products;    /* host array, K x S, [c*S + s], N cells */
+    hsw_quotient_lookups lookups;
+    const void *betas, *gammas, *ys;       /* host, K x 32 bytes as stored, below p; betas/gammas needed only with a permutation or a lookup */
+    const void *omega_ext, *zeta, *delta;  /* host, 32 bytes each as stored, below p; delta only with a permutation */
+    void *const *d_h;                      /* host array, K device pointers, N cells each */
+    uint32_t *status;                      /* host, K words, output; may be NULL */
+} hsw_quotient;
+typedef struct hsw_quotient_report {
+    uint64_t proofs, written, refused_proofs, first_refused;   /* written = N x proofs not refused; first_refused ~0 where none */
+    uint64_t expressions, scratch_bytes;   /* y-folds per proof; scratch of a batch */
+    uint32_t launches, rows_per_thread;
+    float kernel_ms, gates_ms, permutation_ms, lookups_ms, finish_ms;
+} hsw_quotient_report;
+int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_quotient_report *report);
 /* AssignedHashResult.input_bytes of digest #hash_idx (the padded variable part). */
 int hsw_gadget_input_bytes(hsw_gadget *g, size_t hash_idx, uint8_t *out, size_t cap, size_t *len);
 /* HSW_REPR_CANONICAL (default) or HSW_REPR_MONTGOMERY for subsequent digests. */
@@ -1512,7 +1610,9 @@ int hsw_fill_calibrate(hsw_engine *e, void *d_buf, size_t bytes, float *ms);
  * table by global atomics (0; a measuring knob).
  * "permuted_scratch": bytes of scratch hsw_gadget_lookup_permuted holds at a time (default 256 MiB, 1 .. 2^32): the
  * multiplicities where the caller passes no d_m (at most half of it, else HSW_ERR_TOO_LARGE) and the index arrays and value
- * tables of a group of arguments; the arguments are processed in groups that fit, a group being at least one proof. */
+ * tables of a group of arguments; the arguments are processed in groups that fit, a group being at least one proof.
+ * "quotient_scratch": bytes of accumulators hsw_gadget_quotient holds at a time (default and maximum 2^30, 1 .. 2^30):
+ * the proofs of a call go in batches that fit, a batch being at least one proof (a test knob). */
 int hsw_engine_set_option(hsw_engine *e, const char *name, int64_t value);
 
 const char *hsw_strerror(int status);

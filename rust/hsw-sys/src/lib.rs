@@ -611,6 +611,99 @@ pub struct hsw_open_report {
     pub reserved2_: f32,
 }
 
+/// Status bit of `hsw_gadget_quotient`: a stored cell that the proof read is not an encoding below p.
+pub const HSW_QUOTIENT_CELL_NOT_BELOW_P: u32 = 4;
+/// The most factors of one monomial of a gate.
+pub const HSW_QUOTIENT_MAX_FACTORS: u32 = 8;
+/// The greatest extension `log_n - log_rows`.
+pub const HSW_QUOTIENT_MAX_EXTENSION: u32 = 8;
+
+/// The gates of `hsw_gadget_quotient` as sums of monomials: all host arrays, copied, not kept.  Gate `g` owns the terms
+/// `gate_first_term[g] .. gate_first_term[g + 1]`, term `t` the factors `term_first_factor[t] .. term_first_factor[t + 1]`
+/// (at most `HSW_QUOTIENT_MAX_FACTORS`); a factor is a column of the shared index space and a rotation in base rows.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_quotient_gates {
+    pub n_gates: usize,
+    pub n_terms: usize,
+    pub n_factors: usize,
+    pub gate_first_term: *const u32,
+    pub term_coeffs: *const c_void,
+    pub term_first_factor: *const u32,
+    pub factor_column: *const u32,
+    pub factor_rotation: *const i32,
+}
+
+/// The lookup arguments of `hsw_gadget_quotient`: per lookup its input and its table columns, folded with theta (the
+/// first listed the highest power), and per (proof, lookup) the device columns A', S' and Z in extended form.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_quotient_lookups {
+    pub n_lookups: usize,
+    pub first_input: *const u32,
+    pub inputs: *const u32,
+    pub first_table: *const u32,
+    pub tables: *const u32,
+    pub d_permuted_inputs: *const *const c_void,
+    pub d_permuted_tables: *const *const c_void,
+    pub d_products: *const *const c_void,
+    pub thetas: *const c_void,
+}
+
+/// Arguments of `hsw_gadget_quotient`: `n_proofs` independent proofs of one circuit, every column `2^log_n` cells in
+/// extended form; `d_h[c]` receives h of proof `c` on the extended coset.  See include/hsw.h for the expressions and
+/// their order.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_quotient {
+    pub flags: u32,
+    pub log_rows: u32,
+    pub log_n: u32,
+    pub chunk_columns: u32,
+    pub usable_rows: u64,
+    pub n_proofs: usize,
+    pub n_columns: usize,
+    pub n_fixed: usize,
+    pub d_columns: *const *const c_void,
+    pub d_fixed: *const *const c_void,
+    pub d_l0: *const c_void,
+    pub d_l_last: *const c_void,
+    pub d_l_active: *const c_void,
+    pub gates: hsw_quotient_gates,
+    pub n_perm_columns: usize,
+    pub perm_columns: *const u32,
+    pub d_sigmas: *const *const c_void,
+    pub d_perm_products: *const *const c_void,
+    pub lookups: hsw_quotient_lookups,
+    pub betas: *const c_void,
+    pub gammas: *const c_void,
+    pub ys: *const c_void,
+    pub omega_ext: *const c_void,
+    pub zeta: *const c_void,
+    pub delta: *const c_void,
+    pub d_h: *const *mut c_void,
+    pub status: *mut u32,
+}
+
+/// Result of `hsw_gadget_quotient`; `first_refused` (a proof) is `u64::MAX` where there is none.
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_quotient_report {
+    pub proofs: u64,
+    pub written: u64,
+    pub refused_proofs: u64,
+    pub first_refused: u64,
+    pub expressions: u64,
+    pub scratch_bytes: u64,
+    pub launches: u32,
+    pub rows_per_thread: u32,
+    pub kernel_ms: f32,
+    pub gates_ms: f32,
+    pub permutation_ms: f32,
+    pub lookups_ms: f32,
+    pub finish_ms: f32,
+}
+
 pub const HSW_CELL_TARGET: i64 = -3000;
 pub const HSW_CELL_STATE0: i64 = -4000;
 
@@ -906,6 +999,8 @@ extern "C" {
     /// The opening quotients of GWC, written on the device: per group the fold with v and the division by `(X - z)`.
     /// Per group `status[g]` carries `HSW_OPEN_CELL_NOT_BELOW_P` (that group is not written).
     pub fn hsw_gadget_open(g: *mut hsw_gadget, args: *const hsw_open, report: *mut hsw_open_report) -> c_int;
+    /// The quotient h(X) of device columns on the extended coset; probe for the symbol (HSW_ABI_MINOR 1).
+    pub fn hsw_gadget_quotient(g: *mut hsw_gadget, args: *const hsw_quotient, report: *mut hsw_quotient_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

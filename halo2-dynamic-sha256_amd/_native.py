@@ -347,6 +347,25 @@ class OpenReport(C.Structure):
                 ("launches", C.c_uint32), ("batches", C.c_uint32), ("reserved_", C.c_uint32), ("kernel_ms", C.c_float), ("reserved2_", C.c_float)]
 
 
+HSW_SHPLONK_CELL_NOT_BELOW_P, HSW_SHPLONK_MAX_SET_POINTS = 4, 16
+
+
+class Shplonk(C.Structure):
+    """hsw_shplonk: rotation sets of device columns, the arguments of both calls of SHPLONK's multi-point opening
+    (hsw_gadget_shplonk_quotient, hsw_gadget_shplonk_open)."""
+    _fields_ = [("flags", C.c_uint32), ("tile_rows", C.c_uint32), ("rows", C.c_uint64), ("n_columns", C.c_size_t),
+                ("d_columns", C.POINTER(C.c_void_p)), ("input_rows", C.POINTER(C.c_uint64)), ("n_points", C.c_size_t), ("points", C.c_void_p),
+                ("n_sets", C.c_size_t), ("set_first", C.POINTER(C.c_uint64)), ("set_columns", C.POINTER(C.c_uint32)),
+                ("set_point_first", C.POINTER(C.c_uint64)), ("set_points", C.POINTER(C.c_uint32)), ("y", C.c_void_p), ("v", C.c_void_p),
+                ("u", C.c_void_p), ("d_h", C.c_void_p), ("d_out", C.c_void_p), ("status", C.POINTER(C.c_uint32))]
+
+
+class ShplonkReport(C.Structure):
+    _fields_ = [("sets", C.c_uint64), ("items", C.c_uint64), ("columns", C.c_uint64), ("written", C.c_uint64), ("refused", C.c_uint64),
+                ("scratch_bytes", C.c_uint64), ("tile_rows", C.c_uint32), ("tiles", C.c_uint32), ("thread_rows", C.c_uint32),
+                ("launches", C.c_uint32), ("kernel_ms", C.c_float), ("reserved_", C.c_uint32)]
+
+
 HSW_QUOTIENT_CELL_NOT_BELOW_P, HSW_QUOTIENT_MAX_FACTORS, HSW_QUOTIENT_MAX_EXTENSION = 4, 8, 8
 
 
@@ -406,6 +425,7 @@ SYMBOLS = (
     "hsw_gadget_lookup_runs", "hsw_gadget_lookup_multiplicities", "hsw_gadget_lookup_permuted",
     "hsw_gadget_lookup_product", "hsw_gadget_permutation_product", "hsw_gadget_ntt",
     "hsw_gadget_msm", "hsw_gadget_evaluate", "hsw_gadget_open", "hsw_gadget_quotient",
+    "hsw_gadget_shplonk_quotient", "hsw_gadget_shplonk_open",
 )
 
 
@@ -525,6 +545,11 @@ def lib():
         if hasattr(L, "hsw_gadget_quotient"):   # likewise
             L.hsw_gadget_quotient.restype = C.c_int
             L.hsw_gadget_quotient.argtypes = [vp, C.POINTER(Quotient), C.POINTER(QuotientReport)]
+        if hasattr(L, "hsw_gadget_shplonk_quotient"):   # likewise
+            L.hsw_gadget_shplonk_quotient.restype = C.c_int
+            L.hsw_gadget_shplonk_quotient.argtypes = [vp, C.POINTER(Shplonk), C.POINTER(ShplonkReport)]
+            L.hsw_gadget_shplonk_open.restype = C.c_int
+            L.hsw_gadget_shplonk_open.argtypes = [vp, C.POINTER(Shplonk), C.POINTER(ShplonkReport)]
         L.hsw_gadget_streams.restype = C.c_int
         L.hsw_gadget_streams.argtypes = [vp, C.POINTER(GadgetView)]
         L.hsw_gadget_input_bytes.restype = C.c_int

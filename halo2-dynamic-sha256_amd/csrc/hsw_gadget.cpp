@@ -89,7 +89,7 @@ int hsw_gadget_create_contexts(hsw_engine *e, const size_t *max_variable_byte_si
 
 void hsw_gadget_destroy(hsw_gadget *g) {
     if (!g) return;
-    if (g->d_pairs || g->d_lookup_runs || g->d_permuted || g->d_product || g->d_permutation || g->d_ntt || g->ntt_stamp || g->d_msm || g->d_open || g->d_quotient) {   // (every check and count that used them was synchronous)
+    if (g->d_pairs || g->d_lookup_runs || g->d_permuted || g->d_product || g->d_permutation || g->d_ntt || g->ntt_stamp || g->d_msm || g->d_open || g->d_quotient || g->d_shplonk) {   // (every check and count that used them was synchronous)
         EngineScope es(g->ctx->engine);
         (void)hipFree(g->d_pairs);
         (void)hipFree(g->d_lookup_runs);
@@ -101,6 +101,7 @@ void hsw_gadget_destroy(hsw_gadget *g) {
         (void)hipFree(g->d_msm);
         (void)hipFree(g->d_open);
         (void)hipFree(g->d_quotient);
+        (void)hipFree(g->d_shplonk);
     }
     delete g->ctx;
     delete g;

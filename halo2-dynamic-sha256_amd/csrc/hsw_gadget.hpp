@@ -398,6 +398,8 @@ struct hsw_gadget {
     size_t open_cap = 0;                            // staged powers and the scratch of a batch, in bytes; grown and freed like d_pairs
     void *d_quotient = nullptr;                     // hsw_gadget_quotient (hsw_gadget_quotient.cpp): status words, descriptor tables, staged constants
     size_t quotient_cap = 0;                        // and the accumulators V of a batch, in bytes; grown and freed like d_pairs
+    void *d_shplonk = nullptr;                      // hsw_gadget_shplonk_quotient / _open (hsw_gadget_shplonk.cpp): the status word, descriptors,
+    size_t shplonk_cap = 0;                         // staged powers and weights and the scratch of the call, in bytes; grown and freed like d_pairs
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

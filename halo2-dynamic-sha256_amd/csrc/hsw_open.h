@@ -1,5 +1,5 @@
 // hsw_open.h -- launch interface of the evaluation and the opening of device columns (hsw_open.hip; hsw_gadget_evaluate
-// and hsw_gadget_open in hsw_gadget_open.cpp are its only callers).
+// and hsw_gadget_open in hsw_gadget_open.cpp are its callers; hsw_gadget_shplonk.cpp takes launch_open_scan as it is).
 #ifndef HSW_OPEN_H
 #define HSW_OPEN_H
 

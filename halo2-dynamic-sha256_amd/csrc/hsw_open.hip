@@ -14,9 +14,11 @@
 //           a workgroup scan with z^(tile_rows chunk 2^k); every tile's sum becomes its carry-in, thread 0 leaves c(z).
 //   write   (open) tiles again: seed = E_t + z^(8 (active - 1 - t)) carry, then q[j] = s[j+1], s[j] = c[j] + z s[j+1]
 //           down the thread's rows, two 16-byte stores per cell, one multiply per row.  A refused group stores nothing.
-// Field elements travel through LDS limb-major (sh[limb][thread]): 4-byte accesses at stride 1, no bank conflict.
+// Field elements travel through LDS limb-major (sh[limb][thread]): 4-byte accesses at stride 1, no bank conflict
+// (hsw_open_device.hpp: the cell, LDS and scan helpers, shared with hsw_shplonk.hip).
 // Vector loads, vector stores and vector atomics only.
 #include "hsw_open.h"
+#include "hsw_open_device.hpp"
 
 namespace hsw {
 
@@ -24,60 +26,11 @@ typedef unsigned int u32;
 
 namespace {
 
-__device__ __forceinline__ PFe load_cell(const uint4 *col, size_t i) {
-    const uint4 a = col[2 * i], b = col[2 * i + 1];
-    return PFe{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-}
-__device__ __forceinline__ void store_cell(uint4 *col, size_t i, const PFe &v) {
-    col[2 * i] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    col[2 * i + 1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
-__device__ __forceinline__ void lds_put(u32 *sh, u32 t, const PFe &v) {
-    for (int j = 0; j < 8; j++) sh[j * OPEN_THREADS + t] = v.l[j];
-}
-__device__ __forceinline__ PFe lds_get(const u32 *sh, u32 t) {
-    PFe v;
-    for (int j = 0; j < 8; j++) v.l[j] = sh[j * OPEN_THREADS + t];
-    return v;
-}
-
-// a thread's rows of a column, 0 at and beyond col_rows; false if a stored cell that was read is not below p
-__device__ __forceinline__ bool load_rows(const uint4 *cells, u32 col_rows, u32 row0, PFe *a) {
-    bool ok = true;
-#pragma unroll
-    for (u32 k = 0; k < OPEN_ROWS; k++) {
-        a[k] = fr_zero();
-        if (row0 + k < col_rows) { a[k] = load_cell(cells, row0 + k); ok = ok && pfe_below_p(a[k]); }
-    }
-    return ok;
-}
-
 // q[row] = s[row+1], then s[row] = c[row] + z s[row+1]; rows at and beyond `rows` are no rows (there s is 0)
 __device__ __forceinline__ void write_row(uint4 *q, u32 rows, u32 row, const PFe &c, const PFe &z, PFe &s) {
     if (row >= rows) return;
     store_cell(q, row, s);
     s = open_step(c, z, s);
-}
-
-// The inclusive suffix scan over the first `active` threads: sh[t] = x[t] + M x[t+1] + M^2 x[t+2] + ..., with the step
-// multipliers M^(2^k) = pow[k] (LOG) or pow[2^k].  Hillis-Steele, a multiply per step.  Ends synchronised
-template <bool LOG>
-__device__ __forceinline__ void suffix_scan(u32 *sh, const PFe *pow, u32 active, PFe x) {
-    const u32 t = threadIdx.x;
-    lds_put(sh, t, x);
-    __syncthreads();
-    u32 k = 0;
-    for (u32 s = 1; s < active; s <<= 1, k++) {
-        const bool on = t + s < active;
-        PFe o = fr_zero();
-        if (on) o = lds_get(sh, t + s);
-        __syncthreads();
-        if (on) {
-            x = open_step(x, pow[LOG ? k : s], o);
-            lds_put(sh, t, x);
-        }
-        __syncthreads();
-    }
 }
 
 }  // namespace

@@ -1041,6 +1041,94 @@ class Sha256DynamicConfig:
         return (out if isinstance(out, torch.Tensor) else None, evals, status,
                 {f[0]: getattr(rep, f[0]) for f in N.OpenReport._fields_ if not f[0].startswith("reserved")})
 
+    def _shplonk(self, which, rows, columns, sets, points, y, v, u, h, out, input_rows, tile_rows):
+        """What shplonk_quotient and shplonk_open share: the argument rules, the call, (out, status, report)."""
+        import numpy as np
+        import torch
+        dev = self.engine.device
+        rows, tile_rows, n, heights, ptrs = self._open_columns(rows, columns, input_rows, tile_rows)
+        if isinstance(points, (np.ndarray, torch.Tensor)):
+            size = int(np.prod(points.shape))
+            n_points = size // 4 if size % 4 == 0 else 0
+        else:
+            n_points = 1 if isinstance(points, int) else len(points)
+        if n_points < 1:
+            raise ValueError("points: at least one field element of 4 x uint64")
+        z_buf = self._field_elements("points", points, n_points)
+        if len({row.tobytes() for row in z_buf}) != n_points:
+            raise ValueError("points: the entries must differ in value")
+        ss = [([int(b) for b in cols], [int(t) for t in pts]) for cols, pts in sets]
+        if not ss or len(ss) > 65535:
+            raise ValueError("sets: 1 .. 65535 pairs of (column indices, point indices)")
+        if any(not cols or any(b < 0 or b >= n for b in cols) for cols, _ in ss):
+            raise ValueError("sets: each lists at least one column index below %d" % n)
+        listed = [b for cols, _ in ss for b in cols]
+        if len(set(listed)) != len(listed):
+            raise ValueError("sets: a column is listed once in the whole call")
+        if any(not pts or len(pts) > N.HSW_SHPLONK_MAX_SET_POINTS or any(t < 0 or t >= n_points for t in pts) or len(set(pts)) != len(pts) for _, pts in ss):
+            raise ValueError("sets: each lists 1 .. %d distinct point indices below %d" % (N.HSW_SHPLONK_MAX_SET_POINTS, n_points))
+        if {t for _, pts in ss for t in pts} != set(range(n_points)):
+            raise ValueError("points: every entry must be used by a set")
+        y_buf, v_buf = self._field_elements("y", y, 1), self._field_elements("v", v, 1)
+        u_buf = self._field_elements("u", u, 1) if which == "open" else None
+        h_ptr = None
+        if which == "open":
+            if isinstance(h, torch.Tensor):
+                if h.dtype != torch.uint64 or h.device != dev or h.dim() != 2 or h.shape[0] < rows or h.shape[1] != 4 or not h.is_contiguous():
+                    raise ValueError("h must be a contiguous uint64 tensor on %s of shape (rows >= %d, 4)" % (dev, rows))
+                h_ptr = h.data_ptr()
+            else:
+                h_ptr = int(h) if h is not None else 0
+                if h_ptr == 0 or h_ptr % 16:
+                    raise ValueError("h: a tensor or a device address, 16-byte aligned")
+        if out is None:
+            out = torch.zeros((rows, 4), dtype=torch.uint64, device=dev)
+        if isinstance(out, torch.Tensor):
+            if out.dtype != torch.uint64 or out.device != dev or out.dim() != 2 or out.shape[0] < rows or out.shape[1] != 4 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous uint64 tensor on %s of shape (rows >= %d, 4)" % (dev, rows))
+            out_ptr = out.data_ptr()
+        else:
+            out_ptr = int(out)
+            if out_ptr == 0 or out_ptr % 16:
+                raise ValueError("out: a tensor or a device address, 16-byte aligned")
+        first, pfirst = [0], [0]
+        for cols, pts in ss:
+            first.append(first[-1] + len(cols))
+            pfirst.append(pfirst[-1] + len(pts))
+        flat_p = [t for _, pts in ss for t in pts]
+        ns = len(ss)
+        status = np.zeros(1, dtype=np.uint32)
+        args = N.Shplonk(0, tile_rows, rows, n, (C.c_void_p * n)(*ptrs), (C.c_uint64 * n)(*heights), n_points, z_buf.ctypes.data, ns,
+                         (C.c_uint64 * (ns + 1))(*first), (C.c_uint32 * len(listed))(*listed), (C.c_uint64 * (ns + 1))(*pfirst),
+                         (C.c_uint32 * len(flat_p))(*flat_p), y_buf.ctypes.data, v_buf.ctypes.data, u_buf.ctypes.data if u_buf is not None else None,
+                         h_ptr, out_ptr, status.ctypes.data_as(C.POINTER(C.c_uint32)))
+        rep = N.ShplonkReport()
+        torch.cuda.synchronize(dev)                        # the tensors were made on torch's stream, the call runs on the engine's
+        fn = self.lib.hsw_gadget_shplonk_open if which == "open" else self.lib.hsw_gadget_shplonk_quotient
+        self._ok(fn(self.h, C.byref(args), C.byref(rep)))
+        return (out if isinstance(out, torch.Tensor) else None, int(status[0]),
+                {f[0]: getattr(rep, f[0]) for f in N.ShplonkReport._fields_ if not f[0].startswith("reserved")})
+
+    def shplonk_quotient(self, rows, columns, sets, points, y, v, out=None, input_rows=None, tile_rows=0):
+        """hsw_gadget_shplonk_quotient: the first polynomial of SHPLONK's multi-point opening.  sets: a sequence of
+        (column indices, point indices) pairs, the rotation sets; set i folds its columns as c_i = sum_k y^k a_{b_{i,k}}
+        (the first listed column gets y^0), divides by Z_i(X) = prod (X - points[t]) over its point indices, and
+        h = sum_i v^i floor(c_i / Z_i) (the first set gets v^0).  Returns (h, status, report): a uint64 device tensor
+        (rows, 4) that msm commits as it lies, the status word (HSW_SHPLONK_CELL_NOT_BELOW_P: a stored cell that was
+        read is not below p, and h was not written) and the report as a dict.  columns, input_rows, tile_rows: as
+        evaluate takes them; a column is listed once in the whole call.  points: the distinct field elements of the
+        super point set as stored, each used by a set; y, v: field elements as stored.  out: the caller's own
+        contiguous uint64 tensor (rows' >= rows, 4), or a device address (then None is returned in its place)."""
+        return self._shplonk("quotient", rows, columns, sets, points, y, v, None, None, out, input_rows, tile_rows)
+
+    def shplonk_open(self, rows, columns, sets, points, y, v, u, h, out=None, input_rows=None, tile_rows=0):
+        """hsw_gadget_shplonk_open: the second polynomial, after h was committed and u squeezed.  With zd_i = prod (u -
+        z) over the points NOT in set i, zt the product over all points: L = sum_i v^i zd_i c_i - zt h and w[j] =
+        zd_0^-1 sum_{l>j} L[l] u^(l-j-1), so that (X - u) w(X) = (L(X) - L(u)) / zd_0.  h: what shplonk_quotient
+        returned for the same arguments (a (rows, 4) tensor or a device address).  Returns (w, status, report) as
+        shplonk_quotient does."""
+        return self._shplonk("open", rows, columns, sets, points, y, v, u, h, out, input_rows, tile_rows)
+
     def quotient(self, log_rows, log_n, usable_rows, columns, ys, omega_ext, zeta, fixed=None, gates=(), l0=None, l_last=None,
                  l_active=None, perm_columns=(), chunk_columns=0, sigmas=None, perm_products=None, delta=None, betas=None, gammas=None,
                  lookups=(), permuted_inputs=None, permuted_tables=None, lookup_products=None, thetas=None, out=None):

@@ -1431,8 +1431,9 @@ int hsw_gadget_msm(hsw_gadget *g, const hsw_msm *args, hsw_msm_report *report);
  * output bytes do not depend on it, the report says what was used.  The folded column (groups of two columns or more),
  * a cell per thread and a cell per tile live in the gadget's scratch: groups (columns of evaluate) go in batches that
  * hold at most 1 GiB of it, a batch being at least one group, three (two) launches per batch; grown on demand and
- * freed by hsw_gadget_destroy.  The host reads nothing between the launches of a call.  SHPLONK's multi-point quotient,
- * the transcript, the blinding terms and h(X) stay the prover's.  Synchronous, on the engine's stream.  (The calls came
+ * freed by hsw_gadget_destroy.  The host reads nothing between the launches of a call.  SHPLONK's multi-point opening
+ * is hsw_gadget_shplonk_quotient / _open and h(X) is hsw_gadget_quotient (both below); the transcript and the blinding
+ * terms stay the prover's.  Synchronous, on the engine's stream.  (The calls came
  * under HSW_ABI_MINOR 1: probe for the symbols.) */
 #define HSW_OPEN_CELL_NOT_BELOW_P 4u   /* status bit, the value of HSW_NTT_CELL_NOT_BELOW_P */
 #define HSW_OPEN_MIN_TILE_ROWS 256u
@@ -1481,6 +1482,92 @@ typedef struct hsw_open_report {
     float kernel_ms, reserved2_;
 } hsw_open_report;
 int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_report *report);
+/* ---- SHPLONK's multi-point opening of device columns: the two polynomials of ProverSHPLONK ----
+ * What halo2's ProverSHPLONK does after the evaluations with every polynomial in coefficient form: h(X), the y-fold of
+ * every rotation set divided by the set's vanishing polynomial and folded with v, and -- after the prover has committed
+ * h and squeezed u -- the linearisation L(X) divided by (X - u).  Both outputs are committed with hsw_gadget_msm (n_bases
+ * = rows) as they lie: two G1 points however many rotations the circuit queries.  Every value mod p; column b holds
+ * a_b[j] in cell j for j < input_rows[b] and 0 from there to `rows`; rows is 1 .. 2^28 and need not be a power of two.
+ * T = points[0 .. n_points), the super point set: distinct field elements.  Rotation set i lists its columns b_{i,0 ..
+ * m_i-1} = set_columns[set_first[i] .. set_first[i+1]) and its points S_i = { points[k] : k in
+ * set_points[set_point_first[i] .. set_point_first[i+1]) }, t_i = |S_i| of them, z_{i,0 .. t_i-1} in the listed order.
+ *   hsw_gadget_shplonk_quotient (y, v; u and d_h NULL), d_out = h:
+ *       c_i[j] = sum_{k<m_i} y^k * a_{b_{i,k}}[j]           the FIRST listed column gets y^0
+ *       Q_i(X) = floor( c_i(X) / Z_i(X) ),  Z_i(X) = prod_{z in S_i} (X - z)
+ *       h[j]   = sum_i v^i * Q_i[j]                          0 <= j < rows; the first set gets v^0
+ *   hsw_gadget_shplonk_open (y, v, u, d_h = the h of the first call), d_out = w:
+ *       zd_i = prod_{z in T \ S_i} (u - z),   zt = prod_{z in T} (u - z)
+ *       L[j] = sum_i v^i * zd_i * c_i[j]  -  zt * h[j]
+ *       w[j] = zd_0^-1 * sum_{j<l<rows} L[l] * u^(l-j-1)     hence w[rows-1] = 0
+ * No evaluation is needed in either call.  floor(c_i / Z_i) is what halo2 gets by first subtracting the interpolant R_i
+ * of c_i over S_i: c_i = Z_i Q_i + R_i with deg R_i < t_i, and R_i agrees with c_i on S_i.  In the second call the terms
+ * r_i = R_i(u) change L[0] alone, which w never reads (as in hsw_gadget_open): (X - u) w(X) = (L(X) - L(u)) / zd_0.  The
+ * division by Z_i is done by partial fractions, lambda_{i,k} = 1 / prod_{l != k} (z_{i,k} - z_{i,l}):
+ *       Q_i[j] = sum_k lambda_{i,k} * q_{i,k}[j],   q_{i,k}[j] = sum_{l>j} c_i[l] * z_{i,k}^(l-j-1)
+ * the suffix Horner sums of hsw_gadget_open per (set, point); the top min(t_i, rows) cells of Q_i come out exactly 0.
+ * The power orders (y^k in listed order within a set, v^i over sets in listed order) and the normalisation by zd_0^-1
+ * are assumption A10: written from memory of halo2_proofs' shplonk prover, not pinned against its
+ * source.  A fork that orders differently lists its columns or its sets in its order.
+ * d_columns, input_rows: as hsw_gadget_open takes them; rows of a column at and beyond input_rows[b] are NOT READ, and a
+ * column that no set lists is not read at all.  points, y, v, u: HOST memory, 32 bytes each as stored in the
+ * representation of the pass, below p.  d_h: device, `rows` cells, all read.  d_out: device, receives exactly `rows`
+ * cells.  Nothing in device memory but the gadget's scratch and d_out is written.  Cells are in the representation of
+ * the pass; every constant is held in Montgomery form, so canonical and Montgomery cells take the same kernels and the
+ * output is exact bit for bit in both.
+ * Decided on the device (status: ONE host word; may be NULL):
+ *   HSW_SHPLONK_CELL_NOT_BELOW_P  a stored cell that was read -- of a listed column, or of d_h -- is not an encoding
+ *                                 below p: the call is REFUSED, not one byte of d_out is written.
+ * The call still returns HSW_OK, and the report says refused = 1.
+ * Refused before any launch -- HSW_ERR_INVALID_ARG (hsw_last_error names the culprit): rows 0 or above 2^28; zero
+ * columns, points or sets; a set with no column or no point, or with more than HSW_SHPLONK_MAX_SET_POINTS points; more
+ * than 65,535 sets; an index out of range; a column listed twice, in one set or in two; a point index twice in a set; two
+ * entries of `points` equal in value; a point of T that no set uses; a pointer that is NULL or a device pointer not
+ * 16-byte aligned; input_rows[b] > rows; a point or challenge not below p; unknown flags; a tile_rows outside its range;
+ * d_out overlapping the `rows` cells of any column (read or not) or of d_h; quotient: u or d_h not NULL; open: u or d_h
+ * NULL, or zd_0 = 0 (u is a point of T outside S_0).  HSW_ERR_UNSUPPORTED: HSW_REPR_COMPACT64 cells, a pass whose batches
+ * differ in representation.
+ * Three launches per call: tiles (a workgroup per (set, tile): the fold with one staged weight per column, the check,
+ * and per point of the set Horner and the workgroup scan), scan (hsw_gadget_open's, a workgroup per (set, point)),
+ * write (a workgroup per tile: per (set, point) the recurrence down a thread's rows, the sum with the weights W_{i,k} =
+ * v^i lambda_{i,k}, ONE store per output cell).  The second call is the same three launches over one set that holds
+ * every listed column and h, with the weights v^i zd_i y^k / zd_0 and -zt / zd_0, the one point u and W = 1.  tile_rows:
+ * as hsw_gadget_open's.  The scratch -- the staged points, weights and descriptors, c_i for every set of two columns or
+ * more (rows cells), ceil(rows / 8) + tiles cells per (set, point), one status word -- lives in the gadget, is grown on
+ * demand and freed by hsw_gadget_destroy.  It is NOT cut into batches: the write launch needs every set's c_i at once
+ * (HSW_ERR_NOMEM if the device cannot hold it); report.scratch_bytes says how much.  The host reads nothing between
+ * the launches.  One call is one proof's opening: K proofs are K calls.  The transcript, the blinding terms and the
+ * evaluations written to the transcript (hsw_gadget_evaluate) stay the prover's.  Synchronous, on the engine's stream.
+ * (The calls came under HSW_ABI_MINOR 1: probe for the symbols.) */
+#define HSW_SHPLONK_CELL_NOT_BELOW_P 4u   /* status bit, the value of HSW_NTT_CELL_NOT_BELOW_P */
+#define HSW_SHPLONK_MAX_SET_POINTS 16u    /* points of one rotation set */
+typedef struct hsw_shplonk {
+    uint32_t flags, tile_rows;             /* flags: 0; tile_rows: 0 or a power of two, HSW_OPEN_MIN_TILE_ROWS .. 2^20 */
+    uint64_t rows;                         /* 1 .. 2^28 */
+    size_t n_columns;
+    const void *const *d_columns;          /* host array, n_columns device pointers */
+    const uint64_t *input_rows;            /* host, per column, 0 .. rows; NULL = rows everywhere */
+    size_t n_points;
+    const void *points;                    /* host, n_points x 32 bytes as stored, below p, distinct: T */
+    size_t n_sets;                         /* 1 .. 65,535 */
+    const uint64_t *set_first;             /* host, n_sets + 1 offsets into set_columns, increasing from 0 */
+    const uint32_t *set_columns;           /* host, set_first[n_sets] indices below n_columns, each at most once */
+    const uint64_t *set_point_first;       /* host, n_sets + 1 offsets into set_points, increasing from 0 */
+    const uint32_t *set_points;            /* host, set_point_first[n_sets] indices below n_points */
+    const void *y, *v, *u;                 /* host, 32 bytes each as stored, below p; u: open only, NULL for quotient */
+    const void *d_h;                       /* device, rows cells: open only, NULL for quotient */
+    void *d_out;                           /* device, rows cells: h (quotient) or w (open) */
+    uint32_t *status;                      /* host, one word, output; may be NULL */
+} hsw_shplonk;
+typedef struct hsw_shplonk_report {
+    uint64_t sets, items, columns;         /* items: the (set, point) pairs; columns: the listed ones (open: and h) */
+    uint64_t written, refused;             /* written = rows, or 0 when refused (1) */
+    uint64_t scratch_bytes;                /* all of it: one call is one batch */
+    uint32_t tile_rows, tiles, thread_rows, launches;   /* what was used; launches: three */
+    float kernel_ms;
+    uint32_t reserved_;
+} hsw_shplonk_report;
+int hsw_gadget_shplonk_quotient(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *report);
+int hsw_gadget_shplonk_open(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *report);
 /* ---- the quotient h(X) of device columns on the extended coset ----
  * What halo2's evaluate_h and vanishing argument do between the last grand product and the commitments of h: the
  * numerator -- every gate, permutation and lookup expression folded with y -- divided by the vanishing polynomial, row

@@ -611,6 +611,58 @@ pub struct hsw_open_report {
     pub reserved2_: f32,
 }
 
+/// Status bit of `hsw_gadget_shplonk_quotient` / `_open`: a stored cell that was read is not an encoding below p.
+pub const HSW_SHPLONK_CELL_NOT_BELOW_P: u32 = 4;
+/// The most points of one rotation set.
+pub const HSW_SHPLONK_MAX_SET_POINTS: u32 = 16;
+
+/// Arguments of both calls of SHPLONK's multi-point opening: rotation set `i` lists the columns
+/// `set_columns[set_first[i] .. set_first[i + 1])` (folded with `y`, the first gets `y^0`) and the points
+/// `set_points[set_point_first[i] .. set_point_first[i + 1])` of `points`; the sets fold with `v` (the first gets `v^0`).
+/// `u` and `d_h` are NULL for `hsw_gadget_shplonk_quotient` and required for `hsw_gadget_shplonk_open`; `d_out` receives
+/// `rows` cells.
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct hsw_shplonk {
+    pub flags: u32,
+    pub tile_rows: u32,
+    pub rows: u64,
+    pub n_columns: usize,
+    pub d_columns: *const *const c_void,
+    pub input_rows: *const u64,
+    pub n_points: usize,
+    pub points: *const c_void,
+    pub n_sets: usize,
+    pub set_first: *const u64,
+    pub set_columns: *const u32,
+    pub set_point_first: *const u64,
+    pub set_points: *const u32,
+    pub y: *const c_void,
+    pub v: *const c_void,
+    pub u: *const c_void,
+    pub d_h: *const c_void,
+    pub d_out: *mut c_void,
+    pub status: *mut u32,
+}
+
+/// Result of `hsw_gadget_shplonk_quotient` / `_open`; `refused` is 1 when the status bit is set (then `written` is 0).
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct hsw_shplonk_report {
+    pub sets: u64,
+    pub items: u64,
+    pub columns: u64,
+    pub written: u64,
+    pub refused: u64,
+    pub scratch_bytes: u64,
+    pub tile_rows: u32,
+    pub tiles: u32,
+    pub thread_rows: u32,
+    pub launches: u32,
+    pub kernel_ms: f32,
+    pub reserved_: u32,
+}
+
 /// Status bit of `hsw_gadget_quotient`: a stored cell that the proof read is not an encoding below p.
 pub const HSW_QUOTIENT_CELL_NOT_BELOW_P: u32 = 4;
 /// The most factors of one monomial of a gate.
@@ -1001,6 +1053,11 @@ extern "C" {
     pub fn hsw_gadget_open(g: *mut hsw_gadget, args: *const hsw_open, report: *mut hsw_open_report) -> c_int;
     /// The quotient h(X) of device columns on the extended coset; probe for the symbol (HSW_ABI_MINOR 1).
     pub fn hsw_gadget_quotient(g: *mut hsw_gadget, args: *const hsw_quotient, report: *mut hsw_quotient_report) -> c_int;
+    /// SHPLONK's first polynomial `h = sum_i v^i floor(c_i / Z_i)` over rotation sets of device columns, written on the
+    /// device; `*status` carries `HSW_SHPLONK_CELL_NOT_BELOW_P` (nothing is written).  Probe for the symbol (HSW_ABI_MINOR 1).
+    pub fn hsw_gadget_shplonk_quotient(g: *mut hsw_gadget, args: *const hsw_shplonk, report: *mut hsw_shplonk_report) -> c_int;
+    /// SHPLONK's second polynomial `w = (L(X) - L(u)) / ((X - u) zd_0)` from the same sets, `h` and `u`; likewise.
+    pub fn hsw_gadget_shplonk_open(g: *mut hsw_gadget, args: *const hsw_shplonk, report: *mut hsw_shplonk_report) -> c_int;
     pub fn hsw_gadget_streams(g: *mut hsw_gadget, view: *mut hsw_gadget_view) -> c_int;
     pub fn hsw_gadget_input_bytes(g: *mut hsw_gadget, hash_idx: usize, out: *mut u8, cap: usize,
                                   len: *mut usize) -> c_int;

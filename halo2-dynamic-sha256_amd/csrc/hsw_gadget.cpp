@@ -89,19 +89,12 @@ int hsw_gadget_create_contexts(hsw_engine *e, const size_t *max_variable_byte_si
 
 void hsw_gadget_destroy(hsw_gadget *g) {
     if (!g) return;
-    if (g->d_pairs || g->d_lookup_runs || g->d_permuted || g->d_product || g->d_permutation || g->d_ntt || g->ntt_stamp || g->d_msm || g->d_open || g->d_quotient || g->d_shplonk) {   // (every check and count that used them was synchronous)
+    if (g->scratch.d || g->d_pairs || g->d_lookup_runs || g->ntt_stamp) {   // (every call that used them was synchronous)
         EngineScope es(g->ctx->engine);
+        (void)hipFree(g->scratch.d);
         (void)hipFree(g->d_pairs);
         (void)hipFree(g->d_lookup_runs);
-        (void)hipFree(g->d_permuted);
-        (void)hipFree(g->d_product);
-        (void)hipFree(g->d_permutation);
-        (void)hipFree(g->d_ntt);
         for (hsw_gadget::NttTable &t : g->ntt_tables) (void)hipFree(t.d_table);
-        (void)hipFree(g->d_msm);
-        (void)hipFree(g->d_open);
-        (void)hipFree(g->d_quotient);
-        (void)hipFree(g->d_shplonk);
     }
     delete g->ctx;
     delete g;

@@ -20,7 +20,12 @@
 // Implemented in several translation units: hsw_gadget_sha.cpp (padding, host SHA, digest_plan / digest_prepare: no HIP
 // call), hsw_gadget_context.cpp (Context: buffers, layouts, bind / unbind, the jump table), hsw_gadget_digest.cpp (the
 // digest paths and the ties), hsw_gadget_lookup.cpp (the lookup entries of a pass, listed and counted),
-// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z), hsw_gadget_permutation.cpp (the permutation argument's grand products), hsw_gadget_ntt.cpp (the Fr NTT of device columns), hsw_gadget_msm.cpp (their commitments: the G1 MSM), hsw_gadget_open.cpp (their evaluations and opening quotients), hsw_gadget_quotient.cpp (the quotient h(X) on the extended coset) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share.
+// hsw_gadget_permuted.cpp (the permuted lookup columns of a pass), hsw_gadget_product.cpp (their grand product Z),
+// hsw_gadget_permutation.cpp (the permutation argument's grand products), hsw_gadget_ntt.cpp (the Fr NTT of device
+// columns), hsw_gadget_msm.cpp (their commitments: the G1 MSM), hsw_gadget_open.cpp (their evaluations and opening
+// quotients), hsw_gadget_shplonk.cpp (SHPLONK's multi-point opening), hsw_gadget_quotient.cpp (the quotient h(X) on the
+// extended coset) and hsw_gadget.cpp (the rest of the C ABI); hsw_gadget_launch.hpp is what only they share, and
+// hsw_gadget_call.hpp what the calls of the round from hsw_gadget_permuted.cpp on share beyond it.
 #ifndef HSW_GADGET_HPP
 #define HSW_GADGET_HPP
 
@@ -73,6 +78,14 @@ struct AssignedHashResult {
 };
 
 class Context;
+
+// a block of device memory that is replaced by a larger one on demand: the members are in hsw_gadget_call.hpp
+struct DeviceScratch {
+    void *d = nullptr;
+    size_t cap = 0;                  // bytes
+    int reserve(size_t bytes);
+    void release();
+};
 
 // base + cells * cell_bytes, the offset taken modulo 2^64 as the kernels take it: a column given by pointer table may
 // lie below entry 0 of its table
@@ -379,27 +392,14 @@ struct hsw_gadget {
     size_t pairs_cap = 0;                           // grown on demand, freed by hsw_gadget_destroy
     void *d_lookup_runs = nullptr;                  // hsw_gadget_lookup_multiplicities (hsw_gadget_lookup.cpp): its report, run
     size_t lookup_runs_cap = 0;                     // table and zero lists on the device, in bytes; grown and freed like d_pairs
-    void *d_permuted = nullptr;                     // hsw_gadget_lookup_permuted (hsw_gadget_permuted.cpp): its report, staging, index
-    size_t permuted_cap = 0;                        // and value arrays on the device, in bytes; grown and freed like d_pairs
-    void *d_product = nullptr;                      // hsw_gadget_lookup_product (hsw_gadget_product.cpp): status words, arguments,
-    size_t product_cap = 0;                         // challenges and tile products on the device, in bytes; grown and freed like d_pairs
-    void *d_permutation = nullptr;                  // hsw_gadget_permutation_product (hsw_gadget_permutation.cpp): status words, columns,
-    size_t permutation_cap = 0;                     // staged constants and tile products on the device, in bytes; grown and freed like d_pairs
-    void *d_ntt = nullptr;                          // hsw_gadget_ntt (hsw_gadget_ntt.cpp): status words, columns, staged constants and
-    size_t ntt_cap = 0;                             // the points between launches, in bytes; grown and freed like d_pairs
+    // what the calls of the round from hsw_gadget_lookup_permuted to hsw_gadget_quotient stage and work in, one after the
+    // other: each reserves what it needs, stages all it reads and leaves nothing a later call reads (hsw_gadget_call.hpp)
+    hsw::DeviceScratch scratch;
     // the tables of the powers of the roots hsw_gadget_ntt was last called with: root in Montgomery form, log_n, the
     // device table (2^(log_n - 1) cells); stamp orders them by last use (0: free).  Freed by hsw_gadget_destroy
     struct NttTable { uint32_t root[8]; uint32_t log_n; void *d_table; size_t bytes; uint64_t stamp; };
     NttTable ntt_tables[4] = {};
     uint64_t ntt_stamp = 0;
-    void *d_msm = nullptr;                          // hsw_gadget_msm (hsw_gadget_msm.cpp): status words, the bases' check, columns, window points and
-    size_t msm_cap = 0;                             // the partial buckets of a group of columns, in bytes; grown and freed like d_pairs
-    void *d_open = nullptr;                         // hsw_gadget_evaluate / _open (hsw_gadget_open.cpp): status words, evaluations, columns, groups,
-    size_t open_cap = 0;                            // staged powers and the scratch of a batch, in bytes; grown and freed like d_pairs
-    void *d_quotient = nullptr;                     // hsw_gadget_quotient (hsw_gadget_quotient.cpp): status words, descriptor tables, staged constants
-    size_t quotient_cap = 0;                        // and the accumulators V of a batch, in bytes; grown and freed like d_pairs
-    void *d_shplonk = nullptr;                      // hsw_gadget_shplonk_quotient / _open (hsw_gadget_shplonk.cpp): the status word, descriptors,
-    size_t shplonk_cap = 0;                         // staged powers and weights and the scratch of the call, in bytes; grown and freed like d_pairs
     ~hsw_gadget() { hsw::free_region_tape(tape); }
 };
 #endif

@@ -1,6 +1,7 @@
 // hsw_gadget_launch.hpp -- what the translation units of the gadget share beyond hsw_gadget.hpp (which tests include
-// too): the engine behind the handle, and the launch builder of the digest paths (hsw_gadget_digest.cpp) and of
-// hsw_gadget_verify (hsw_gadget.cpp).  Internal: not part of the boundary.
+// too): the engine behind the handle, hip_status, pass_repr, and the launch builder (Launch, Run, batch_runs) of the
+// digest paths (hsw_gadget_digest.cpp) and of hsw_gadget_verify (hsw_gadget.cpp).  What the calls of the round over
+// caller-owned device columns share beyond that is hsw_gadget_call.hpp.  Internal: not part of the boundary.
 #ifndef HSW_GADGET_LAUNCH_HPP
 #define HSW_GADGET_LAUNCH_HPP
 
@@ -28,58 +29,6 @@ inline int pass_repr(const Context &c, uint32_t *repr) {
         else if (c.batches[i].repr_flags != *repr) return HSW_ERR_UNSUPPORTED;
     }
     return HSW_OK;
-}
-
-// ---- what the calls over caller-owned device columns share (hsw_gadget_ntt.cpp, hsw_gadget_open.cpp,
-// hsw_gadget_quotient.cpp) ----
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// the representation of the pass for a call that takes 32-byte cells: HSW_OK and *montgomery, or the refusal
-inline int pass_cells(const Context &c, bool *montgomery) {
-    uint32_t repr = 0;
-    if (pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(c.engine, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
-    if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(c.engine, HSW_ERR_UNSUPPORTED, "32-byte cells only");
-    *montgomery = (repr & HSW_REPR_MONTGOMERY) != 0;
-    return HSW_OK;
-}
-
-struct Events {                                     // the stage boundaries of one call
-    std::vector<hipEvent_t> ev;
-    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    hipError_t record(hipStream_t s) {
-        hipEvent_t e = nullptr;
-        hipError_t he = hipEventCreate(&e);
-        if (he != hipSuccess) return he;
-        ev.push_back(e);
-        return hipEventRecord(e, s);
-    }
-};
-
-// 32 stored bytes as a field element; false: not below p
-inline bool load_below_p(PFe &x, const void *stored) {
-    std::memcpy(&x, stored, 32);
-    return pfe_below_p(x);
-}
-
-// bytes [lo, hi) that item `index` of a call writes (out) or reads; other: whatever else the caller wants to name
-struct Interval { uintptr_t lo, hi; size_t index; bool out; size_t other; };
-// An output may overlap neither another output nor anything read: one sweep in address order, with the furthest end of
-// the outputs (and whose it is) and of all intervals seen so far.  true: *writer is the output at fault and *with the
-// interval it overlaps (sorts iv)
-inline bool output_overlaps(std::vector<Interval> &iv, Interval *writer, Interval *with) {
-    std::sort(iv.begin(), iv.end(), [](const Interval &x, const Interval &y) { return x.lo < y.lo; });
-    uintptr_t end_out = 0, end_any = 0;
-    Interval last_out{}, last_any{};
-    for (const Interval &x : iv) {
-        if (x.out ? x.lo < end_any : x.lo < end_out) {
-            *writer = x.out ? x : last_out;
-            *with = x.out ? last_any : x;
-            return true;
-        }
-        if (x.out && x.hi > end_out) { end_out = x.hi; last_out = x; }
-        if (x.hi > end_any) { end_any = x.hi; last_any = x; }
-    }
-    return false;
 }
 
 // Where the launches of a batch write -- or, for hsw_gadget_verify, read: the generator and the verifier build

@@ -2,7 +2,7 @@
 // of device cells from the accessors the launches and deliveries use (Context::lookup_extra, chip_column_cell), and
 // counted on the device by hsw_lookup_counts_kernel.  A translation unit of its own next to hsw_gadget.cpp: only the
 // two entry points below refer to the new kernels.
-#include "hsw_gadget_launch.hpp"
+#include "hsw_gadget_call.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -101,9 +101,9 @@ int hsw_gadget_lookup_multiplicities(hsw_gadget *g, const hsw_lookup_counts *out
     if ((reinterpret_cast<uintptr_t>(out->d_range) | reinterpret_cast<uintptr_t>(out->d_spread)) & 3u)
         return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "a counter table that is not 4-byte aligned");
     if (out->d_range && !(c.whole && c.d_lookup)) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "this gadget has no lookup column");
-    uint32_t repr = 0;
-    if (hsw::pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
-    if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "32-byte cells only");
+    bool mont = false;
+    const int prc = hsw::pass_cells(c, &mont);
+    if (prc != HSW_OK) return prc;
     std::vector<hsw_lookup_run> runs;
     int rc = list_runs(g, runs);
     if (rc != HSW_OK) return rc;
@@ -168,7 +168,7 @@ int hsw_gadget_lookup_multiplicities(hsw_gadget *g, const hsw_lookup_counts *out
     if (he == hipSuccess && zero && out->d_spread)
         he = hsw::launch_lookup_zero(out->d_spread, spread_pitch, (uint32_t)spread_rows, reinterpret_cast<const uint32_t *>(d + off_z1),
                                      zero_ctx[1].size(), stream);
-    if (he == hipSuccess) he = hsw::launch_lookup_counts(p, (size_t)n_chunks, (repr & HSW_REPR_MONTGOMERY) != 0, stream);
+    if (he == hipSuccess) he = hsw::launch_lookup_counts(p, (size_t)n_chunks, mont, stream);
     if (he == hipSuccess) he = hipEventRecord(e->ev1, stream);
     hsw::LookupReport got{};
     if (he == hipSuccess) he = hipMemcpyAsync(&got, d, sizeof got, hipMemcpyDeviceToHost, stream);

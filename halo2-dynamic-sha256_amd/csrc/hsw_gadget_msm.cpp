@@ -2,11 +2,10 @@
 // on the host, the plan of hsw_msm_value.hpp, the launches of hsw_msm.hip group of columns by group, then the host tail
 // -- W window points per column copied back, the Horner over the windows and the one inversion, with the value layer's
 // own code.  A translation unit of its own: only the entry point below refers to those kernels.
-#include "hsw_gadget_launch.hpp"
+#include "hsw_gadget_call.hpp"
 
 #include <algorithm>
 #include <chrono>
-#include <cstdio>
 #include <cstring>
 
 #include "hsw_msm.h"
@@ -17,25 +16,7 @@ namespace {
 const size_t MSM_SCRATCH_BYTES = (size_t)1 << 30;              // the partial buckets of a group of columns
 const size_t MSM_GRID_COLUMNS = 65535;                         // blockIdx.z, blockIdx.y
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Events {                                     // the stage boundaries of one call
-    std::vector<hipEvent_t> ev;
-    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    hipError_t record(hipStream_t s) {
-        hipEvent_t e = nullptr;
-        hipError_t he = hipEventCreate(&e);
-        if (he != hipSuccess) return he;
-        ev.push_back(e);
-        return hipEventRecord(e, s);
-    }
-};
-
-int fail_column(hsw_engine *e, int status, const char *what, size_t b) {
-    char buf[200];
-    std::snprintf(buf, sizeof buf, "column %zu: %s", b, what);
-    return hsw_engine_fail(e, status, buf);
-}
+using hsw::fail_at;
 
 }  // namespace
 
@@ -56,72 +37,61 @@ extern "C" int hsw_gadget_msm(hsw_gadget *g, const hsw_msm *args, hsw_msm_report
     uint64_t max_rows = 0;
     for (size_t b = 0; b < n; b++) {
         const uint64_t rows = args->input_rows ? args->input_rows[b] : args->n_bases;
-        if (rows > args->n_bases) return fail_column(e, HSW_ERR_INVALID_ARG, "input_rows above n_bases", b);
+        if (rows > args->n_bases) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "input_rows above n_bases");
         const uintptr_t in = reinterpret_cast<uintptr_t>(args->d_scalars[b]);
-        if (!in || (in & 15u)) return fail_column(e, HSW_ERR_INVALID_ARG, "a scalar pointer that is NULL or not 16-byte aligned", b);
+        if (!in || (in & 15u)) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "a scalar pointer that is NULL or not 16-byte aligned");
         max_rows = std::max(max_rows, rows);
     }
     hsw::MsmPlan plan;
     if (!hsw::msm_plan((uint32_t)max_rows, args->window_bits, args->slice_rows, plan))
         return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "window_bits is 0 .. 8 and slice_rows 0 or a power of two, 64 .. 2^28");
-    uint32_t repr = 0;
-    if (hsw::pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
-    if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "32-byte cells only");
-    const bool mont = (repr & HSW_REPR_MONTGOMERY) != 0;
+    bool mont = false;
+    const int prc = hsw::pass_cells(c, &mont);
+    if (prc != HSW_OK) return prc;
     // columns in groups whose partial buckets fit the scratch
     const size_t column_bytes = (size_t)hsw::msm_partial_points(plan) * sizeof(hsw::G1);
     const size_t group = std::min(std::min(n, MSM_GRID_COLUMNS), std::max<size_t>(1, MSM_SCRATCH_BYTES / column_bytes));
     const size_t n_groups = (n + group - 1) / group;
     // device staging: [status words][the bases' check][columns][window points][partial buckets of a group]
-    const size_t off_check = align256(n * sizeof(uint32_t)), off_cols = align256(off_check + sizeof(hsw::MsmCheck));
-    const size_t off_win = align256(off_cols + n * sizeof(hsw::MsmColumn)), win_bytes = n * plan.windows * sizeof(hsw::G1);
-    const size_t off_partial = align256(off_win + win_bytes), scratch_bytes = group * column_bytes, bytes = off_partial + scratch_bytes;
-    EngineScope es(e);
-    if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
-    if (bytes > g->msm_cap) {                                // (every earlier call has been waited for: nothing reads the old one)
-        void *p = nullptr;
-        const hipError_t he = hipMalloc(&p, bytes);
-        if (he != hipSuccess) return hsw::hip_status(he);
-        (void)hipFree(g->d_msm);
-        g->d_msm = p; g->msm_cap = bytes;
-    }
-    uint8_t *d = static_cast<uint8_t *>(g->d_msm);
-    std::vector<uint8_t> host(off_win, 0);                   // (the status words start at 0)
     const hsw::MsmCheck check0{0u, ~0u};
-    std::memcpy(host.data() + off_check, &check0, sizeof check0);
+    hsw::Staging st;
+    st.zeroed(n * sizeof(uint32_t));
+    const size_t off_check = st.add(&check0, sizeof check0), off_cols = st.zeroed(n * sizeof(hsw::MsmColumn));
+    const size_t win_bytes = n * plan.windows * sizeof(hsw::G1), off_win = st.work(win_bytes);
+    const size_t scratch_bytes = group * column_bytes, off_partial = st.work(scratch_bytes);
     for (size_t b = 0; b < n; b++) {
-        hsw::MsmColumn mc{};
+        hsw::MsmColumn &mc = st.image<hsw::MsmColumn>(off_cols)[b];
         mc.cells = static_cast<const uint4 *>(args->d_scalars[b]);
         mc.rows = (uint32_t)(args->input_rows ? args->input_rows[b] : args->n_bases);
-        std::memcpy(host.data() + off_cols + b * sizeof mc, &mc, sizeof mc);
     }
+    EngineScope es(e);
+    if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
+    const int grc = g->scratch.reserve(st.bytes);
+    if (grc != HSW_OK) return grc;
+    void *d = g->scratch.d;
     hsw::MsmParams p{};
     p.plan = plan;
     p.bases = static_cast<const uint4 *>(args->d_bases);
-    p.partial = reinterpret_cast<uint4 *>(d + off_partial);
+    p.partial = hsw::at<uint4>(d, off_partial);
     p.montgomery = mont ? 1u : 0u;
     const hipStream_t stream = es.stream;
-    Events ev;
-    hipError_t he = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = ev.record(stream);
-    if (he == hipSuccess) he = hsw::launch_msm_check(p.bases, (uint32_t)max_rows, reinterpret_cast<hsw::MsmCheck *>(d + off_check), stream);
+    hsw::Events ev;
+    hipError_t he = hsw::upload(st, d, stream, ev);
+    if (he == hipSuccess) he = hsw::launch_msm_check(p.bases, (uint32_t)max_rows, hsw::at<hsw::MsmCheck>(d, off_check), stream);
     for (size_t b0 = 0; he == hipSuccess && b0 < n; b0 += group) {
         const uint32_t cols = (uint32_t)std::min(group, n - b0);
-        p.cols = reinterpret_cast<const hsw::MsmColumn *>(d + off_cols) + b0;
-        p.status = reinterpret_cast<uint32_t *>(d) + b0;
-        p.windows = reinterpret_cast<uint4 *>(d + off_win + b0 * plan.windows * sizeof(hsw::G1));
+        p.cols = hsw::at<const hsw::MsmColumn>(d, off_cols) + b0;
+        p.status = hsw::at<uint32_t>(d, 0) + b0;
+        p.windows = hsw::at<uint4>(d, off_win + b0 * plan.windows * sizeof(hsw::G1));
         he = hsw::launch_msm_accumulate(p, cols, stream);
         if (he == hipSuccess) he = hsw::launch_msm_reduce(p, cols, stream);
     }
     if (he == hipSuccess) he = ev.record(stream);
     std::vector<uint8_t> back(off_cols + win_bytes);         // the status words and the check, then the window points
-    if (he == hipSuccess) he = hipMemcpyAsync(back.data(), d, off_cols, hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(back.data() + off_cols, d + off_win, win_bytes, hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    float ms = 0;
-    if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]);
-    e->timed = false;
-    if (he != hipSuccess) return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+    if (he == hipSuccess) he = hipMemcpyAsync(back.data() + off_cols, hsw::at<uint8_t>(d, off_win), win_bytes, hipMemcpyDeviceToHost, stream);
+    std::vector<float> ms;
+    const int frc = hsw::finish(e, he, stream, ev, d, back.data(), off_cols, ms);
+    if (frc != HSW_OK) return frc;
     const auto t0 = std::chrono::steady_clock::now();
     hsw::MsmCheck check;
     std::memcpy(&check, back.data() + off_check, sizeof check);
@@ -138,7 +108,7 @@ extern "C" int hsw_gadget_msm(hsw_gadget *g, const hsw_msm *args, hsw_msm_report
         if (args->status) args->status[b] = st;
     }
     report->finish_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    report->kernel_ms = ms;
+    report->kernel_ms = ms[0];
     report->columns = n;
     report->bad_bases = check.bad;
     if (check.bad) report->first_bad_base = check.first;

@@ -3,10 +3,9 @@
 // (hsw_ntt_value.hpp), the table of omega's powers built or found in the gadget's cache, then the launches of
 // hsw_ntt.hip, group of columns by group.  A translation unit of its own: only the entry point below refers to those
 // kernels.
-#include "hsw_gadget_launch.hpp"
+#include "hsw_gadget_call.hpp"
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 
 #include "hsw_nounwind.hpp"
@@ -17,16 +16,9 @@ namespace {
 const size_t NTT_SCRATCH_BYTES = (size_t)1 << 30;              // the points of a group of columns between launches
 const size_t NTT_GRID_COLUMNS = 65535;                         // blockIdx.y
 
-using hsw::align256;
-using hsw::Events;
+using hsw::fail_at;
 using hsw::Interval;
 using hsw::load_below_p;
-
-int fail_column(hsw_engine *e, int status, const char *what, size_t b) {
-    char buf[200];
-    std::snprintf(buf, sizeof buf, "column %zu: %s", b, what);
-    return hsw_engine_fail(e, status, buf);
-}
 
 }  // namespace
 
@@ -49,17 +41,17 @@ extern "C" int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report
     iv.reserve(2 * n);
     for (size_t b = 0; b < n; b++) {
         const uint64_t rows = args->input_rows ? args->input_rows[b] : N;
-        if (rows > N) return fail_column(e, HSW_ERR_INVALID_ARG, "input_rows above 2^log_n", b);
+        if (rows > N) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "input_rows above 2^log_n");
         const uintptr_t in = reinterpret_cast<uintptr_t>(args->d_inputs[b]), out = reinterpret_cast<uintptr_t>(args->d_outputs[b]);
-        if (!in || (in & 15u)) return fail_column(e, HSW_ERR_INVALID_ARG, "an input pointer that is NULL or not 16-byte aligned", b);
-        if (!out || (out & 15u)) return fail_column(e, HSW_ERR_INVALID_ARG, "an output pointer that is NULL or not 16-byte aligned", b);
+        if (!in || (in & 15u)) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "an input pointer that is NULL or not 16-byte aligned");
+        if (!out || (out & 15u)) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "an output pointer that is NULL or not 16-byte aligned");
         iv.push_back(Interval{out, out + (uintptr_t)N * HSW_CELL_BYTES, b, true, 0});
         if (rows && in != out) iv.push_back(Interval{in, in + (uintptr_t)rows * HSW_CELL_BYTES, b, false, 0});   // (in place: the output's interval stands for both)
     }
     // an output may overlap neither another output nor an input that is not its own in place
     Interval writer{}, with{};
     if (hsw::output_overlaps(iv, &writer, &with))
-        return fail_column(e, HSW_ERR_INVALID_ARG, "its output overlaps an input that is not its own in place, or another output", writer.index);
+        return fail_at(e, HSW_ERR_INVALID_ARG, "column", writer.index, "its output overlaps an input that is not its own in place, or another output");
     if (!args->omega) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "omega is NULL");
     bool mont = false;
     const int prc = hsw::pass_cells(c, &mont);
@@ -81,19 +73,15 @@ extern "C" int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report
     if (n_pass > 1) group = std::min(group, std::max<size_t>(1, NTT_SCRATCH_BYTES / column_bytes));
     // device staging: [status words][columns][shift's windows][tile table in][tile table out][omega's windows][points]
     const size_t tile = (size_t)1 << hsw::NTT_TILE_LOG;
-    const size_t off_cols = align256(n * sizeof(uint32_t)), off_win = align256(off_cols + n * sizeof(hsw::NttColumn));
-    const size_t off_in = align256(off_win + sizeof(hsw::NttWindows)), off_out = align256(off_in + tile * sizeof(hsw::PFe));
-    const size_t off_tw = align256(off_out + tile * sizeof(hsw::PFe)), off_points = align256(off_tw + sizeof(hsw::NttWindows));
-    const size_t scratch_bytes = n_pass > 1 ? group * column_bytes : 0, bytes = off_points + scratch_bytes;
+    hsw::Staging st;
+    st.zeroed(n * sizeof(uint32_t));
+    const size_t off_cols = st.zeroed(n * sizeof(hsw::NttColumn)), off_win = st.zeroed(sizeof(hsw::NttWindows));
+    const size_t off_in = st.zeroed(tile * sizeof(hsw::PFe)), off_out = st.zeroed(tile * sizeof(hsw::PFe)), off_tw = st.zeroed(sizeof(hsw::NttWindows));
+    const size_t scratch_bytes = n_pass > 1 ? group * column_bytes : 0, off_points = st.work(scratch_bytes);
     EngineScope es(e);
     if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
-    if (bytes > g->ntt_cap) {                                // (every earlier call has been waited for: nothing reads the old one)
-        void *p = nullptr;
-        const hipError_t he = hipMalloc(&p, bytes);
-        if (he != hipSuccess) return hsw::hip_status(he);
-        (void)hipFree(g->d_ntt);
-        g->d_ntt = p; g->ntt_cap = bytes;
-    }
+    const int grc = g->scratch.reserve(st.bytes);
+    if (grc != HSW_OK) return grc;
     // the table of omega's powers: the cache's, or a new one in the slot that is free or was used longest ago
     const size_t table_cells = (size_t)1 << (L - 1);
     hsw_gadget::NttTable *table = nullptr;
@@ -113,22 +101,19 @@ extern "C" int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report
         std::memcpy(table->root, omega.l, 32);
     }
     table->stamp = ++g->ntt_stamp;
-    uint8_t *d = static_cast<uint8_t *>(g->d_ntt);
-    std::vector<uint8_t> host(off_points, 0);                // (the status words start at 0)
+    void *d = g->scratch.d;
     for (size_t b = 0; b < n; b++) {
-        hsw::NttColumn nc{};
+        hsw::NttColumn &nc = st.image<hsw::NttColumn>(off_cols)[b];
         nc.in = static_cast<const uint4 *>(args->d_inputs[b]);
         nc.out = static_cast<uint4 *>(args->d_outputs[b]);
-        nc.scratch = reinterpret_cast<uint4 *>(d + off_points + (b % group) * column_bytes);
+        nc.scratch = hsw::at<uint4>(d, off_points + (b % group) * column_bytes);
         nc.rows = (uint32_t)(args->input_rows ? args->input_rows[b] : N);
-        std::memcpy(host.data() + off_cols + b * sizeof nc, &nc, sizeof nc);
     }
     if (shift_in || out_mode == hsw::NTT_OUT_TABLE) {
-        hsw::NttWindows win;
+        hsw::NttWindows &win = *st.image<hsw::NttWindows>(off_win);
         hsw::ntt_stage_windows(shift, win);
-        std::memcpy(host.data() + off_win, &win, sizeof win);
         // g^(offset) of every place of a tile: where launch 0 loads from, or where the last launch stores to (times c)
-        std::vector<hsw::PFe> tab(tile);
+        hsw::PFe *tab = st.image<hsw::PFe>(shift_in ? off_in : off_out);
         for (uint32_t l = 0; l < tile; l++) {
             if (shift_in) tab[l] = hsw::ntt_power(win, hsw::ntt_offset(pass0, l));
             else {
@@ -137,32 +122,26 @@ extern "C" int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report
                 if (args->scale) tab[l] = hsw::fr_mont_mul(tab[l], scale);
             }
         }
-        std::memcpy(host.data() + (shift_in ? off_in : off_out), tab.data(), tile * sizeof(hsw::PFe));
     }
-    if (!cached) {
-        hsw::NttWindows win;
-        hsw::ntt_stage_windows(omega, win);
-        std::memcpy(host.data() + off_tw, &win, sizeof win);
-    }
+    if (!cached) hsw::ntt_stage_windows(omega, *st.image<hsw::NttWindows>(off_tw));
     hsw::NttParams p{};
     p.plan = plan;
     p.twiddle = static_cast<const hsw::PFe *>(table->d_table);
-    p.shift = reinterpret_cast<const hsw::NttWindows *>(d + off_win);
-    p.tile_in = reinterpret_cast<const hsw::PFe *>(d + off_in);
-    p.tile_out = reinterpret_cast<const hsw::PFe *>(d + off_out);
+    p.shift = hsw::at<const hsw::NttWindows>(d, off_win);
+    p.tile_in = hsw::at<const hsw::PFe>(d, off_in);
+    p.tile_out = hsw::at<const hsw::PFe>(d, off_out);
     p.scale = scale;
     p.shift_in = shift_in ? 1u : 0u;
     p.out_mode = out_mode;
     const hipStream_t stream = es.stream;
-    Events ev;
-    hipError_t he = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = ev.record(stream);
+    hsw::Events ev;
+    hipError_t he = hsw::upload(st, d, stream, ev);
     if (he == hipSuccess && !cached)
-        he = hsw::launch_ntt_twiddles(static_cast<hsw::PFe *>(table->d_table), reinterpret_cast<const hsw::NttWindows *>(d + off_tw), (uint32_t)table_cells, stream);
+        he = hsw::launch_ntt_twiddles(static_cast<hsw::PFe *>(table->d_table), hsw::at<const hsw::NttWindows>(d, off_tw), (uint32_t)table_cells, stream);
     if (he == hipSuccess) he = ev.record(stream);
     for (size_t b0 = 0; he == hipSuccess && b0 < n; b0 += group) {
-        p.cols = reinterpret_cast<const hsw::NttColumn *>(d + off_cols) + b0;
-        p.status = reinterpret_cast<uint32_t *>(d) + b0;
+        p.cols = hsw::at<const hsw::NttColumn>(d, off_cols) + b0;
+        p.status = hsw::at<uint32_t>(d, 0) + b0;
         for (uint32_t k = 0; he == hipSuccess && k < n_pass; k++) {
             p.pass = hsw::ntt_pass(plan, k);
             he = hsw::launch_ntt_pass(p, (uint32_t)std::min(group, n - b0), stream);
@@ -170,14 +149,11 @@ extern "C" int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report
     }
     if (he == hipSuccess) he = ev.record(stream);
     std::vector<uint32_t> status(n, 0);
-    if (he == hipSuccess) he = hipMemcpyAsync(status.data(), d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    float ms[2] = {0, 0};
-    for (size_t i = 0; he == hipSuccess && i < 2; i++) he = hipEventElapsedTime(&ms[i], ev.ev[i], ev.ev[i + 1]);
-    e->timed = false;
-    if (he != hipSuccess) {
+    std::vector<float> ms;
+    const int frc = hsw::finish(e, he, stream, ev, d, status.data(), n * sizeof(uint32_t), ms);
+    if (frc != HSW_OK) {
         if (!cached) table->stamp = 0;                       // (the table may not have been built: not to be found again)
-        return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+        return frc;
     }
     report->twiddle_ms = cached ? 0.0f : ms[0];
     report->kernel_ms = ms[1];

@@ -3,10 +3,9 @@
 // and staged with their powers (hsw_open_value.hpp), the groups (or the columns of evaluate) cut into batches whose
 // scratch stays under 1 GiB, then the launches of hsw_open.hip batch by batch.  A translation unit of its own: only the
 // two entry points below refer to those kernels.
-#include "hsw_gadget_launch.hpp"
+#include "hsw_gadget_call.hpp"
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 
 #include "hsw_nounwind.hpp"
@@ -18,15 +17,9 @@ const size_t OPEN_SCRATCH_BYTES = (size_t)1 << 30;             // the scratch of
 const size_t OPEN_GRID_Y = 65535;                              // blockIdx.y
 
 using hsw::align256;
-using hsw::Events;
+using hsw::fail_at;
 using hsw::Interval;
 using hsw::load_below_p;
-
-int fail_at(hsw_engine *e, const char *kind, size_t i, const char *what) {
-    char buf[200];
-    std::snprintf(buf, sizeof buf, "%s %zu: %s", kind, i, what);
-    return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, buf);
-}
 
 // what both calls ask of rows, tile_rows, the columns and the representation; 0 or the status to return
 int check_common(hsw_engine *e, hsw::Context &c, uint32_t flags, uint64_t rows, uint32_t tile_rows, size_t n_columns,
@@ -38,21 +31,11 @@ int check_common(hsw_engine *e, hsw::Context &c, uint32_t flags, uint64_t rows, 
     if (n_columns > 0xFFFFFFFFull) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "n_columns is below 2^32");
     if (!d_columns) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "the column pointer array is NULL");
     for (size_t b = 0; b < n_columns; b++) {
-        if (input_rows && input_rows[b] > rows) return fail_at(e, "column", b, "input_rows above rows");
+        if (input_rows && input_rows[b] > rows) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "input_rows above rows");
         const uintptr_t in = reinterpret_cast<uintptr_t>(d_columns[b]);
-        if (!in || (in & 15u)) return fail_at(e, "column", b, "a pointer that is NULL or not 16-byte aligned");
+        if (!in || (in & 15u)) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "a pointer that is NULL or not 16-byte aligned");
     }
     return hsw::pass_cells(c, &mont);
-}
-
-int grow(hsw_gadget *g, size_t bytes) {                        // (every earlier call has been waited for: nothing reads the old one)
-    if (bytes <= g->open_cap) return HSW_OK;
-    void *p = nullptr;
-    const hipError_t he = hipMalloc(&p, bytes);
-    if (he != hipSuccess) return hsw::hip_status(he);
-    (void)hipFree(g->d_open);
-    g->d_open = p; g->open_cap = bytes;
-    return HSW_OK;
 }
 
 }  // namespace
@@ -75,12 +58,12 @@ extern "C" int hsw_gadget_evaluate(hsw_gadget *g, const hsw_evaluate *args, hsw_
     if (!args->out_evals) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "out_evals is NULL");
     std::vector<hsw::PFe> z(n_points);
     for (size_t t = 0; t < n_points; t++)
-        if (!load_below_p(z[t], static_cast<const uint8_t *>(args->points) + 32 * t)) return fail_at(e, "point", t, "its stored limbs are not below p");
+        if (!load_below_p(z[t], static_cast<const uint8_t *>(args->points) + 32 * t)) return fail_at(e, HSW_ERR_INVALID_ARG, "point", t, "its stored limbs are not below p");
     // the items: the distinct (column, point) pairs, by column
     std::vector<uint64_t> pairs(n_queries);
     for (size_t i = 0; i < n_queries; i++) {
-        if (args->query_column[i] >= n) return fail_at(e, "query", i, "its column index is out of range");
-        if (args->query_point[i] >= n_points) return fail_at(e, "query", i, "its point index is out of range");
+        if (args->query_column[i] >= n) return fail_at(e, HSW_ERR_INVALID_ARG, "query", i, "its column index is out of range");
+        if (args->query_point[i] >= n_points) return fail_at(e, HSW_ERR_INVALID_ARG, "query", i, "its point index is out of range");
         pairs[i] = ((uint64_t)args->query_column[i] << 32) | args->query_point[i];
     }
     const std::vector<uint64_t> query_pair(pairs);
@@ -115,31 +98,28 @@ extern "C" int hsw_gadget_evaluate(hsw_gadget *g, const hsw_evaluate *args, hsw_
     }
     batch_first.push_back(cols.size());
     // device staging: [status words][evaluations][columns][items][points][the tiles' sums]
-    const size_t off_evals = align256(n * sizeof(uint32_t)), off_cols = align256(off_evals + n_items * sizeof(hsw::PFe));
-    const size_t off_items = align256(off_cols + cols.size() * sizeof(hsw::OpenColumn)), off_points = align256(off_items + n_items * sizeof(hsw::OpenItem));
-    const size_t off_tiles = align256(off_points + n_points * sizeof(hsw::OpenPoint));
+    hsw::Staging st;
+    st.zeroed(n * sizeof(uint32_t));
+    const size_t off_evals = st.zeroed(n_items * sizeof(hsw::PFe)), off_cols = st.add(cols.data(), cols.size() * sizeof(hsw::OpenColumn));
+    const size_t off_items = st.add(items.data(), n_items * sizeof(hsw::OpenItem)), off_points = st.zeroed(n_points * sizeof(hsw::OpenPoint));
+    const size_t off_tiles = st.work(scratch_bytes);
+    for (size_t t = 0; t < n_points; t++) hsw::open_stage_point(hsw::open_to_mont(z[t], mont), geo, st.image<hsw::OpenPoint>(off_points)[t]);
     EngineScope es(e);
     if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
-    const int grc = grow(g, off_tiles + scratch_bytes);
+    const int grc = g->scratch.reserve(st.bytes);
     if (grc != HSW_OK) return grc;
-    uint8_t *d = static_cast<uint8_t *>(g->d_open);
-    std::vector<uint8_t> host(off_tiles, 0);                   // (the status words start at 0)
-    std::memcpy(host.data() + off_cols, cols.data(), cols.size() * sizeof(hsw::OpenColumn));
-    std::memcpy(host.data() + off_items, items.data(), n_items * sizeof(hsw::OpenItem));
-    for (size_t t = 0; t < n_points; t++)
-        hsw::open_stage_point(hsw::open_to_mont(z[t], mont), geo, *reinterpret_cast<hsw::OpenPoint *>(host.data() + off_points + t * sizeof(hsw::OpenPoint)));
+    void *d = g->scratch.d;
     hsw::OpenParams p{};
     p.geo = geo;
-    p.cols = reinterpret_cast<const hsw::OpenColumn *>(d + off_cols);
-    p.items = reinterpret_cast<const hsw::OpenItem *>(d + off_items);
-    p.points = reinterpret_cast<const hsw::OpenPoint *>(d + off_points);
-    p.tiles = reinterpret_cast<uint4 *>(d + off_tiles);
-    p.evals = reinterpret_cast<uint4 *>(d + off_evals);
-    p.status = reinterpret_cast<uint32_t *>(d);
+    p.cols = hsw::at<const hsw::OpenColumn>(d, off_cols);
+    p.items = hsw::at<const hsw::OpenItem>(d, off_items);
+    p.points = hsw::at<const hsw::OpenPoint>(d, off_points);
+    p.tiles = hsw::at<uint4>(d, off_tiles);
+    p.evals = hsw::at<uint4>(d, off_evals);
+    p.status = hsw::at<uint32_t>(d, 0);
     const hipStream_t stream = es.stream;
-    Events ev;
-    hipError_t he = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = ev.record(stream);
+    hsw::Events ev;
+    hipError_t he = hsw::upload(st, d, stream, ev);
     uint32_t launches = 0;
     for (size_t k = 0; he == hipSuccess && k + 1 < batch_first.size(); k++) {
         const size_t c0 = batch_first[k], c1 = batch_first[k + 1];
@@ -152,12 +132,9 @@ extern "C" int hsw_gadget_evaluate(hsw_gadget *g, const hsw_evaluate *args, hsw_
     }
     if (he == hipSuccess) he = ev.record(stream);
     std::vector<uint8_t> back(off_cols);
-    if (he == hipSuccess) he = hipMemcpyAsync(back.data(), d, back.size(), hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    float ms = 0;
-    if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]);
-    e->timed = false;
-    if (he != hipSuccess) return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+    std::vector<float> ms;
+    const int frc = hsw::finish(e, he, stream, ev, d, back.data(), back.size(), ms);
+    if (frc != HSW_OK) return frc;
     std::vector<uint32_t> status(n);
     std::memcpy(status.data(), back.data(), n * sizeof(uint32_t));
     for (size_t b = 0; b < n; b++) {
@@ -177,7 +154,7 @@ extern "C" int hsw_gadget_evaluate(hsw_gadget *g, const hsw_evaluate *args, hsw_
     report->tiles = geo.n_tiles;
     report->thread_rows = hsw::OPEN_ROWS;
     report->launches = launches;
-    report->kernel_ms = ms;
+    report->kernel_ms = ms[0];
     if (args->status) std::memcpy(args->status, status.data(), n * sizeof(uint32_t));
     return HSW_OK;
 } HSW_NO_UNWIND
@@ -208,19 +185,19 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
     }
     for (size_t k = 0; k < n_groups; k++) {
         const uint64_t f0 = args->group_first[k], f1 = args->group_first[k + 1];
-        if (f1 <= f0) return fail_at(e, "group", k, "an empty group (group_first must increase)");
-        if (f1 > 0xFFFFFFFFull) return fail_at(e, "group", k, "group_first is below 2^32");
+        if (f1 <= f0) return fail_at(e, HSW_ERR_INVALID_ARG, "group", k, "an empty group (group_first must increase)");
+        if (f1 > 0xFFFFFFFFull) return fail_at(e, HSW_ERR_INVALID_ARG, "group", k, "group_first is below 2^32");
         for (uint64_t i = f0; i < f1; i++)
-            if (args->group_columns[i] >= n) return fail_at(e, "group", k, "a column index out of range");
-        if (!load_below_p(z[k], static_cast<const uint8_t *>(args->points) + 32 * k)) return fail_at(e, "group", k, "a point whose stored limbs are not below p");
-        if (!load_below_p(v[k], static_cast<const uint8_t *>(args->challenges) + 32 * k)) return fail_at(e, "group", k, "a challenge whose stored limbs are not below p");
+            if (args->group_columns[i] >= n) return fail_at(e, HSW_ERR_INVALID_ARG, "group", k, "a column index out of range");
+        if (!load_below_p(z[k], static_cast<const uint8_t *>(args->points) + 32 * k)) return fail_at(e, HSW_ERR_INVALID_ARG, "group", k, "a point whose stored limbs are not below p");
+        if (!load_below_p(v[k], static_cast<const uint8_t *>(args->challenges) + 32 * k)) return fail_at(e, HSW_ERR_INVALID_ARG, "group", k, "a challenge whose stored limbs are not below p");
         const uintptr_t q = reinterpret_cast<uintptr_t>(args->d_quotients[k]);
-        if (!q || (q & 15u)) return fail_at(e, "group", k, "a quotient pointer that is NULL or not 16-byte aligned");
+        if (!q || (q & 15u)) return fail_at(e, HSW_ERR_INVALID_ARG, "group", k, "a quotient pointer that is NULL or not 16-byte aligned");
         iv.push_back(Interval{q, q + (uintptr_t)rows * HSW_CELL_BYTES, k, true, 0});
     }
     // a quotient may overlap neither the `rows` cells of a column nor another quotient
     Interval writer{}, with{};
-    if (hsw::output_overlaps(iv, &writer, &with)) return fail_at(e, "group", writer.index, "its quotient overlaps a column or another quotient");
+    if (hsw::output_overlaps(iv, &writer, &with)) return fail_at(e, HSW_ERR_INVALID_ARG, "group", writer.index, "its quotient overlaps a column or another quotient");
     // batches of groups whose scratch fits: per group the tiles' sums, a cell per thread and, for two columns or more, c
     const size_t n_refs = (size_t)args->group_first[n_groups];
     const size_t tile_bytes = (size_t)geo.n_tiles * sizeof(hsw::PFe), seed_bytes = align256((size_t)geo.seeds * sizeof(hsw::PFe));
@@ -236,23 +213,22 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
     }
     batch_first.push_back(n_groups);
     // device staging: [status words][evaluations][columns][group columns][groups][items][points][the scratch of a batch]
-    const size_t off_evals = align256(n_groups * sizeof(uint32_t)), off_cols = align256(off_evals + n_groups * sizeof(hsw::PFe));
-    const size_t off_refs = align256(off_cols + n * sizeof(hsw::OpenColumn)), off_groups = align256(off_refs + n_refs * sizeof(uint32_t));
-    const size_t off_items = align256(off_groups + n_groups * sizeof(hsw::OpenGroup)), off_points = align256(off_items + n_groups * sizeof(hsw::OpenItem));
-    const size_t off_scratch = align256(off_points + n_groups * sizeof(hsw::OpenPoint));
+    hsw::Staging st;
+    st.zeroed(n_groups * sizeof(uint32_t));
+    const size_t off_evals = st.zeroed(n_groups * sizeof(hsw::PFe)), off_cols = st.zeroed(n * sizeof(hsw::OpenColumn));
+    const size_t off_refs = st.add(args->group_columns, n_refs * sizeof(uint32_t)), off_groups = st.zeroed(n_groups * sizeof(hsw::OpenGroup));
+    const size_t off_items = st.zeroed(n_groups * sizeof(hsw::OpenItem)), off_points = st.zeroed(n_groups * sizeof(hsw::OpenPoint));
+    const size_t off_scratch = st.work(scratch_bytes);
     EngineScope es(e);
     if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
-    const int grc = grow(g, off_scratch + scratch_bytes);
+    const int grc = g->scratch.reserve(st.bytes);
     if (grc != HSW_OK) return grc;
-    uint8_t *d = static_cast<uint8_t *>(g->d_open);
-    std::vector<uint8_t> host(off_scratch, 0);                 // (the status words start at 0)
+    void *d = g->scratch.d;
     for (size_t b = 0; b < n; b++) {
-        hsw::OpenColumn oc{};
+        hsw::OpenColumn &oc = st.image<hsw::OpenColumn>(off_cols)[b];
         oc.cells = static_cast<const uint4 *>(args->d_columns[b]);
         oc.rows = (uint32_t)(args->input_rows ? args->input_rows[b] : rows);
-        std::memcpy(host.data() + off_cols + b * sizeof oc, &oc, sizeof oc);
     }
-    std::memcpy(host.data() + off_refs, args->group_columns, n_refs * sizeof(uint32_t));
     for (size_t bk = 0; bk + 1 < batch_first.size(); bk++) {
         const size_t g0 = batch_first[bk], g1 = batch_first[bk + 1];
         size_t off = (g1 - g0) * tile_bytes;                     // the tiles' sums of the batch come first, group after group
@@ -261,10 +237,10 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
             og.first = (uint32_t)args->group_first[k];
             og.m = (uint32_t)(args->group_first[k + 1] - args->group_first[k]);
             og.v = hsw::open_to_mont(v[k], mont);
-            og.seeds = reinterpret_cast<uint4 *>(d + off_scratch + off);
+            og.seeds = hsw::at<uint4>(d, off_scratch + off);
             off += seed_bytes;
             if (og.m > 1) {
-                og.c = reinterpret_cast<uint4 *>(d + off_scratch + off);
+                og.c = hsw::at<uint4>(d, off_scratch + off);
                 off += c_bytes;
                 og.src = og.c; og.src_rows = (uint32_t)rows;
             } else {                                             // one column: it is its own c
@@ -273,26 +249,24 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
                 og.src_rows = (uint32_t)(args->input_rows ? args->input_rows[b] : rows);
             }
             og.q = static_cast<uint4 *>(args->d_quotients[k]);
-            std::memcpy(host.data() + off_groups + k * sizeof og, &og, sizeof og);
-            const hsw::OpenItem it{(uint32_t)k, (uint32_t)k};
-            std::memcpy(host.data() + off_items + k * sizeof it, &it, sizeof it);
-            hsw::open_stage_point(hsw::open_to_mont(z[k], mont), geo, *reinterpret_cast<hsw::OpenPoint *>(host.data() + off_points + k * sizeof(hsw::OpenPoint)));
+            st.image<hsw::OpenGroup>(off_groups)[k] = og;
+            st.image<hsw::OpenItem>(off_items)[k] = hsw::OpenItem{(uint32_t)k, (uint32_t)k};
+            hsw::open_stage_point(hsw::open_to_mont(z[k], mont), geo, st.image<hsw::OpenPoint>(off_points)[k]);
         }
     }
     hsw::OpenParams p{};
     p.geo = geo;
-    p.cols = reinterpret_cast<const hsw::OpenColumn *>(d + off_cols);
-    p.group_cols = reinterpret_cast<const uint32_t *>(d + off_refs);
-    p.groups = reinterpret_cast<const hsw::OpenGroup *>(d + off_groups);
-    p.items = reinterpret_cast<const hsw::OpenItem *>(d + off_items);
-    p.points = reinterpret_cast<const hsw::OpenPoint *>(d + off_points);
-    p.tiles = reinterpret_cast<uint4 *>(d + off_scratch);
-    p.evals = reinterpret_cast<uint4 *>(d + off_evals);
-    p.status = reinterpret_cast<uint32_t *>(d);
+    p.cols = hsw::at<const hsw::OpenColumn>(d, off_cols);
+    p.group_cols = hsw::at<const uint32_t>(d, off_refs);
+    p.groups = hsw::at<const hsw::OpenGroup>(d, off_groups);
+    p.items = hsw::at<const hsw::OpenItem>(d, off_items);
+    p.points = hsw::at<const hsw::OpenPoint>(d, off_points);
+    p.tiles = hsw::at<uint4>(d, off_scratch);
+    p.evals = hsw::at<uint4>(d, off_evals);
+    p.status = hsw::at<uint32_t>(d, 0);
     const hipStream_t stream = es.stream;
-    Events ev;
-    hipError_t he = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = ev.record(stream);
+    hsw::Events ev;
+    hipError_t he = hsw::upload(st, d, stream, ev);
     uint32_t launches = 0;
     for (size_t bk = 0; he == hipSuccess && bk + 1 < batch_first.size(); bk++) {
         const uint32_t nb = (uint32_t)(batch_first[bk + 1] - batch_first[bk]);
@@ -304,12 +278,9 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
     }
     if (he == hipSuccess) he = ev.record(stream);
     std::vector<uint8_t> back(off_cols);
-    if (he == hipSuccess) he = hipMemcpyAsync(back.data(), d, back.size(), hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    float ms = 0;
-    if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]);
-    e->timed = false;
-    if (he != hipSuccess) return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+    std::vector<float> ms;
+    const int frc = hsw::finish(e, he, stream, ev, d, back.data(), back.size(), ms);
+    if (frc != HSW_OK) return frc;
     std::vector<uint32_t> status(n_groups);
     std::memcpy(status.data(), back.data(), n_groups * sizeof(uint32_t));
     for (size_t k = 0; k < n_groups; k++) {
@@ -325,7 +296,7 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
     report->thread_rows = hsw::OPEN_ROWS;
     report->launches = launches;
     report->batches = (uint32_t)(batch_first.size() - 1);
-    report->kernel_ms = ms;
+    report->kernel_ms = ms[0];
     if (args->status) std::memcpy(args->status, status.data(), n_groups * sizeof(uint32_t));
     return HSW_OK;
 } HSW_NO_UNWIND

@@ -2,33 +2,14 @@
 // arguments' multiplicities counted by hsw_lookup_counts_kernel from the runs hsw_gadget_lookup_runs lists -- one table
 // per ARGUMENT, where hsw_gadget_lookup_multiplicities counts one per proof -- or given, then expanded into A' and S' by
 // the kernels of hsw_lookup_permuted.hip.  A translation unit of its own: only the entry point below refers to them.
-#include "hsw_gadget_launch.hpp"
+#include "hsw_gadget_call.hpp"
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 
 #include "hsw_lookup_permuted.h"
 #include "hsw_nounwind.hpp"
 #include "hsw_permuted_value.hpp"
-
-namespace {
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Events {                                     // the stage boundaries of one call
-    std::vector<hipEvent_t> ev;
-    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    hipError_t record(hipStream_t s) {
-        hipEvent_t e = nullptr;
-        hipError_t he = hipEventCreate(&e);
-        if (he != hipSuccess) return he;
-        ev.push_back(e);
-        return hipEventRecord(e, s);
-    }
-};
-
-}  // namespace
 
 extern "C" int hsw_gadget_lookup_permuted(hsw_gadget *g, const hsw_lookup_permuted *args, hsw_permuted_report *report) try {
     if (!g || !args || !report) return HSW_ERR_INVALID_ARG;
@@ -54,10 +35,9 @@ extern "C" int hsw_gadget_lookup_permuted(hsw_gadget *g, const hsw_lookup_permut
     if (m_pitch < T) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "m_pitch below the table size");
     if (reinterpret_cast<uintptr_t>(args->d_m) & 3u) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "d_m is not 4-byte aligned");
     if (!spread && !(c.whole && c.d_lookup)) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "this gadget has no lookup column");
-    uint32_t repr = 0;
-    if (hsw::pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
-    if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "32-byte cells only");
-    const bool mont = (repr & HSW_REPR_MONTGOMERY) != 0;
+    bool mont = false;
+    const int prc = hsw::pass_cells(c, &mont);
+    if (prc != HSW_OK) return prc;
     std::vector<hsw::PFe> thetas;
     if (spread) {
         if (!args->thetas) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "the spread argument needs thetas");
@@ -87,11 +67,8 @@ extern "C" int hsw_gadget_lookup_permuted(hsw_gadget *g, const hsw_lookup_permut
             dev.push_back(hsw::LookupRun{r.d_cells, r.d_spread, r.n, 0, a});
         }
         for (size_t a = 0; a < n_args; a++)
-            if (per_arg[a] > u) {
-                char buf[128];
-                std::snprintf(buf, sizeof buf, "argument %zu has %llu lookup entries, more than usable_rows", a, (unsigned long long)per_arg[a]);
-                return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, buf);
-            }
+            if (per_arg[a] > u)
+                return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, ("argument " + std::to_string(a) + " has " + std::to_string(per_arg[a]) + " lookup entries, more than usable_rows").c_str());
         if (dev.size() >= (1u << 24)) return hsw_engine_fail(e, HSW_ERR_TOO_LARGE, "more than 2^24 lookup runs");
     }
     uint64_t chunk = (report->entries / 2048 + 255) / 256 * 256;
@@ -114,43 +91,34 @@ extern "C" int hsw_gadget_lookup_permuted(hsw_gadget *g, const hsw_lookup_permut
     const size_t group_tables = spread ? group / (size_t)ncols : 1;
     // device staging: [report][thetas][runs][arguments][heads of a group][m, where it is not the caller's][index arrays
     // of a group][value tables of a group]
-    const size_t off_thetas = align256(sizeof(hsw::PermutedReport)), off_runs = align256(off_thetas + thetas.size() * sizeof(hsw::PFe));
-    const size_t off_args = align256(off_runs + dev.size() * sizeof(hsw::LookupRun)), off_heads = align256(off_args + n_args * sizeof(hsw::PermutedArg));
-    const size_t off_m = align256(off_heads + group * sizeof(hsw::PermutedHead)), off_index = align256(off_m + m_bytes);
-    const size_t off_values = align256(off_index + group * index_bytes), bytes = off_values + group_tables * value_bytes;
+    const hsw::PermutedReport none{{0, ~0ull}, 0, 0};
+    hsw::Staging st;
+    st.add(&none, sizeof none);
+    const size_t off_thetas = st.add(thetas.data(), thetas.size() * sizeof(hsw::PFe)), off_runs = st.add(dev.data(), dev.size() * sizeof(hsw::LookupRun));
+    const size_t off_args = st.zeroed(n_args * sizeof(hsw::PermutedArg));
+    const size_t off_heads = st.work(group * sizeof(hsw::PermutedHead)), off_m = st.work(m_bytes), off_index = st.work(group * index_bytes);
+    const size_t off_values = st.work(group_tables * value_bytes);
     EngineScope es(e);
     if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
-    if (bytes > g->permuted_cap) {                           // (every earlier call has been waited for: nothing reads the old one)
-        void *p = nullptr;
-        const hipError_t he = hipMalloc(&p, bytes);
-        if (he != hipSuccess) return hsw::hip_status(he);
-        (void)hipFree(g->d_permuted);
-        g->d_permuted = p; g->permuted_cap = bytes;
-    }
-    uint8_t *d = static_cast<uint8_t *>(g->d_permuted);
-    uint32_t *m_base = args->d_m ? args->d_m : reinterpret_cast<uint32_t *>(d + off_m);
-    uint4 *d_values = reinterpret_cast<uint4 *>(d + off_values);
-    std::vector<uint8_t> host(off_heads, 0);
-    const hsw::PermutedReport none{{0, ~0ull}, 0, 0};
-    std::memcpy(host.data(), &none, sizeof none);
-    if (!thetas.empty()) std::memcpy(host.data() + off_thetas, thetas.data(), thetas.size() * sizeof(hsw::PFe));
-    if (!dev.empty()) std::memcpy(host.data() + off_runs, dev.data(), dev.size() * sizeof(hsw::LookupRun));
+    const int grc = g->scratch.reserve(st.bytes);
+    if (grc != HSW_OK) return grc;
+    void *d = g->scratch.d;
+    uint32_t *m_base = args->d_m ? args->d_m : hsw::at<uint32_t>(d, off_m);
+    uint4 *d_values = hsw::at<uint4>(d, off_values);
     for (size_t a = 0; a < n_args; a++) {
         const size_t table = spread ? (a % group) / (size_t)ncols : 0;    // its value table among the group's
-        const hsw::PermutedArg pa{m_base + a * m_pitch, args->d_input_columns[a], args->d_table_columns[a], d_values + 2 * table * (size_t)T};
-        std::memcpy(host.data() + off_args + a * sizeof pa, &pa, sizeof pa);
+        st.image<hsw::PermutedArg>(off_args)[a] = hsw::PermutedArg{m_base + a * m_pitch, args->d_input_columns[a], args->d_table_columns[a], d_values + 2 * table * (size_t)T};
     }
-    hsw::PermutedReport *d_report = reinterpret_cast<hsw::PermutedReport *>(d);
+    hsw::PermutedReport *d_report = hsw::at<hsw::PermutedReport>(d, 0);
     const hipStream_t stream = es.stream;
-    Events ev;
-    hipError_t he = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = ev.record(stream);
+    hsw::Events ev;
+    hipError_t he = hsw::upload(st, d, stream, ev);
     // ---- stage 1, all arguments: the multiplicities and the flag
     if (he == hipSuccess && given) he = hsw::launch_permuted_sums(m_base, m_pitch, (uint32_t)T, (uint32_t)u, n_args, d_report, stream);
     if (he == hipSuccess && !given) he = hsw::launch_permuted_zero(m_base, m_pitch, (uint32_t)T, n_args, stream);
     if (he == hipSuccess && !given && !dev.empty()) {
         hsw::LookupCountParams p{};
-        p.runs = reinterpret_cast<const hsw::LookupRun *>(d + off_runs);
+        p.runs = hsw::at<const hsw::LookupRun>(d, off_runs);
         p.n_runs = (uint32_t)dev.size();
         p.chunk = (uint32_t)chunk;
         p.range = p.spread = m_base;                          // (the kernel's "proof" is the argument: LookupRun::context)
@@ -165,31 +133,26 @@ extern "C" int hsw_gadget_lookup_permuted(hsw_gadget *g, const hsw_lookup_permut
                                   : args->flags & HSW_PERMUTED_THETA_ON_SPREAD ? hsw::PERMUTED_VALUE_THETA_ON_SPREAD : hsw::PERMUTED_VALUE_SPREAD;
     for (size_t a0 = 0; a0 < n_args && he == hipSuccess; a0 += group) {
         hsw::PermutedParams p{};
-        p.args = reinterpret_cast<const hsw::PermutedArg *>(d + off_args) + a0;
+        p.args = hsw::at<const hsw::PermutedArg>(d, off_args) + a0;
         p.n_args = (uint32_t)std::min(group, n_args - a0);
         p.T = (uint32_t)T; p.u = (uint32_t)u;
-        p.index = reinterpret_cast<uint32_t *>(d + off_index);
-        p.heads = reinterpret_cast<hsw::PermutedHead *>(d + off_heads);
+        p.index = hsw::at<uint32_t>(d, off_index);
+        p.heads = hsw::at<hsw::PermutedHead>(d, off_heads);
         p.report = d_report;
         he = hsw::launch_permuted_prepare(p, stream);
         const size_t tables = spread ? p.n_args / (size_t)ncols : 1;
         if (he == hipSuccess && (spread || a0 == 0))          // (RANGE: one table for every group)
-            he = hsw::launch_permuted_values(d_values, reinterpret_cast<const uint32_t *>(d + off_thetas) + (spread ? a0 / ncols * 8 : 0), kind,
+            he = hsw::launch_permuted_values(d_values, hsw::at<const uint32_t>(d, off_thetas) + (spread ? a0 / ncols * 8 : 0), kind,
                                              (uint32_t)T, tables, mont, stream);
         if (he == hipSuccess) he = ev.record(stream);
         if (he == hipSuccess) he = hsw::launch_permuted_write(p, stream);
         if (he == hipSuccess) he = ev.record(stream);
     }
     hsw::PermutedReport got{};
-    if (he == hipSuccess) he = hipMemcpyAsync(&got, d, sizeof got, hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    for (size_t i = 0; he == hipSuccess && i + 1 < ev.ev.size(); i++) {
-        float ms = 0;
-        he = hipEventElapsedTime(&ms, ev.ev[i], ev.ev[i + 1]);
-        (i % 2 ? report->write_ms : report->prepare_ms) += ms;
-    }
-    e->timed = false;
-    if (he != hipSuccess) return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+    std::vector<float> ms;
+    const int frc = hsw::finish(e, he, stream, ev, d, &got, sizeof got, ms);
+    if (frc != HSW_OK) return frc;
+    for (size_t i = 0; i < ms.size(); i++) (i % 2 ? report->write_ms : report->prepare_ms) += ms[i];
     report->kernel_ms = report->prepare_ms + report->write_ms;
     report->arguments = n_args;
     report->not_in_table = got.count.not_in_table;

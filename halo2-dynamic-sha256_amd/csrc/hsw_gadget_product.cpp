@@ -1,10 +1,9 @@
 // hsw_gadget_product.cpp -- the grand-product column Z of halo2's lookup argument (include/hsw.h, "grand-product column"):
 // every refusal decided on the host, the caller's pointers and challenges staged, then the three launches of
 // hsw_lookup_product.hip.  A translation unit of its own: only the entry point below refers to those kernels.
-#include "hsw_gadget_launch.hpp"
+#include "hsw_gadget_call.hpp"
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 
 #include "hsw_lookup_permuted.h"
@@ -15,31 +14,8 @@ static_assert(hsw::PRODUCT_OPEN == HSW_PRODUCT_OPEN && hsw::PRODUCT_ZERO_DENOM =
                   hsw::PRODUCT_CELL_NOT_BELOW_P == HSW_PRODUCT_CELL_NOT_BELOW_P,
               "the device's status bits are the public ones");
 
-namespace {
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Events {                                     // the stage boundaries of one call
-    std::vector<hipEvent_t> ev;
-    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    hipError_t record(hipStream_t s) {
-        hipEvent_t e = nullptr;
-        hipError_t he = hipEventCreate(&e);
-        if (he != hipSuccess) return he;
-        ev.push_back(e);
-        return hipEventRecord(e, s);
-    }
-};
-
-struct Interval { uintptr_t lo, hi; size_t arg; bool z; };    // bytes [lo, hi) of argument arg's Z column or of a column it reads
-
-int fail_arg(hsw_engine *e, int status, const char *what, size_t a) {
-    char buf[160];
-    std::snprintf(buf, sizeof buf, "argument %zu: %s", a, what);
-    return hsw_engine_fail(e, status, buf);
-}
-
-}  // namespace
+using hsw::fail_at;
+using hsw::Interval;
 
 extern "C" int hsw_gadget_lookup_product(hsw_gadget *g, const hsw_lookup_product *args, hsw_product_report *report) try {
     if (!g || !args || !report) return HSW_ERR_INVALID_ARG;
@@ -63,30 +39,27 @@ extern "C" int hsw_gadget_lookup_product(hsw_gadget *g, const hsw_lookup_product
     iv.reserve(5 * n_args);
     for (size_t a = 0; a < n_args; a++) {
         const uint64_t rows = args->input_rows ? args->input_rows[a] : u;
-        if (rows > u) return fail_arg(e, HSW_ERR_INVALID_ARG, "input_rows above usable_rows", a);
+        if (rows > u) return fail_at(e, HSW_ERR_INVALID_ARG, "argument", a, "input_rows above usable_rows");
         const uintptr_t col[5] = {reinterpret_cast<uintptr_t>(args->d_inputs[a]), spread ? reinterpret_cast<uintptr_t>(args->d_inputs_spread[a]) : 16,
                                   reinterpret_cast<uintptr_t>(args->d_permuted_inputs[a]), reinterpret_cast<uintptr_t>(args->d_permuted_tables[a]),
                                   reinterpret_cast<uintptr_t>(args->d_products[a])};
         const uint64_t cells[5] = {rows, spread ? rows : 0, u, u, u + 1};
         for (int k = 0; k < 5; k++) {
-            if (!col[k] || (col[k] & 15u)) return fail_arg(e, HSW_ERR_INVALID_ARG, "a column pointer that is NULL or not 16-byte aligned", a);
-            if (cells[k]) iv.push_back(Interval{col[k], col[k] + (uintptr_t)cells[k] * HSW_CELL_BYTES, a, k == 4});
+            if (!col[k] || (col[k] & 15u)) return fail_at(e, HSW_ERR_INVALID_ARG, "argument", a, "a column pointer that is NULL or not 16-byte aligned");
+            if (cells[k]) iv.push_back(Interval{col[k], col[k] + (uintptr_t)cells[k] * HSW_CELL_BYTES, a, k == 4, 0});
         }
     }
-    // a Z column may overlap neither a column that is read nor another Z column: one sweep in address order, with the
-    // furthest end of the Z columns and of all columns seen so far
-    std::sort(iv.begin(), iv.end(), [](const Interval &x, const Interval &y) { return x.lo < y.lo; });
-    uintptr_t end_z = 0, end_any = 0;
-    for (const Interval &x : iv) {
-        if (x.z ? x.lo < end_any : x.lo < end_z) return fail_arg(e, HSW_ERR_INVALID_ARG, "its Z column overlaps a column read or another Z column, or its columns overlap another argument's Z", x.arg);
-        if (x.z) end_z = std::max(end_z, x.hi);
-        end_any = std::max(end_any, x.hi);
+    // a Z column may overlap neither a column that is read nor another Z column; the argument named is the one whose
+    // interval comes later in address order (of two that start together, the later argument)
+    Interval writer{}, with{};
+    if (hsw::output_overlaps(iv, &writer, &with)) {
+        const bool writer_later = with.out || writer.lo > with.lo || (writer.lo == with.lo && writer.index > with.index);
+        return fail_at(e, HSW_ERR_INVALID_ARG, "argument", writer_later ? writer.index : with.index, "its Z column overlaps a column read or another Z column, or its columns overlap another argument's Z");
     }
     if (!args->betas || !args->gammas || (spread && !args->thetas)) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "a challenge array is NULL");
-    uint32_t repr = 0;
-    if (hsw::pass_repr(c, &repr) != HSW_OK) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "the batches of the pass differ in representation");
-    if ((repr | c.repr_flags) & HSW_REPR_COMPACT64) return hsw_engine_fail(e, HSW_ERR_UNSUPPORTED, "32-byte cells only");
-    const bool mont = (repr & HSW_REPR_MONTGOMERY) != 0;
+    bool mont = false;
+    const int prc = hsw::pass_cells(c, &mont);
+    if (prc != HSW_OK) return prc;
     std::vector<hsw::ProductChallenges> ch((size_t)K);
     for (size_t k = 0; k < (size_t)K; k++) {
         hsw::ProductChallenges &x = ch[k];
@@ -101,41 +74,32 @@ extern "C" int hsw_gadget_lookup_product(hsw_gadget *g, const hsw_lookup_product
     const uint64_t n_tiles = (u + 1 + hsw::PRODUCT_TILE - 1) / hsw::PRODUCT_TILE;
     if (n_tiles * n_args > 0x7fffffffull) return hsw_engine_fail(e, HSW_ERR_TOO_LARGE, "too many tiles for one launch");
     // device staging: [status words][arguments][challenges][tile products]
-    const size_t off_args = align256(n_args * sizeof(uint32_t)), off_ch = align256(off_args + n_args * sizeof(hsw::ProductArg));
-    const size_t off_tiles = align256(off_ch + ch.size() * sizeof(hsw::ProductChallenges));
-    const size_t bytes = off_tiles + n_args * (size_t)n_tiles * 2 * sizeof(hsw::PFe);
+    hsw::Staging st;
+    st.zeroed(n_args * sizeof(uint32_t));
+    const size_t off_args = st.zeroed(n_args * sizeof(hsw::ProductArg)), off_ch = st.add(ch.data(), ch.size() * sizeof(hsw::ProductChallenges));
+    const size_t off_tiles = st.work(n_args * (size_t)n_tiles * 2 * sizeof(hsw::PFe));
+    for (size_t a = 0; a < n_args; a++)
+        st.image<hsw::ProductArg>(off_args)[a] = hsw::ProductArg{static_cast<const uint4 *>(args->d_inputs[a]), spread ? static_cast<const uint4 *>(args->d_inputs_spread[a]) : nullptr,
+                                                                 static_cast<const uint4 *>(args->d_permuted_inputs[a]), static_cast<const uint4 *>(args->d_permuted_tables[a]),
+                                                                 static_cast<uint4 *>(args->d_products[a]), (uint32_t)(args->input_rows ? args->input_rows[a] : u),
+                                                                 (uint32_t)(spread ? a / ncols : a)};
     EngineScope es(e);
     if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
-    if (bytes > g->product_cap) {                            // (every earlier call has been waited for: nothing reads the old one)
-        void *p = nullptr;
-        const hipError_t he = hipMalloc(&p, bytes);
-        if (he != hipSuccess) return hsw::hip_status(he);
-        (void)hipFree(g->d_product);
-        g->d_product = p; g->product_cap = bytes;
-    }
-    uint8_t *d = static_cast<uint8_t *>(g->d_product);
-    std::vector<uint8_t> host(off_tiles, 0);                 // (the status words start at 0)
-    for (size_t a = 0; a < n_args; a++) {
-        const hsw::ProductArg pa{static_cast<const uint4 *>(args->d_inputs[a]), spread ? static_cast<const uint4 *>(args->d_inputs_spread[a]) : nullptr,
-                                 static_cast<const uint4 *>(args->d_permuted_inputs[a]), static_cast<const uint4 *>(args->d_permuted_tables[a]),
-                                 static_cast<uint4 *>(args->d_products[a]), (uint32_t)(args->input_rows ? args->input_rows[a] : u),
-                                 (uint32_t)(spread ? a / ncols : a)};
-        std::memcpy(host.data() + off_args + a * sizeof pa, &pa, sizeof pa);
-    }
-    std::memcpy(host.data() + off_ch, ch.data(), ch.size() * sizeof(hsw::ProductChallenges));
+    const int grc = g->scratch.reserve(st.bytes);
+    if (grc != HSW_OK) return grc;
+    void *d = g->scratch.d;
     hsw::ProductParams p{};
-    p.args = reinterpret_cast<const hsw::ProductArg *>(d + off_args);
-    p.ch = reinterpret_cast<const hsw::ProductChallenges *>(d + off_ch);
+    p.args = hsw::at<const hsw::ProductArg>(d, off_args);
+    p.ch = hsw::at<const hsw::ProductChallenges>(d, off_ch);
     p.n_args = (uint32_t)n_args; p.n_tiles = (uint32_t)n_tiles;
     p.T = (uint32_t)T; p.u = (uint32_t)u;
     p.kind = !spread ? hsw::PERMUTED_VALUE_RANGE
                      : args->flags & HSW_PERMUTED_THETA_ON_SPREAD ? hsw::PERMUTED_VALUE_THETA_ON_SPREAD : hsw::PERMUTED_VALUE_SPREAD;
-    p.tiles = reinterpret_cast<hsw::PFe *>(d + off_tiles);
-    p.status = reinterpret_cast<uint32_t *>(d);
+    p.tiles = hsw::at<hsw::PFe>(d, off_tiles);
+    p.status = hsw::at<uint32_t>(d, 0);
     const hipStream_t stream = es.stream;
-    Events ev;
-    hipError_t he = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = ev.record(stream);
+    hsw::Events ev;
+    hipError_t he = hsw::upload(st, d, stream, ev);
     if (he == hipSuccess) he = hsw::launch_product_tiles(p, mont, stream);
     if (he == hipSuccess) he = ev.record(stream);
     if (he == hipSuccess) he = hsw::launch_product_scan(p, stream);
@@ -143,12 +107,9 @@ extern "C" int hsw_gadget_lookup_product(hsw_gadget *g, const hsw_lookup_product
     if (he == hipSuccess) he = hsw::launch_product_write(p, mont, stream);
     if (he == hipSuccess) he = ev.record(stream);
     std::vector<uint32_t> status(n_args, 0);
-    if (he == hipSuccess) he = hipMemcpyAsync(status.data(), d, n_args * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    float ms[3] = {0, 0, 0};
-    for (size_t i = 0; he == hipSuccess && i < 3; i++) he = hipEventElapsedTime(&ms[i], ev.ev[i], ev.ev[i + 1]);
-    e->timed = false;
-    if (he != hipSuccess) return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+    std::vector<float> ms;
+    const int frc = hsw::finish(e, he, stream, ev, d, status.data(), n_args * sizeof(uint32_t), ms);
+    if (frc != HSW_OK) return frc;
     report->tiles_ms = ms[0]; report->scan_ms = ms[1]; report->write_ms = ms[2];
     report->kernel_ms = ms[0] + ms[1] + ms[2];
     report->arguments = n_args;

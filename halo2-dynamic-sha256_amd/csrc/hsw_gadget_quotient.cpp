@@ -3,10 +3,9 @@
 // staged as hsw_quotient_value.hpp takes them (rotations as row offsets, coefficients with their R factors, t_inv by
 // fr_inv), the proofs cut into batches whose accumulators fit the scratch, then the launches of hsw_quotient.hip batch
 // by batch.  A translation unit of its own: only the entry point below refers to those kernels.
-#include "hsw_gadget_launch.hpp"
+#include "hsw_gadget_call.hpp"
 
 #include <algorithm>
-#include <cstdio>
 #include <cstring>
 
 #include "hsw_nounwind.hpp"
@@ -15,19 +14,12 @@
 
 namespace {
 
-using hsw::align256;
-using hsw::Events;
+using hsw::fail_at;
 using hsw::Interval;
 using hsw::load_below_p;
 using hsw::PFe;
 
 const size_t QUOTIENT_GRID_Y = 65535;                          // blockIdx.y
-
-int fail_at(hsw_engine *e, const char *kind, size_t i, const char *what) {
-    char buf[200];
-    std::snprintf(buf, sizeof buf, "%s %zu: %s", kind, i, what);
-    return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, buf);
-}
 
 // offsets[0 .. n] ascending from 0 to `end`
 bool offsets_ok(const uint32_t *off, size_t n, size_t end) {
@@ -39,16 +31,6 @@ bool offsets_ok(const uint32_t *off, size_t n, size_t end) {
 
 // the kinds of columns a call reads, for the overlap message
 const char *const KIND[] = {"column", "fixed column", "l0", "l_last", "l_active", "sigma", "permutation product", "permuted input", "permuted table", "lookup product"};
-
-struct Staging {                                    // the host image of the tables, and where each lies
-    std::vector<uint8_t> host;
-    size_t add(const void *src, size_t bytes) {
-        const size_t at = host.size();
-        host.resize(align256(at + std::max<size_t>(bytes, 1)), 0);
-        if (src && bytes) std::memcpy(host.data() + at, src, bytes);
-        return at;
-    }
-};
 
 }  // namespace
 
@@ -92,11 +74,11 @@ extern "C" int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_
         if (!offsets_ok(ga.gate_first_term, ga.n_gates, ga.n_terms)) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "gate_first_term is not ascending from 0 to n_terms");
         if (!offsets_ok(ga.term_first_factor, ga.n_terms, ga.n_factors)) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "term_first_factor is not ascending from 0 to n_factors");
         for (size_t t = 0; t < ga.n_terms; t++)
-            if (ga.term_first_factor[t + 1] - ga.term_first_factor[t] > HSW_QUOTIENT_MAX_FACTORS) return fail_at(e, "term", t, "more than HSW_QUOTIENT_MAX_FACTORS factors");
+            if (ga.term_first_factor[t + 1] - ga.term_first_factor[t] > HSW_QUOTIENT_MAX_FACTORS) return fail_at(e, HSW_ERR_INVALID_ARG, "term", t, "more than HSW_QUOTIENT_MAX_FACTORS factors");
         for (size_t f = 0; f < ga.n_factors; f++) {
-            if (ga.factor_column[f] >= width) return fail_at(e, "factor", f, "its column index is out of range");
+            if (ga.factor_column[f] >= width) return fail_at(e, HSW_ERR_INVALID_ARG, "factor", f, "its column index is out of range");
             const int64_t r = ga.factor_rotation[f];
-            if (r <= -(int64_t)n || r >= (int64_t)n) return fail_at(e, "factor", f, "a rotation of 2^log_rows rows or more");
+            if (r <= -(int64_t)n || r >= (int64_t)n) return fail_at(e, HSW_ERR_INVALID_ARG, "factor", f, "a rotation of 2^log_rows rows or more");
             factor_offset[f] = (uint32_t)(((uint64_t)(r + (int64_t)n) << ext_log) & (N - 1));
         }
     } else if (ga.n_terms || ga.n_factors) {
@@ -110,19 +92,19 @@ extern "C" int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_
         if (!a.delta) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "delta is NULL");
         S = (n_perm + L - 1) / L;
         for (size_t j = 0; j < n_perm; j++)
-            if (a.perm_columns[j] >= width) return fail_at(e, "permutation column", j, "its column index is out of range");
+            if (a.perm_columns[j] >= width) return fail_at(e, HSW_ERR_INVALID_ARG, "permutation column", j, "its column index is out of range");
     }
     if (n_lk) {
         if (!lk.first_input || !lk.inputs || !lk.first_table || !lk.tables || !lk.d_permuted_inputs || !lk.d_permuted_tables || !lk.d_products || !lk.thetas)
             return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "an array of the lookups is NULL");
         if (lk.first_input[0] != 0 || lk.first_table[0] != 0) return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, "first_input[0] and first_table[0] are 0");
         for (size_t l = 0; l < n_lk; l++) {
-            if (lk.first_input[l + 1] <= lk.first_input[l]) return fail_at(e, "lookup", l, "no input column (first_input must increase)");
-            if (lk.first_table[l + 1] <= lk.first_table[l]) return fail_at(e, "lookup", l, "no table column (first_table must increase)");
+            if (lk.first_input[l + 1] <= lk.first_input[l]) return fail_at(e, HSW_ERR_INVALID_ARG, "lookup", l, "no input column (first_input must increase)");
+            if (lk.first_table[l + 1] <= lk.first_table[l]) return fail_at(e, HSW_ERR_INVALID_ARG, "lookup", l, "no table column (first_table must increase)");
             for (uint32_t k = lk.first_input[l]; k < lk.first_input[l + 1]; k++)
-                if (lk.inputs[k] >= width) return fail_at(e, "lookup", l, "an input column index out of range");
+                if (lk.inputs[k] >= width) return fail_at(e, HSW_ERR_INVALID_ARG, "lookup", l, "an input column index out of range");
             for (uint32_t k = lk.first_table[l]; k < lk.first_table[l + 1]; k++)
-                if (lk.tables[k] >= width) return fail_at(e, "lookup", l, "a table column index out of range");
+                if (lk.tables[k] >= width) return fail_at(e, HSW_ERR_INVALID_ARG, "lookup", l, "a table column index out of range");
         }
     }
     // ---- the pointers: present, aligned, and no d_h over anything read or over another d_h ----
@@ -141,19 +123,17 @@ extern "C" int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_
     for (size_t i = 0; i < n_perm; i++) reads(a.d_sigmas[i], 5, i);
     for (size_t i = 0; i < (n_perm ? K * S : 0); i++) reads(a.d_perm_products[i], 6, i);
     for (size_t i = 0; i < K * n_lk; i++) { reads(lk.d_permuted_inputs[i], 7, i); reads(lk.d_permuted_tables[i], 8, i); reads(lk.d_products[i], 9, i); }
-    if (bad_ptr) return fail_at(e, KIND[bad_kind], bad_index, "a pointer that is NULL or not 16-byte aligned");
+    if (bad_ptr) return fail_at(e, HSW_ERR_INVALID_ARG, KIND[bad_kind], bad_index, "a pointer that is NULL or not 16-byte aligned");
     for (size_t k = 0; k < K; k++) {
         const uintptr_t x = reinterpret_cast<uintptr_t>(a.d_h[k]);
-        if (!x || (x & 15u)) return fail_at(e, "proof", k, "a d_h pointer that is NULL or not 16-byte aligned");
+        if (!x || (x & 15u)) return fail_at(e, HSW_ERR_INVALID_ARG, "proof", k, "a d_h pointer that is NULL or not 16-byte aligned");
         iv.push_back(Interval{x, x + col_bytes, k, true, 0});
     }
     {
         Interval writer{}, with{};
         if (hsw::output_overlaps(iv, &writer, &with)) {
-            char buf[200];
-            if (with.out) std::snprintf(buf, sizeof buf, "proof %zu: its d_h overlaps the d_h of proof %zu", writer.index, with.index);
-            else std::snprintf(buf, sizeof buf, "proof %zu: its d_h overlaps %s %zu", writer.index, KIND[with.other], with.index);
-            return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, buf);
+            const std::string what = std::string("its d_h overlaps ") + (with.out ? "the d_h of proof" : KIND[with.other]) + " " + std::to_string(with.index);
+            return fail_at(e, HSW_ERR_INVALID_ARG, "proof", writer.index, what.c_str());
         }
     }
     bool mont = false;
@@ -162,7 +142,7 @@ extern "C" int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_
     // ---- coefficients, challenges and constants ----
     std::vector<PFe> coeff(ga.n_terms);
     for (size_t t = 0; t < ga.n_terms; t++) {
-        if (!load_below_p(coeff[t], static_cast<const uint8_t *>(ga.term_coeffs) + 32 * t)) return fail_at(e, "term", t, "a coefficient whose stored limbs are not below p");
+        if (!load_below_p(coeff[t], static_cast<const uint8_t *>(ga.term_coeffs) + 32 * t)) return fail_at(e, HSW_ERR_INVALID_ARG, "term", t, "a coefficient whose stored limbs are not below p");
         coeff[t] = hsw::quotient_coeff(coeff[t], ga.term_first_factor[t + 1] - ga.term_first_factor[t], mont);
     }
     PFe w, zeta, delta = hsw::fr_zero();
@@ -180,13 +160,13 @@ extern "C" int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_
         hsw::QuotientProof &pr = proofs[k];
         std::memset(&pr, 0, sizeof pr);
         PFe y, theta = hsw::fr_zero();
-        if (!load_below_p(y, static_cast<const uint8_t *>(a.ys) + 32 * k)) return fail_at(e, "proof", k, "a y whose stored limbs are not below p");
-        if (n_lk && !load_below_p(theta, static_cast<const uint8_t *>(lk.thetas) + 32 * k)) return fail_at(e, "proof", k, "a theta whose stored limbs are not below p");
+        if (!load_below_p(y, static_cast<const uint8_t *>(a.ys) + 32 * k)) return fail_at(e, HSW_ERR_INVALID_ARG, "proof", k, "a y whose stored limbs are not below p");
+        if (n_lk && !load_below_p(theta, static_cast<const uint8_t *>(lk.thetas) + 32 * k)) return fail_at(e, HSW_ERR_INVALID_ARG, "proof", k, "a theta whose stored limbs are not below p");
         pr.y = hsw::quotient_to_mont(y, mont);
         pr.theta = hsw::quotient_to_mont(theta, mont);
         if (fixed_family) {
-            if (!load_below_p(pr.beta, static_cast<const uint8_t *>(a.betas) + 32 * k)) return fail_at(e, "proof", k, "a beta whose stored limbs are not below p");
-            if (!load_below_p(pr.gamma, static_cast<const uint8_t *>(a.gammas) + 32 * k)) return fail_at(e, "proof", k, "a gamma whose stored limbs are not below p");
+            if (!load_below_p(pr.beta, static_cast<const uint8_t *>(a.betas) + 32 * k)) return fail_at(e, HSW_ERR_INVALID_ARG, "proof", k, "a beta whose stored limbs are not below p");
+            if (!load_below_p(pr.gamma, static_cast<const uint8_t *>(a.gammas) + 32 * k)) return fail_at(e, HSW_ERR_INVALID_ARG, "proof", k, "a gamma whose stored limbs are not below p");
             pr.beta_mul = hsw::product_theta_mul(pr.beta, mont);
         }
         PFe bd = hsw::fr_mont_mul(pr.beta, zeta_mont);           // beta zeta in cell form, then times delta per column
@@ -207,8 +187,8 @@ extern "C" int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_
     const size_t per_batch = std::min(std::min(K, QUOTIENT_GRID_Y), std::max<size_t>(1, e->quotient_scratch / v_bytes));
     const size_t scratch_bytes = per_batch * v_bytes;
     // ---- device staging: [status words][tables ...][the accumulators of a batch] ----
-    Staging st;
-    st.add(nullptr, K * sizeof(uint32_t));                      // (the status words start at 0)
+    hsw::Staging st;
+    st.zeroed(K * sizeof(uint32_t));                      // (the status words start at 0)
     const size_t o_cols = st.add(a.d_columns, K * m * sizeof(void *)), o_fixed = st.add(a.d_fixed, F * sizeof(void *));
     const size_t o_gft = st.add(ga.gate_first_term, ga.n_gates ? (ga.n_gates + 1) * 4 : 0), o_tff = st.add(ga.term_first_factor, ga.n_gates ? (ga.n_terms + 1) * 4 : 0);
     const size_t o_fc = st.add(ga.factor_column, ga.n_factors * 4), o_fo = st.add(factor_offset.data(), ga.n_factors * 4);
@@ -222,43 +202,36 @@ extern "C" int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_
     const size_t o_lz = st.add(lk.d_products, K * n_lk * sizeof(void *));
     const size_t o_pr = st.add(proofs.data(), K * sizeof(hsw::QuotientProof)), o_ti = st.add(t_inv.data(), t_inv.size() * sizeof(PFe));
     const size_t o_h = st.add(a.d_h, K * sizeof(void *)), o_k = st.add(&kc, sizeof kc);
-    const size_t o_v = st.host.size();
+    const size_t o_v = st.work(scratch_bytes);
     EngineScope es(e);
     if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
-    if (o_v + scratch_bytes > g->quotient_cap) {                 // every earlier call has been waited for, so nothing reads the old block:
-        (void)hipFree(g->d_quotient);                            // it goes first, and the peak is the new block alone, not old + new
-        g->d_quotient = nullptr; g->quotient_cap = 0;
-        void *p = nullptr;
-        const hipError_t he = hipMalloc(&p, o_v + scratch_bytes);
-        if (he != hipSuccess) return hsw::hip_status(he);
-        g->d_quotient = p; g->quotient_cap = o_v + scratch_bytes;
-    }
-    uint8_t *d = static_cast<uint8_t *>(g->d_quotient);
+    const int grc = g->scratch.reserve(st.bytes);
+    if (grc != HSW_OK) return grc;
+    void *d = g->scratch.d;
     hsw::QuotientParams p{};
     p.N = (uint32_t)N; p.mask = (uint32_t)(N - 1); p.ext = 1u << ext_log; p.u_off = (uint32_t)((a.usable_rows << ext_log) & (N - 1));
     p.m = (uint32_t)m; p.F = (uint32_t)F;
-    p.cols = reinterpret_cast<const PFe *const *>(d + o_cols); p.fixed = reinterpret_cast<const PFe *const *>(d + o_fixed);
+    p.cols = hsw::at<const PFe *const>(d, o_cols); p.fixed = hsw::at<const PFe *const>(d, o_fixed);
     p.l0 = static_cast<const PFe *>(a.d_l0); p.l_last = static_cast<const PFe *>(a.d_l_last); p.l_active = static_cast<const PFe *>(a.d_l_active);
     p.n_gates = (uint32_t)ga.n_gates; p.n_perm = (uint32_t)n_perm; p.L = L; p.S = (uint32_t)S;
-    p.gate_first_term = reinterpret_cast<const uint32_t *>(d + o_gft); p.term_first_factor = reinterpret_cast<const uint32_t *>(d + o_tff);
-    p.factor_column = reinterpret_cast<const uint32_t *>(d + o_fc); p.factor_offset = reinterpret_cast<const uint32_t *>(d + o_fo);
-    p.term_coeff = reinterpret_cast<const PFe *>(d + o_coeff);
-    p.perm_columns = reinterpret_cast<const uint32_t *>(d + o_pc); p.sigmas = reinterpret_cast<const PFe *const *>(d + o_sig);
-    p.perm_z = reinterpret_cast<const PFe *const *>(d + o_pz); p.beta_delta = reinterpret_cast<const PFe *>(d + o_bd);
-    p.powers = reinterpret_cast<const hsw::PermutationPowers *>(d + o_pw);
+    p.gate_first_term = hsw::at<const uint32_t>(d, o_gft); p.term_first_factor = hsw::at<const uint32_t>(d, o_tff);
+    p.factor_column = hsw::at<const uint32_t>(d, o_fc); p.factor_offset = hsw::at<const uint32_t>(d, o_fo);
+    p.term_coeff = hsw::at<const PFe>(d, o_coeff);
+    p.perm_columns = hsw::at<const uint32_t>(d, o_pc); p.sigmas = hsw::at<const PFe *const>(d, o_sig);
+    p.perm_z = hsw::at<const PFe *const>(d, o_pz); p.beta_delta = hsw::at<const PFe>(d, o_bd);
+    p.powers = hsw::at<const hsw::PermutationPowers>(d, o_pw);
     p.n_lookups = (uint32_t)n_lk;
-    p.first_input = reinterpret_cast<const uint32_t *>(d + o_fi); p.inputs = reinterpret_cast<const uint32_t *>(d + o_in);
-    p.first_table = reinterpret_cast<const uint32_t *>(d + o_ft); p.tables = reinterpret_cast<const uint32_t *>(d + o_tb);
-    p.lk_a = reinterpret_cast<const PFe *const *>(d + o_la); p.lk_s = reinterpret_cast<const PFe *const *>(d + o_ls); p.lk_z = reinterpret_cast<const PFe *const *>(d + o_lz);
-    p.proofs = reinterpret_cast<const hsw::QuotientProof *>(d + o_pr); p.t_inv = reinterpret_cast<const PFe *>(d + o_ti);
-    p.h = reinterpret_cast<PFe *const *>(d + o_h); p.V = reinterpret_cast<PFe *>(d + o_v);
-    p.status = reinterpret_cast<uint32_t *>(d); p.k = reinterpret_cast<const hsw::QuotientConstants *>(d + o_k);
+    p.first_input = hsw::at<const uint32_t>(d, o_fi); p.inputs = hsw::at<const uint32_t>(d, o_in);
+    p.first_table = hsw::at<const uint32_t>(d, o_ft); p.tables = hsw::at<const uint32_t>(d, o_tb);
+    p.lk_a = hsw::at<const PFe *const>(d, o_la); p.lk_s = hsw::at<const PFe *const>(d, o_ls); p.lk_z = hsw::at<const PFe *const>(d, o_lz);
+    p.proofs = hsw::at<const hsw::QuotientProof>(d, o_pr); p.t_inv = hsw::at<const PFe>(d, o_ti);
+    p.h = hsw::at<PFe *const>(d, o_h); p.V = hsw::at<PFe>(d, o_v);
+    p.status = hsw::at<uint32_t>(d, 0); p.k = hsw::at<const hsw::QuotientConstants>(d, o_k);
     const hipStream_t stream = es.stream;
     // the families of every batch, then its finish: an event at every boundary, summed per family afterwards
-    Events ev;
+    hsw::Events ev;
     std::vector<int> stage;                                      // what ran between event i and i + 1: 0 gates, 1 permutation, 2 lookups, 3 finish
-    hipError_t he = hipMemcpyAsync(d, st.host.data(), st.host.size(), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = ev.record(stream);
+    hipError_t he = hsw::upload(st, d, stream, ev);
     uint32_t launches = 0;
     for (size_t k0 = 0; he == hipSuccess && k0 < K; k0 += per_batch) {
         const uint32_t nb = (uint32_t)std::min(per_batch, K - k0), base = (uint32_t)k0;
@@ -278,16 +251,11 @@ extern "C" int hsw_gadget_quotient(hsw_gadget *g, const hsw_quotient *args, hsw_
         }
     }
     std::vector<uint32_t> status(K, 0);
-    if (he == hipSuccess) he = hipMemcpyAsync(status.data(), d, K * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    std::vector<float> between;
+    const int frc = hsw::finish(e, he, stream, ev, d, status.data(), K * sizeof(uint32_t), between);
+    if (frc != HSW_OK) return frc;
     float ms[4] = {0, 0, 0, 0};
-    for (size_t i = 0; he == hipSuccess && i < stage.size(); i++) {
-        float x = 0;
-        he = hipEventElapsedTime(&x, ev.ev[i], ev.ev[i + 1]);
-        ms[stage[i]] += x;
-    }
-    e->timed = false;
-    if (he != hipSuccess) return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+    for (size_t i = 0; i < stage.size(); i++) ms[stage[i]] += between[i];
     for (size_t k = 0; k < K; k++) {
         status[k] &= hsw::QUOTIENT_CELL_NOT_BELOW_P;
         if (status[k]) { if (!report->refused_proofs++) report->first_refused = k; }

@@ -5,11 +5,10 @@
 // Both entry points are one routine: the second call is the first over ONE set that holds every listed column and h.
 // The scratch is not cut into batches: the write launch needs every set's c at once.  A translation unit of its own:
 // only the two entry points below refer to those kernels.
-#include "hsw_gadget_launch.hpp"
+#include "hsw_gadget_call.hpp"
 
 #include <algorithm>
 #include <array>
-#include <cstdio>
 #include <cstring>
 
 #include "hsw_nounwind.hpp"
@@ -18,28 +17,12 @@
 namespace {
 
 using hsw::align256;
-using hsw::Events;
+using hsw::fail_at;
 using hsw::Interval;
 using hsw::load_below_p;
 using hsw::PFe;
 
 int fail(hsw_engine *e, const char *what) { return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, what); }
-int fail_at(hsw_engine *e, const char *kind, size_t i, const char *what) {
-    char buf[200];
-    std::snprintf(buf, sizeof buf, "%s %zu: %s", kind, i, what);
-    return hsw_engine_fail(e, HSW_ERR_INVALID_ARG, buf);
-}
-
-int grow(hsw_gadget *g, size_t bytes) {                        // (every earlier call has been waited for: nothing reads the old one)
-    if (bytes <= g->shplonk_cap) return HSW_OK;
-    (void)hipFree(g->d_shplonk);                               // it goes first: the peak is the new block alone, not old + new
-    g->d_shplonk = nullptr; g->shplonk_cap = 0;
-    void *p = nullptr;
-    const hipError_t he = hipMalloc(&p, bytes);
-    if (he != hipSuccess) return hsw_engine_fail(g->ctx->engine, hsw::hip_status(he), "the scratch of the SHPLONK opening does not fit the device");
-    g->d_shplonk = p; g->shplonk_cap = bytes;
-    return HSW_OK;
-}
 
 int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *report, bool open) {
     if (!g || !args || !report) return HSW_ERR_INVALID_ARG;
@@ -56,9 +39,9 @@ int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *rep
     if (n >= 0xFFFFFFFFull) return fail(e, "n_columns is below 2^32 - 1");
     if (!args->d_columns) return fail(e, "the column pointer array is NULL");
     for (size_t b = 0; b < n; b++) {
-        if (args->input_rows && args->input_rows[b] > rows) return fail_at(e, "column", b, "input_rows above rows");
+        if (args->input_rows && args->input_rows[b] > rows) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "input_rows above rows");
         const uintptr_t in = reinterpret_cast<uintptr_t>(args->d_columns[b]);
-        if (!in || (in & 15u)) return fail_at(e, "column", b, "a pointer that is NULL or not 16-byte aligned");
+        if (!in || (in & 15u)) return fail_at(e, HSW_ERR_INVALID_ARG, "column", b, "a pointer that is NULL or not 16-byte aligned");
     }
     bool mont = false;
     const int rc = hsw::pass_cells(c, &mont);
@@ -79,7 +62,7 @@ int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *rep
     }
     std::vector<PFe> z(n_points);
     for (size_t t = 0; t < n_points; t++)
-        if (!load_below_p(z[t], static_cast<const uint8_t *>(args->points) + 32 * t)) return fail_at(e, "point", t, "its stored limbs are not below p");
+        if (!load_below_p(z[t], static_cast<const uint8_t *>(args->points) + 32 * t)) return fail_at(e, HSW_ERR_INVALID_ARG, "point", t, "its stored limbs are not below p");
     PFe y, v, u = hsw::fr_zero();
     if (!load_below_p(y, args->y)) return fail(e, "y: its stored limbs are not below p");
     if (!load_below_p(v, args->v)) return fail(e, "v: its stored limbs are not below p");
@@ -89,26 +72,26 @@ int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *rep
     std::vector<uint8_t> col_used(n, 0), point_used(n_points, 0);
     for (size_t i = 0; i < n_sets; i++) {
         const uint64_t f0 = args->set_first[i], f1 = args->set_first[i + 1], p0 = args->set_point_first[i], p1 = args->set_point_first[i + 1];
-        if (f1 <= f0) return fail_at(e, "set", i, "no column (set_first must increase)");
-        if (p1 <= p0) return fail_at(e, "set", i, "no point (set_point_first must increase)");
-        if (f1 - f0 > n) return fail_at(e, "set", i, "a column listed twice");
-        if (p1 - p0 > hsw::SHPLONK_MAX_SET_POINTS) return fail_at(e, "set", i, "more than HSW_SHPLONK_MAX_SET_POINTS points");
+        if (f1 <= f0) return fail_at(e, HSW_ERR_INVALID_ARG, "set", i, "no column (set_first must increase)");
+        if (p1 <= p0) return fail_at(e, HSW_ERR_INVALID_ARG, "set", i, "no point (set_point_first must increase)");
+        if (f1 - f0 > n) return fail_at(e, HSW_ERR_INVALID_ARG, "set", i, "a column listed twice");
+        if (p1 - p0 > hsw::SHPLONK_MAX_SET_POINTS) return fail_at(e, HSW_ERR_INVALID_ARG, "set", i, "more than HSW_SHPLONK_MAX_SET_POINTS points");
         for (uint64_t k = f0; k < f1; k++) {
             const uint32_t b = args->set_columns[k];
-            if (b >= n) return fail_at(e, "set", i, "a column index out of range");
-            if (col_used[b]) return fail_at(e, "set", i, "a column listed twice");
+            if (b >= n) return fail_at(e, HSW_ERR_INVALID_ARG, "set", i, "a column index out of range");
+            if (col_used[b]) return fail_at(e, HSW_ERR_INVALID_ARG, "set", i, "a column listed twice");
             col_used[b] = 1;
         }
         for (uint64_t k = p0; k < p1; k++) {
             const uint32_t t = args->set_points[k];
-            if (t >= n_points) return fail_at(e, "set", i, "a point index out of range");
+            if (t >= n_points) return fail_at(e, HSW_ERR_INVALID_ARG, "set", i, "a point index out of range");
             for (uint64_t l = p0; l < k; l++)
-                if (args->set_points[l] == t) return fail_at(e, "set", i, "a point index twice");
+                if (args->set_points[l] == t) return fail_at(e, HSW_ERR_INVALID_ARG, "set", i, "a point index twice");
             point_used[t] = 1;
         }
     }
     for (size_t t = 0; t < n_points; t++)
-        if (!point_used[t]) return fail_at(e, "point", t, "no set uses it");
+        if (!point_used[t]) return fail_at(e, HSW_ERR_INVALID_ARG, "point", t, "no set uses it");
     {   // T is a set: no two entries equal in value (one representation: equal values are equal limbs)
         std::vector<std::pair<std::array<uint32_t, 8>, size_t>> sorted(n_points);
         for (size_t t = 0; t < n_points; t++) {
@@ -117,7 +100,7 @@ int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *rep
         }
         std::sort(sorted.begin(), sorted.end());
         for (size_t t = 1; t < n_points; t++)
-            if (sorted[t].first == sorted[t - 1].first) return fail_at(e, "point", sorted[t].second, "equal in value to another point");
+            if (sorted[t].first == sorted[t - 1].first) return fail_at(e, HSW_ERR_INVALID_ARG, "point", sorted[t].second, "equal in value to another point");
     }
     {   // d_out may overlap neither the `rows` cells of a column (read or not) nor h
         std::vector<Interval> iv;
@@ -131,7 +114,7 @@ int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *rep
         Interval writer{}, with{};
         if (hsw::output_overlaps(iv, &writer, &with)) {
             if (open && with.index == n) return fail(e, "d_out overlaps d_h");
-            return fail_at(e, "column", with.index, "d_out overlaps it");
+            return fail_at(e, HSW_ERR_INVALID_ARG, "column", with.index, "d_out overlaps it");
         }
     }
     // every constant in Montgomery form
@@ -188,62 +171,54 @@ int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *rep
     }
     // device staging: [the status word][the scan's s[0] per item][columns][set columns][their weights][sets][items]
     // [their weights][points][the tiles' sums][a cell per thread and item][c of every set of two columns or more]
-    const size_t cell = sizeof(PFe);
-    const size_t off_evals = 256, off_cols = align256(off_evals + k_items * cell), off_refs = align256(off_cols + k_cols * sizeof(hsw::OpenColumn));
-    const size_t off_cw = align256(off_refs + k_refs * sizeof(uint32_t)), off_sets = align256(off_cw + k_refs * cell);
-    const size_t off_items = align256(off_sets + k_sets * sizeof(hsw::ShplonkSet)), off_iw = align256(off_items + k_items * sizeof(hsw::OpenItem));
-    const size_t off_points = align256(off_iw + k_items * cell), off_tiles = align256(off_points + k_points * sizeof(hsw::OpenPoint));
-    const size_t off_seeds = align256(off_tiles + k_items * (size_t)geo.n_tiles * cell), off_c = align256(off_seeds + k_items * (size_t)geo.seeds * cell);
-    const size_t c_bytes = align256((size_t)rows * cell);
-    size_t total = off_c;
-    EngineScope es(e);
-    if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
+    const size_t cell = sizeof(PFe), c_bytes = align256((size_t)rows * cell);
+    hsw::Staging st;
+    st.zeroed(sizeof(uint32_t));
+    const size_t off_evals = st.zeroed(k_items * cell), off_cols = st.zeroed(k_cols * sizeof(hsw::OpenColumn));
+    const size_t off_refs = st.add(refs.data(), k_refs * sizeof(uint32_t)), off_cw = st.add(col_weights.data(), k_refs * cell);
+    const size_t off_sets = st.zeroed(k_sets * sizeof(hsw::ShplonkSet)), off_items = st.add(items.data(), k_items * sizeof(hsw::OpenItem));
+    const size_t off_iw = st.add(item_weights.data(), k_items * cell), off_points = st.zeroed(k_points * sizeof(hsw::OpenPoint));
+    const size_t off_tiles = st.work(k_items * (size_t)geo.n_tiles * cell), off_seeds = st.work(k_items * (size_t)geo.seeds * cell);
+    size_t off_c = st.work(0);
     for (size_t i = 0; i < k_sets; i++)
-        if (sets[i].m > 1) total += c_bytes;
-    const int grc = grow(g, total);
-    if (grc != HSW_OK) return grc;
-    uint8_t *d = static_cast<uint8_t *>(g->d_shplonk);
-    {
-        size_t off = off_c;
-        for (size_t i = 0; i < k_sets; i++) {
-            if (sets[i].m > 1) {
-                sets[i].c = reinterpret_cast<uint4 *>(d + off);
-                sets[i].src = sets[i].c;
-                off += c_bytes;
-            } else {                                             // one column: it is its own c
-                const uint32_t b = refs[sets[i].first];
-                sets[i].src = static_cast<const uint4 *>(args->d_columns[b]);
-                sets[i].src_rows = (uint32_t)(args->input_rows ? args->input_rows[b] : rows);
-            }
-        }
-    }
-    std::vector<uint8_t> host(off_tiles, 0);                   // (the status word starts at 0)
+        if (sets[i].m > 1) st.work(c_bytes);
+    const size_t total = st.bytes;
     for (size_t b = 0; b < k_cols; b++) {
-        hsw::OpenColumn oc{};
+        hsw::OpenColumn &oc = st.image<hsw::OpenColumn>(off_cols)[b];
         oc.cells = static_cast<const uint4 *>(b < n ? args->d_columns[b] : args->d_h);
         oc.rows = (uint32_t)(b < n && args->input_rows ? args->input_rows[b] : rows);
-        std::memcpy(host.data() + off_cols + b * sizeof oc, &oc, sizeof oc);
     }
-    std::memcpy(host.data() + off_refs, refs.data(), k_refs * sizeof(uint32_t));
-    std::memcpy(host.data() + off_cw, col_weights.data(), k_refs * cell);
-    std::memcpy(host.data() + off_sets, sets.data(), k_sets * sizeof(hsw::ShplonkSet));
-    std::memcpy(host.data() + off_items, items.data(), k_items * sizeof(hsw::OpenItem));
-    std::memcpy(host.data() + off_iw, item_weights.data(), k_items * cell);
-    for (size_t t = 0; t < k_points; t++)
-        hsw::open_stage_point(open ? um : zm[t], geo, *reinterpret_cast<hsw::OpenPoint *>(host.data() + off_points + t * sizeof(hsw::OpenPoint)));
+    for (size_t t = 0; t < k_points; t++) hsw::open_stage_point(open ? um : zm[t], geo, st.image<hsw::OpenPoint>(off_points)[t]);
+    EngineScope es(e);
+    if (!es.ok) return hsw_engine_fail(e, HSW_ERR_NO_DEVICE, "hipSetDevice failed");
+    const int grc = g->scratch.reserve(total);
+    if (grc != HSW_OK) return hsw_engine_fail(e, grc, "the scratch of the SHPLONK opening does not fit the device");
+    void *d = g->scratch.d;
+    for (size_t i = 0; i < k_sets; i++) {
+        if (sets[i].m > 1) {
+            sets[i].c = hsw::at<uint4>(d, off_c);
+            sets[i].src = sets[i].c;
+            off_c += c_bytes;
+        } else {                                                 // one column: it is its own c
+            const uint32_t b = refs[sets[i].first];
+            sets[i].src = static_cast<const uint4 *>(args->d_columns[b]);
+            sets[i].src_rows = (uint32_t)(args->input_rows ? args->input_rows[b] : rows);
+        }
+    }
+    std::memcpy(st.image<hsw::ShplonkSet>(off_sets), sets.data(), k_sets * sizeof(hsw::ShplonkSet));
     hsw::ShplonkParams p{};
     p.geo = geo;
-    p.cols = reinterpret_cast<const hsw::OpenColumn *>(d + off_cols);
-    p.set_cols = reinterpret_cast<const uint32_t *>(d + off_refs);
-    p.col_weights = reinterpret_cast<const PFe *>(d + off_cw);
-    p.sets = reinterpret_cast<const hsw::ShplonkSet *>(d + off_sets);
-    p.items = reinterpret_cast<const hsw::OpenItem *>(d + off_items);
-    p.item_weights = reinterpret_cast<const PFe *>(d + off_iw);
-    p.points = reinterpret_cast<const hsw::OpenPoint *>(d + off_points);
-    p.tiles = reinterpret_cast<uint4 *>(d + off_tiles);
-    p.seeds = reinterpret_cast<uint4 *>(d + off_seeds);
+    p.cols = hsw::at<const hsw::OpenColumn>(d, off_cols);
+    p.set_cols = hsw::at<const uint32_t>(d, off_refs);
+    p.col_weights = hsw::at<const PFe>(d, off_cw);
+    p.sets = hsw::at<const hsw::ShplonkSet>(d, off_sets);
+    p.items = hsw::at<const hsw::OpenItem>(d, off_items);
+    p.item_weights = hsw::at<const PFe>(d, off_iw);
+    p.points = hsw::at<const hsw::OpenPoint>(d, off_points);
+    p.tiles = hsw::at<uint4>(d, off_tiles);
+    p.seeds = hsw::at<uint4>(d, off_seeds);
     p.out = static_cast<uint4 *>(args->d_out);
-    p.status = reinterpret_cast<uint32_t *>(d);
+    p.status = hsw::at<uint32_t>(d, 0);
     p.n_sets = (uint32_t)k_sets;
     p.unit = open ? 1u : 0u;
     hsw::OpenParams sp{};                                      // the scan of hsw_open.hip over the items
@@ -251,23 +226,19 @@ int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *rep
     sp.items = p.items;
     sp.points = p.points;
     sp.tiles = p.tiles;
-    sp.evals = reinterpret_cast<uint4 *>(d + off_evals);
+    sp.evals = hsw::at<uint4>(d, off_evals);
     sp.status = p.status;
     const hipStream_t stream = es.stream;
-    Events ev;
-    hipError_t he = hipMemcpyAsync(d, host.data(), host.size(), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = ev.record(stream);
+    hsw::Events ev;
+    hipError_t he = hsw::upload(st, d, stream, ev);
     if (he == hipSuccess) he = hsw::launch_shplonk_tiles(p, stream);
     if (he == hipSuccess) he = hsw::launch_open_scan(sp, (uint32_t)k_items, stream);
     if (he == hipSuccess) he = hsw::launch_shplonk_write(p, stream);
     if (he == hipSuccess) he = ev.record(stream);
     uint32_t status = 0;
-    if (he == hipSuccess) he = hipMemcpyAsync(&status, d, sizeof status, hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    float ms = 0;
-    if (he == hipSuccess) he = hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]);
-    e->timed = false;
-    if (he != hipSuccess) return hsw_engine_fail(e, HSW_ERR_HIP, hipGetErrorString(he));
+    std::vector<float> ms;
+    const int frc = hsw::finish(e, he, stream, ev, d, &status, sizeof status, ms);
+    if (frc != HSW_OK) return frc;
     status &= hsw::SHPLONK_CELL_NOT_BELOW_P;
     report->sets = n_sets;
     report->items = n_set_points;
@@ -279,7 +250,7 @@ int shplonk_call(hsw_gadget *g, const hsw_shplonk *args, hsw_shplonk_report *rep
     report->tiles = geo.n_tiles;
     report->thread_rows = hsw::OPEN_ROWS;
     report->launches = 3;
-    report->kernel_ms = ms;
+    report->kernel_ms = ms[0];
     if (args->status) *args->status = status;
     return HSW_OK;
 }

@@ -305,6 +305,11 @@ int hsw_engine_set_option(hsw_engine *e, const char *name, int64_t value) try {
         e->quotient_scratch = (size_t)value;
         return HSW_OK;
     }
+    if (std::strcmp(name, "round_scratch") == 0) {     // hsw_gadget_ntt, _msm, _evaluate, _open: bytes of scratch per group or batch; tests shrink it to reach those loops
+        if (value < 1 || value > ((int64_t)1 << 30)) return set_err(e, HSW_ERR_INVALID_ARG, "round_scratch must be 1 .. 2^30 bytes");
+        e->round_scratch = (size_t)value;
+        return HSW_OK;
+    }
     if (std::strcmp(name, "chunk_blocks") == 0) {      // blocks per launch of a long batch; tests shrink it to reach that loop
         if (value < 1 || value > (1 << 20)) return set_err(e, HSW_ERR_INVALID_ARG, "chunk_blocks must be 1 .. 2^20");
         e->chunk_blocks = (size_t)value;

@@ -62,6 +62,7 @@ struct hsw_engine {
     int lookup_lds = 1;                  // hsw_lookup_counts_kernel: small tables counted in LDS first; 0 = global atomics only
     size_t permuted_scratch = (size_t)256 << 20;   // hsw_gadget_lookup_permuted: the budget of a group's index and value arrays, in bytes
     size_t quotient_scratch = (size_t)1 << 30;     // hsw_gadget_quotient: the accumulators V of a batch of proofs, in bytes (a batch is at least one proof)
+    size_t round_scratch = (size_t)1 << 30;        // hsw_gadget_ntt, _msm, _evaluate and _open: the scratch of a group of columns or a batch, in bytes (at least one column, group or item set)
     hsw::VerifyReport *d_report = nullptr;
     hsw_launch_info last_launch{};       // hsw_last_launch
     void *d_mont_tab = nullptr;          // Em::M32 kernels: Montgomery form of every byte, its spread, and the byte << 8 (24 KiB)

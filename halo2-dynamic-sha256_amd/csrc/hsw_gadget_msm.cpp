@@ -13,7 +13,6 @@
 
 namespace {
 
-const size_t MSM_SCRATCH_BYTES = (size_t)1 << 30;              // the partial buckets of a group of columns
 const size_t MSM_GRID_COLUMNS = 65535;                         // blockIdx.z, blockIdx.y
 
 using hsw::fail_at;
@@ -48,9 +47,10 @@ extern "C" int hsw_gadget_msm(hsw_gadget *g, const hsw_msm *args, hsw_msm_report
     bool mont = false;
     const int prc = hsw::pass_cells(c, &mont);
     if (prc != HSW_OK) return prc;
-    // columns in groups whose partial buckets fit the scratch
+    // columns in groups whose partial buckets fit the scratch (1 GiB, or what the option "round_scratch" lowers it to); the
+    // grid limit cannot be the one that cuts: at one bucket per window a column still takes 24 KB, 65,535 of them above 1 GiB
     const size_t column_bytes = (size_t)hsw::msm_partial_points(plan) * sizeof(hsw::G1);
-    const size_t group = std::min(std::min(n, MSM_GRID_COLUMNS), std::max<size_t>(1, MSM_SCRATCH_BYTES / column_bytes));
+    const size_t group = std::min(std::min(n, MSM_GRID_COLUMNS), std::max<size_t>(1, e->round_scratch / column_bytes));
     const size_t n_groups = (n + group - 1) / group;
     // device staging: [status words][the bases' check][columns][window points][partial buckets of a group]
     const hsw::MsmCheck check0{0u, ~0u};

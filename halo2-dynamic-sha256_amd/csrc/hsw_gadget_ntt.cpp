@@ -13,7 +13,6 @@
 
 namespace {
 
-const size_t NTT_SCRATCH_BYTES = (size_t)1 << 30;              // the points of a group of columns between launches
 const size_t NTT_GRID_COLUMNS = 65535;                         // blockIdx.y
 
 using hsw::fail_at;
@@ -67,10 +66,10 @@ extern "C" int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report
     const uint32_t out_mode = args->shift && (args->flags & HSW_NTT_SHIFT_AFTER) ? hsw::NTT_OUT_TABLE : args->scale ? hsw::NTT_OUT_SCALE : hsw::NTT_OUT_PLAIN;
     const uint32_t n_pass = plan.n_pass;
     const hsw::NttPass pass0 = hsw::ntt_pass(plan, 0), pass_last = hsw::ntt_pass(plan, n_pass - 1);
-    // columns in groups whose points between launches fit the scratch
+    // columns in groups whose points between launches fit the scratch (1 GiB, or what the option "round_scratch" lowers it to)
     const size_t column_bytes = (size_t)N * HSW_CELL_BYTES;
     size_t group = std::min(n, NTT_GRID_COLUMNS);
-    if (n_pass > 1) group = std::min(group, std::max<size_t>(1, NTT_SCRATCH_BYTES / column_bytes));
+    if (n_pass > 1) group = std::min(group, std::max<size_t>(1, e->round_scratch / column_bytes));
     // device staging: [status words][columns][shift's windows][tile table in][tile table out][omega's windows][points]
     const size_t tile = (size_t)1 << hsw::NTT_TILE_LOG;
     hsw::Staging st;

@@ -1,8 +1,8 @@
 // hsw_gadget_open.cpp -- device columns evaluated at points and opened (include/hsw.h, "evaluate device columns at
 // points, and open them"): every refusal decided on the host, the points and challenges brought into Montgomery form
 // and staged with their powers (hsw_open_value.hpp), the groups (or the columns of evaluate) cut into batches whose
-// scratch stays under 1 GiB, then the launches of hsw_open.hip batch by batch.  A translation unit of its own: only the
-// two entry points below refer to those kernels.
+// scratch stays under 1 GiB (the engine option "round_scratch" lowers it), then the launches of hsw_open.hip batch by
+// batch.  A translation unit of its own: only the two entry points below refer to those kernels.
 #include "hsw_gadget_call.hpp"
 
 #include <algorithm>
@@ -13,7 +13,6 @@
 
 namespace {
 
-const size_t OPEN_SCRATCH_BYTES = (size_t)1 << 30;             // the scratch of a batch
 const size_t OPEN_GRID_Y = 65535;                              // blockIdx.y
 
 using hsw::align256;
@@ -92,7 +91,7 @@ extern "C" int hsw_gadget_evaluate(hsw_gadget *g, const hsw_evaluate *args, hsw_
     size_t scratch_bytes = 0, acc = 0;
     for (size_t k = 0; k < cols.size(); k++) {
         const size_t need = cols[k].n_items * item_bytes;
-        if (k > batch_first.back() && (acc + need > OPEN_SCRATCH_BYTES || k - batch_first.back() >= OPEN_GRID_Y)) { batch_first.push_back(k); acc = 0; }
+        if (k > batch_first.back() && (acc + need > e->round_scratch || k - batch_first.back() >= OPEN_GRID_Y)) { batch_first.push_back(k); acc = 0; }
         acc += need;
         scratch_bytes = std::max(scratch_bytes, acc);
     }
@@ -207,7 +206,7 @@ extern "C" int hsw_gadget_open(hsw_gadget *g, const hsw_open *args, hsw_open_rep
     for (size_t k = 0; k < n_groups; k++) {
         const bool folded = args->group_first[k + 1] - args->group_first[k] > 1;
         const size_t need = tile_bytes + seed_bytes + (folded ? c_bytes : 0);
-        if (k > batch_first.back() && (acc + need > OPEN_SCRATCH_BYTES || k - batch_first.back() >= OPEN_GRID_Y)) { batch_first.push_back(k); acc = 0; }
+        if (k > batch_first.back() && (acc + need > e->round_scratch || k - batch_first.back() >= OPEN_GRID_Y)) { batch_first.push_back(k); acc = 0; }
         acc += need;
         scratch_bytes = std::max(scratch_bytes, align256(acc));
     }

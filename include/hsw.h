@@ -1301,7 +1301,8 @@ int hsw_gadget_permutation_product(hsw_gadget *g, const hsw_permutation_product 
  * workgroup holds), else digits of at most max(1, pass_log - 2) bits, because a launch that reads or writes at a stride
  * keeps runs of four cells -- 2 launches up to log_n 16, 3 up to 24, 4 up to 28 by default.  Only a column's last launch
  * writes d_outputs[b]; before it the points live in the gadget's scratch (N cells per column; columns go in groups that
- * hold at most 1 GiB of it, a group being at least one column), grown on demand and freed by hsw_gadget_destroy.  The
+ * hold at most 1 GiB of it -- or what the engine option "round_scratch" lowers that to --, a group being at least one
+ * column), grown on demand and freed by hsw_gadget_destroy.  The
  * table of the N / 2 powers of w is built on the device from O(log N) staged powers and cached by (w as a value,
  * log_n): four tables, the least recently used one evicted, all freed by hsw_gadget_destroy.  The host reads nothing
  * between launches.  Synchronous.  (The call came under HSW_ABI_MINOR 1: probe for the symbol.) */
@@ -1360,9 +1361,9 @@ int hsw_gadget_ntt(hsw_gadget *g, const hsw_ntt *args, hsw_ntt_report *report);
  * knobs exist so that small inputs reach every path: window_bits (0: the library's choice, 8; else 1 ..
  * HSW_MSM_MAX_WINDOW_BITS) and slice_rows (0: the library's choice, 4096, doubled until a column has at most 1024
  * slices; else a power of two from 64 to 2^28), the rows one workgroup accumulates; the report says what was used.
- * The partial buckets live in the gadget's scratch (columns go in groups that hold at most 1 GiB of them, a group being
- * at least one column), grown on demand and freed by hsw_gadget_destroy; nothing is allocated between the launches of a
- * group.  The blinding term blind * W is a one-point addition and stays the prover's, as does the transcript.
+ * The partial buckets live in the gadget's scratch (columns go in groups that hold at most 1 GiB of them -- or what the
+ * engine option "round_scratch" lowers that to --, a group being at least one column), grown on demand and
+ * freed by hsw_gadget_destroy; nothing is allocated between the launches of a group.  The blinding term blind * W is a one-point addition and stays the prover's, as does the transcript.
  * Synchronous, on the engine's stream.  (The call came under HSW_ABI_MINOR 1: probe for the symbol.) */
 #define HSW_MSM_CELL_NOT_BELOW_P 4u    /* status bit, the value of HSW_NTT_CELL_NOT_BELOW_P */
 #define HSW_MSM_BASE_NOT_BELOW_Q 8u    /* status bit */
@@ -1430,7 +1431,8 @@ int hsw_gadget_msm(hsw_gadget *g, const hsw_msm *args, hsw_msm_report *report);
  * from HSW_OPEN_MIN_TILE_ROWS to 2^20 -- it exists so that small inputs reach the multi-tile and chunked-scan paths; the
  * output bytes do not depend on it, the report says what was used.  The folded column (groups of two columns or more),
  * a cell per thread and a cell per tile live in the gadget's scratch: groups (columns of evaluate) go in batches that
- * hold at most 1 GiB of it, a batch being at least one group, three (two) launches per batch; grown on demand and
+ * hold at most 1 GiB of it (or what the engine option "round_scratch" lowers that to), a batch being at least one group
+ * (one column with all its points), three (two) launches per batch; grown on demand and
  * freed by hsw_gadget_destroy.  The host reads nothing between the launches of a call.  SHPLONK's multi-point opening
  * is hsw_gadget_shplonk_quotient / _open and h(X) is hsw_gadget_quotient (both below); the transcript and the blinding
  * terms stay the prover's.  Synchronous, on the engine's stream.  (The calls came
@@ -1699,7 +1701,11 @@ int hsw_fill_calibrate(hsw_engine *e, void *d_buf, size_t bytes, float *ms);
  * multiplicities where the caller passes no d_m (at most half of it, else HSW_ERR_TOO_LARGE) and the index arrays and value
  * tables of a group of arguments; the arguments are processed in groups that fit, a group being at least one proof.
  * "quotient_scratch": bytes of accumulators hsw_gadget_quotient holds at a time (default and maximum 2^30, 1 .. 2^30):
- * the proofs of a call go in batches that fit, a batch being at least one proof (a test knob). */
+ * the proofs of a call go in batches that fit, a batch being at least one proof (a test knob).
+ * "round_scratch": bytes of scratch that hsw_gadget_ntt, hsw_gadget_msm, hsw_gadget_evaluate and hsw_gadget_open hold
+ * between the launches of a group of columns or of a batch (default and maximum 2^30, 1 .. 2^30): the points of the NTT's
+ * columns, the MSM's partial buckets, the tiles' sums of evaluate and the scratch of open's groups; a group or batch is
+ * at least one column, one group, or one column with all its points (a test knob; the grid limits do not move). */
 int hsw_engine_set_option(hsw_engine *e, const char *name, int64_t value);
 
 const char *hsw_strerror(int status);

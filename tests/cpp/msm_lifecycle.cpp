@@ -3,7 +3,7 @@
 // before a launch, with its status and its hsw_last_error (and that it launches nothing, allocates nothing and writes
 // neither out_points nor status); what the report says of the plan per (n_bases, window_bits, slice_rows); the launches
 // -- the check and two per group of columns; the growth and the reuse of the scratch; the groups of columns under 1 GiB
-// of partial buckets; no device allocation and no event left at the end.  The columns and the bases are addresses only:
+// of partial buckets, and under what the engine option "round_scratch" lowers that to; no device allocation and no event left at the end.  The columns and the bases are addresses only:
 // no launch runs, so nothing reads them, and the points the host tail makes of the unwritten scratch are not looked at.
 #include <hip/hip_runtime.h>
 
@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../halo2-dynamic-sha256_amd/csrc/hsw_gadget.hpp"
 #include "../../halo2-dynamic-sha256_amd/csrc/hsw_msm_value.hpp"
 #include "../../include/hsw.h"
 
@@ -179,6 +180,44 @@ int main() {
         CHECK(hip_stub_live_events() > 0);                                   // (the engine's own)
         hsw_gadget_destroy(g);                                               // frees the scratch: the leak check at the end
         CHECK(hip_stub_live_device_allocations() < live0 + 1);
+    }
+    CHECK(hip_stub_live_device_allocations() == 0);
+    {   // ---- "round_scratch": six columns of 5 slices x 32 windows x 255 buckets x 96 bytes on a gadget of their own
+        const size_t sizes[1] = {128};
+        hsw_gadget *g = nullptr;
+        CHECK(hsw_gadget_create_ex(e, sizes, 1, 1, HSW_GADGET_WHOLE_DIGEST, &g) == HSW_OK);
+        const size_t live0 = hip_stub_live_device_allocations();
+        const int64_t column = 5 * 32 * 255 * 96;                            // 3,916,800 bytes
+        CHECK(hsw_engine_set_option(e, "round_scratch", 0) == HSW_ERR_INVALID_ARG && std::strstr(hsw_last_error(e), "round_scratch must be 1 .. 2^30 bytes"));
+        CHECK(hsw_engine_set_option(e, "round_scratch", ((int64_t)1 << 30) + 1) == HSW_ERR_INVALID_ARG);
+        Columns col(6, 300);
+        const uint64_t rows[6] = {300, 65, 300, 0, 1, 299};
+        hsw_msm a = col.args(300, 8, 64);
+        a.input_rows = rows;
+        CHECK(hsw_engine_set_option(e, "round_scratch", 2 * column) == HSW_OK);      // exactly two columns: three groups
+        int l0 = hip_stub_launches();
+        CHECK(hsw_gadget_msm(g, &a, &rep) == HSW_OK && rep.launches == 1 + 2 * 3 && hip_stub_launches() == l0 + 7 && rep.scratch_bytes == 7833600 && rep.columns == 6);
+        const size_t cap2 = g->scratch.cap;
+        const void *d2 = g->scratch.d;
+        CHECK(cap2 >= 7833600 && cap2 < 3 * (size_t)column && hip_stub_live_device_allocations() == live0 + 1);
+        CHECK(hsw_engine_set_option(e, "round_scratch", 2 * column - 1) == HSW_OK);  // a byte short of two: six groups of one
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_msm(g, &a, &rep) == HSW_OK && rep.launches == 1 + 2 * 6 && hip_stub_launches() == l0 + 13 && rep.scratch_bytes == 3916800);
+        CHECK(g->scratch.cap == cap2 && g->scratch.d == d2);                 // (a smaller need: the scratch as it was)
+        CHECK(hsw_engine_set_option(e, "round_scratch", 1) == HSW_OK);               // below one column: a group is one column still
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_msm(g, &a, &rep) == HSW_OK && rep.launches == 13 && hip_stub_launches() == l0 + 13 && rep.scratch_bytes == 3916800);
+        CHECK(hsw_engine_set_option(e, "round_scratch", (int64_t)1 << 30) == HSW_OK);
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_msm(g, &a, &rep) == HSW_OK && rep.launches == 3 && hip_stub_launches() == l0 + 3 && rep.scratch_bytes == 23500800);
+        const size_t cap6 = g->scratch.cap;
+        const void *d6 = g->scratch.d;
+        CHECK(cap6 == cap2 + 4 * (size_t)column && hip_stub_live_device_allocations() == live0 + 1);   // grown by four columns: replaced, not added to
+        CHECK(hsw_engine_set_option(e, "round_scratch", 2 * column) == HSW_OK);
+        CHECK(hsw_gadget_msm(g, &a, &rep) == HSW_OK && rep.launches == 7 && rep.scratch_bytes == 7833600 && g->scratch.cap == cap6 && g->scratch.d == d6);
+        CHECK(hsw_engine_set_option(e, "round_scratch", (int64_t)1 << 30) == HSW_OK);
+        for (uint32_t s : col.status) CHECK(s == 0);
+        hsw_gadget_destroy(g);
     }
     hsw_engine_destroy(e);
     CHECK(hip_stub_live_device_allocations() == 0 && hip_stub_live_pinned_allocations() == 0 && hip_stub_live_events() == 0);

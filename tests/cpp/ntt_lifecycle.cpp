@@ -3,8 +3,8 @@
 // before a launch, with its status and its hsw_last_error (and that it launches nothing and allocates nothing), among
 // them an omega of order N / 2 and one of order 2 N; the launches per (log_n, pass_log); the groups of columns and the
 // growth of the scratch; the cache of twiddle tables (a hit launches no table kernel, a fifth root evicts the one used
-// longest ago, all freed); the overlap rules (in place accepted, every other overlap refused); no device allocation and
-// no event left at the end.  The columns are addresses only: no launch runs, so nothing reads them.
+// longest ago, all freed); the overlap rules (in place accepted, every other overlap refused); the groups of columns
+// under the engine option "round_scratch", launch by launch; no device allocation and no event left at the end.  The columns are addresses only: no launch runs, so nothing reads them.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -12,6 +12,8 @@
 #include <cstring>
 #include <vector>
 
+#include "../../halo2-dynamic-sha256_amd/csrc/hsw_gadget.hpp"
+#include "../../halo2-dynamic-sha256_amd/csrc/hsw_ntt.h"
 #include "../../halo2-dynamic-sha256_amd/csrc/hsw_ntt_value.hpp"
 #include "../../include/hsw.h"
 
@@ -227,6 +229,57 @@ int main() {
             CHECK(hip_stub_launches() == l0 + 1 + 2 * 3);
             CHECK(hip_stub_live_device_allocations() == live0 + 5);
         }
+        hsw_gadget_destroy(g);
+    }
+    CHECK(hip_stub_live_device_allocations() == 0);
+    {   // ---- "round_scratch": five columns of 64 KiB (log_n 11, two launches a group) on a gadget of their own
+        const size_t sizes[1] = {128};
+        hsw_gadget *g = nullptr;
+        CHECK(hsw_gadget_create_ex(e, sizes, 1, 1, HSW_GADGET_WHOLE_DIGEST, &g) == HSW_OK);
+        const size_t live0 = hip_stub_live_device_allocations();
+        CHECK(hsw_engine_set_option(e, "round_scratch", 0) == HSW_ERR_INVALID_ARG && std::strstr(hsw_last_error(e), "round_scratch must be 1 .. 2^30 bytes"));
+        CHECK(hsw_engine_set_option(e, "round_scratch", ((int64_t)1 << 30) + 1) == HSW_ERR_INVALID_ARG);
+        const Columns col(5, 11);
+        const PFe w = root(11);
+        const hsw_ntt a = col.args(11, &w, status);
+        CHECK(hsw_engine_set_option(e, "round_scratch", 2 * 65536 + 31) == HSW_OK);   // two columns and a little: groups of 2, 2 and 1
+        int l0 = hip_stub_launches();
+        CHECK(hsw_gadget_ntt(g, &a, &rep) == HSW_OK && rep.launches == 2 && rep.scratch_bytes == 2 * 65536 && rep.written == 5 * 2048);
+        CHECK(hip_stub_launches() == l0 + 1 + 3 * 2);                           // the table, then two launches for each of three groups
+        const size_t cap2 = g->scratch.cap;
+        const void *d2 = g->scratch.d;
+        CHECK(cap2 >= 2 * 65536 && hip_stub_live_device_allocations() == live0 + 2);
+        {   // the staged columns (behind the status words' 256 bytes): column b keeps its points in slot b modulo 2, and the
+            // second slot ends where the scratch ends
+            const hsw::NttColumn *nc = reinterpret_cast<const hsw::NttColumn *>(static_cast<const uint8_t *>(d2) + 256);
+            const size_t slot[5] = {0, 1, 0, 1, 0};
+            for (size_t b = 0; b < 5; b++)
+                CHECK(nc[b].in == col.in[b] && nc[b].out == col.out[b] && reinterpret_cast<const uint8_t *>(nc[b].scratch) == static_cast<const uint8_t *>(d2) + cap2 - (2 - slot[b]) * 65536);
+        }
+        CHECK(hsw_engine_set_option(e, "round_scratch", 1) == HSW_OK);          // below one column: five groups of one
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_ntt(g, &a, &rep) == HSW_OK && rep.launches == 2 && rep.scratch_bytes == 65536 && hip_stub_launches() == l0 + 5 * 2);
+        CHECK(g->scratch.cap == cap2 && g->scratch.d == d2);                    // (a smaller need: the scratch as it was)
+        for (size_t b = 0; b < 5; b++)                                          // one slot, and every column in it
+            CHECK(reinterpret_cast<const hsw::NttColumn *>(static_cast<const uint8_t *>(d2) + 256)[b].scratch == reinterpret_cast<const hsw::NttColumn *>(static_cast<const uint8_t *>(d2) + 256)[0].scratch);
+        {   // one launch holds nothing between launches: the option cuts nothing
+            const Columns one(3, 8);
+            const hsw_ntt b = one.args(8, &w8, status);
+            l0 = hip_stub_launches();
+            CHECK(hsw_gadget_ntt(g, &b, &rep) == HSW_OK && rep.launches == 1 && rep.scratch_bytes == 0 && hip_stub_launches() == l0 + 1 + 1);
+        }
+        CHECK(hsw_engine_set_option(e, "round_scratch", (int64_t)1 << 30) == HSW_OK);
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_ntt(g, &a, &rep) == HSW_OK && rep.launches == 2 && rep.scratch_bytes == 5 * 65536 && hip_stub_launches() == l0 + 2);
+        const size_t cap5 = g->scratch.cap;
+        const void *d5 = g->scratch.d;
+        CHECK(cap5 == cap2 + 3 * 65536 && hip_stub_live_device_allocations() == live0 + 3);   // grown by three columns: replaced, not added to
+        CHECK(hsw_engine_set_option(e, "round_scratch", 2 * 65536) == HSW_OK);  // exactly two columns
+        CHECK(hsw_gadget_ntt(g, &a, &rep) == HSW_OK && rep.scratch_bytes == 2 * 65536 && g->scratch.cap == cap5 && g->scratch.d == d5);
+        CHECK(hsw_engine_set_option(e, "round_scratch", 2 * 65536 - 1) == HSW_OK);   // a byte short of two: groups of one
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_ntt(g, &a, &rep) == HSW_OK && rep.scratch_bytes == 65536 && hip_stub_launches() == l0 + 5 * 2);
+        CHECK(hsw_engine_set_option(e, "round_scratch", (int64_t)1 << 30) == HSW_OK);
         hsw_gadget_destroy(g);
     }
     hsw_engine_destroy(e);

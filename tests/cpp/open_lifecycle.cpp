@@ -3,8 +3,8 @@
 // refusal that is decided before a launch, with its status and its hsw_last_error (and that it launches nothing,
 // allocates nothing and writes neither out_evals nor status); what the report says of the geometry per (rows,
 // tile_rows); the launches -- two per batch of columns, three per batch of groups; the growth and the reuse of the
-// scratch that both calls share; the batches of groups under 1 GiB of scratch; no device allocation and no event left
-// at the end.  The columns and the quotients are addresses only: no launch runs, so nothing reads or writes them, and
+// scratch that both calls share; the batches of groups under 1 GiB of scratch, and the batches of both calls under what
+// the engine option "round_scratch" lowers that to; no device allocation and no event left at the end.  The columns and the quotients are addresses only: no launch runs, so nothing reads or writes them, and
 // the evaluations the host tail copies out of the unwritten scratch are not looked at.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../halo2-dynamic-sha256_amd/csrc/hsw_gadget.hpp"
 #include "../../halo2-dynamic-sha256_amd/csrc/hsw_open_value.hpp"
 #include "../../include/hsw.h"
 
@@ -300,6 +301,59 @@ int main() {
         CHECK(hip_stub_live_events() > 0);                                   // (the engine's own)
         hsw_gadget_destroy(g);                                               // frees the scratch: the leak check at the end
         CHECK(hip_stub_live_device_allocations() < live0 + 1);
+    }
+    CHECK(hip_stub_live_device_allocations() == 0);
+    {   // ---- "round_scratch": 773 rows in tiles of 256 -- 4 tiles, 128 bytes an item -- on a gadget of their own
+        const size_t sizes[1] = {128};
+        hsw_gadget *g = nullptr;
+        CHECK(hsw_gadget_create_ex(e, sizes, 1, 1, HSW_GADGET_WHOLE_DIGEST, &g) == HSW_OK);
+        const size_t live0 = hip_stub_live_device_allocations();
+        CHECK(hsw_engine_set_option(e, "round_scratch", 0) == HSW_ERR_INVALID_ARG && std::strstr(hsw_last_error(e), "round_scratch must be 1 .. 2^30 bytes"));
+        CHECK(hsw_engine_set_option(e, "round_scratch", ((int64_t)1 << 30) + 1) == HSW_ERR_INVALID_ARG);
+        // evaluate: five columns of 1, 3, 0, 2 and 1 queries, listed in an order that interleaves the columns
+        Call call(5, 773, 8, 1);
+        call.qc = {1, 0, 3, 1, 4, 3, 1, 1};                                  // (the last one a duplicate: seven items)
+        call.qp = {0, 1, 2, 3, 4, 5, 6, 6};
+        const hsw_evaluate ea = call.evaluate(256);
+        CHECK(hsw_engine_set_option(e, "round_scratch", 4 * 128) == HSW_OK); // four items: columns {0, 1} and {3, 4}
+        int l0 = hip_stub_launches();
+        CHECK(hsw_gadget_evaluate(g, &ea, &erep) == HSW_OK && erep.launches == 4 && hip_stub_launches() == l0 + 4 && erep.scratch_bytes == 512 && erep.tiles == 4);
+        CHECK(erep.columns == 5 && erep.queries == 8);
+        const size_t cap4 = g->scratch.cap;
+        const void *d4 = g->scratch.d;
+        CHECK(hsw_engine_set_option(e, "round_scratch", 1) == HSW_OK);       // below one item: a column with all its points, alone
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_evaluate(g, &ea, &erep) == HSW_OK && erep.launches == 8 && hip_stub_launches() == l0 + 8 && erep.scratch_bytes == 3 * 128);
+        CHECK(g->scratch.cap == cap4 && g->scratch.d == d4);                 // (a smaller need: the scratch as it was)
+        CHECK(hsw_engine_set_option(e, "round_scratch", (int64_t)1 << 30) == HSW_OK);
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_evaluate(g, &ea, &erep) == HSW_OK && erep.launches == 2 && hip_stub_launches() == l0 + 2 && erep.scratch_bytes == 7 * 128);
+        CHECK(g->scratch.cap == cap4 + 3 * 128 && hip_stub_live_device_allocations() == live0 + 1);   // grown by three items: replaced, not added to
+        // open: six groups, folded ones of 2, 3 and 2 columns and single columns in turn; a folded group holds 128 + 3,328 +
+        // 24,832 = 28,288 bytes (tiles, a cell per thread, c), a single one 128 + 3,328 = 3,456
+        call.gfirst = {0, 2, 3, 6, 7, 9, 10};
+        call.gcols = {0, 1, 2, 3, 4, 0, 1, 2, 3, 4};
+        call.quot.resize(6); call.points.resize(32 * 6); call.challenges.resize(32 * 6);
+        const hsw_open oa = call.open(256);
+        CHECK(hsw_engine_set_option(e, "round_scratch", 28288 + 3456) == HSW_OK);   // a folded group and the single one behind it
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_open(g, &oa, &orep) == HSW_OK && orep.batches == 3 && orep.launches == 9 && hip_stub_launches() == l0 + 9 && orep.scratch_bytes == 31744);
+        CHECK(orep.groups == 6 && orep.written == 6 * 773 && orep.tiles == 4);
+        const size_t cap_pair = g->scratch.cap;
+        const void *d_pair = g->scratch.d;
+        CHECK(cap_pair > cap4 + 3 * 128);
+        CHECK(hsw_engine_set_option(e, "round_scratch", 28288 + 3456 - 1) == HSW_OK);   // a byte short: every group alone
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_open(g, &oa, &orep) == HSW_OK && orep.batches == 6 && orep.launches == 18 && hip_stub_launches() == l0 + 18 && orep.scratch_bytes == 28416);
+        CHECK(hsw_engine_set_option(e, "round_scratch", 1) == HSW_OK);
+        CHECK(hsw_gadget_open(g, &oa, &orep) == HSW_OK && orep.batches == 6 && orep.launches == 18 && orep.scratch_bytes == 28416);
+        CHECK(g->scratch.cap == cap_pair && g->scratch.d == d_pair);
+        CHECK(hsw_engine_set_option(e, "round_scratch", (int64_t)1 << 30) == HSW_OK);
+        l0 = hip_stub_launches();
+        CHECK(hsw_gadget_open(g, &oa, &orep) == HSW_OK && orep.batches == 1 && orep.launches == 3 && hip_stub_launches() == l0 + 3);
+        CHECK(orep.scratch_bytes == 3 * 28288 + 3 * 3456);                   // 95,232, a multiple of 256 as it is
+        CHECK(g->scratch.cap == cap_pair + (95232 - 31744) && hip_stub_live_device_allocations() == live0 + 1);
+        hsw_gadget_destroy(g);
     }
     hsw_engine_destroy(e);
     CHECK(hip_stub_live_device_allocations() == 0 && hip_stub_live_pinned_allocations() == 0 && hip_stub_live_events() == 0);

@@ -120,8 +120,9 @@ class Case:
         assert np.array_equal(before, after), "device memory of the caller was written"
         return rc, out, status, {f[0]: getattr(rep, f[0]) for f in N.MsmReport._fields_}
 
-    def run(self, window_bits=0, slice_rows=0, refused=(), bad_bases=0):
-        """the call, then every check that holds for any outcome"""
+    def run(self, window_bits=0, slice_rows=0, refused=(), bad_bases=0, groups=1, held=None):
+        """the call, then every check that holds for any outcome.  groups: the groups of columns the call is to take;
+        held: the columns whose partial buckets the scratch is to hold (under the default budget: as many as fit 1 GiB)"""
         N = self.N
         rc, out, status, report = self.call(window_bits, slice_rows)
         assert rc == N.HSW_OK, self.cfg.lib.hsw_last_error(self.cfg.engine.h)
@@ -130,8 +131,10 @@ class Case:
                                              report["launches"], report["kernel_ms"], report["finish_ms"], report["scratch_bytes"], status.tolist()))
         c, W, s, slices = plan(self.checked, window_bits, slice_rows)
         assert (report["window_bits"], report["windows"], report["slice_rows"], report["slices"]) == (c, W, s, slices)
-        assert report["launches"] == (1 if self.checked else 0) + 2 and report["columns"] == self.n
-        assert report["scratch_bytes"] == min(self.n, max(1, (1 << 30) // (W * slices * ((1 << c) - 1) * 96))) * W * slices * ((1 << c) - 1) * 96
+        assert report["launches"] == (1 if self.checked else 0) + 2 * groups and report["columns"] == self.n
+        if held is None:
+            held = min(self.n, max(1, (1 << 30) // (W * slices * ((1 << c) - 1) * 96)))
+        assert report["scratch_bytes"] == held * W * slices * ((1 << c) - 1) * 96
         if bad_bases:
             assert report["bad_bases"] == bad_bases[0] and report["first_bad_base"] == bad_bases[1]
             assert (status == N.HSW_MSM_BASE_NOT_BELOW_Q).all() and (out == np.uint64(OUT_SENT)).all()
@@ -238,6 +241,41 @@ def test_a_base_not_below_q_refuses_everything_inside_the_checked_rows_only(hsw,
     # the same base beyond the checked rows: not read (those rows hold coordinates far above q anyway)
     case.poke(base + 2 * 250 + 1, q_words)
     case.run(8, 64)
+    cfg.close()
+
+
+# ---- 4b. groups of columns: the engine option "round_scratch" lowers the 1 GiB a group's partial buckets may take ------------
+# (the other limit of a group, 65,535 columns in a grid dimension, cannot be the one that cuts: at one bucket per window a
+# column still takes 254 x 96 = 24 KB of partial buckets, and 65,535 of them are above 1 GiB)
+@REPR
+def test_groups_of_columns_under_a_scratch_budget(hsw, eng_int, mont):
+    """300 bases, window_bits 8, slice_rows 64: 5 slices x 32 windows x 255 buckets x 96 bytes a column.  Six columns of
+    heights 300, 65, 300, 0, 1, 299 -- in groups of two, the one-row column takes the slot the second 300-row column left
+    full of slices, and the 299-row one the slot of the empty column.  Every group has its own offset into the columns,
+    the status words and the window points."""
+    cfg = gadget(hsw, eng_int, mont)
+    pts, logs = chains(300)
+    column = 5 * 32 * 255 * 96
+    scal = [random_scalars(45 + b, 300) for b in range(5)] + [None]
+    case = Case(cfg, hsw, mont, pts, logs, [300, 65, 300, 0, 1, 299], scal, reads=[0, 1, 2, 3, 4, 0])   # the last reads column 0's input
+    whole, _, _ = case.run(8, 64)                                            # one group
+    try:
+        for budget, groups, held in ((2 * column, 3, 2), (2 * column - 1, 6, 1), (1, 6, 1)):
+            eng_int.set_option("round_scratch", budget)
+            out, status, _ = case.run(8, 64, groups=groups, held=held)
+            assert np.array_equal(out, whole) and not status.any()
+        assert words_point(out[4]) == commitment(scal[4][:1], logs)          # the one-row column: its scalar times base 0
+        # a cell equal to r in column 2, the first column of the second group (the third of six)
+        case.poke(case.at[2] + 17, cell_words(P_INT, False))
+        for budget, groups, held in ((2 * column, 3, 2), (1, 6, 1)):
+            eng_int.set_option("round_scratch", budget)
+            out, status, report = case.run(8, 64, refused=(2,), groups=groups, held=held)
+            assert status.tolist() == [0, 0, 4, 0, 0, 0] and report["first_refused"] == 2 and report["refused_columns"] == 1
+            assert (out[2] == np.uint64(OUT_SENT)).all() and np.array_equal(np.delete(out, 2, 0), np.delete(whole, 2, 0))
+    finally:
+        eng_int.set_option("round_scratch", 1 << 30)
+    out, _, _ = case.run(8, 64, refused=(2,))                                # the option is back: one group again
+    assert np.array_equal(np.delete(out, 2, 0), np.delete(whole, 2, 0))
     cfg.close()
 
 

@@ -100,8 +100,9 @@ class Case:
         self.buf[self.slot_in(b) + row] = torch.from_numpy(limbs([x]).copy().view(np.int64)[0]).cuda()
         torch.cuda.synchronize()
 
-    def run(self, omega=None, shift=None, scale=None, shift_after=False, pass_log=0, launches=None):
-        """the call, then every check that holds for any outcome; returns (output cells per column or None, status, report)"""
+    def run(self, omega=None, shift=None, scale=None, shift_after=False, pass_log=0, launches=None, held=None):
+        """the call, then every check that holds for any outcome; returns (output cells per column or None, status, report).
+        held: the columns whose points the scratch is to hold between launches (all of them by default)"""
         import torch
         N, n, rows, mont = self.N, self.n, self.rows, self.mont
         omega = root_of_unity(self.log_n) if omega is None else omega
@@ -148,7 +149,7 @@ class Case:
         if launches is not None:
             assert report["launches"] == launches
         assert report["twiddle_bytes"] == 32 * max(1, rows // 2)
-        assert report["scratch_bytes"] == (0 if report["launches"] == 1 else 32 * rows * n)
+        assert report["scratch_bytes"] == (0 if report["launches"] == 1 else 32 * rows * (n if held is None else held))
         return outputs, status, report
 
 
@@ -257,6 +258,93 @@ def test_a_cell_not_below_p_refuses_its_column_alone(hsw, eng_int, log_n, pass_l
     case.poke(1, rows, m + P_INT)
     _, status, rep = case.run(scale=SCALE, pass_log=pass_log)
     assert not status.any() and rep["refused_columns"] == 0
+    cfg.close()
+
+
+# ---- 5b. groups of columns: the engine option "round_scratch" lowers the 1 GiB a group's points may take --------------------
+def grouped_case(cfg, hsw, log_n, mont, seed):
+    """column 0 in place, columns 1 and 2 read one input, column 3 is short, column 4 plain"""
+    n = 1 << log_n
+    return Case(cfg, hsw, log_n, mont, [n, n - 5, n - 5, 7, n], seed, order="interleaved", in_place=(0,), reads=[0, 1, 1, 3, 4])
+
+
+@REPR
+@pytest.mark.parametrize("log_n,pass_log", [(9, 3), (12, 0)], ids=["nine_launches", "two_launches"])
+def test_groups_of_columns_under_a_scratch_budget(hsw, eng_int, log_n, pass_log, mont):
+    """Five columns in groups of 2, 2, 1 and in five groups of one: column b keeps its points in slot b modulo the group,
+    and every group's launches start at its own column and status word."""
+    n = 1 << log_n
+    cfg = gadget(hsw, eng_int, mont)
+    whole, _, _ = grouped_case(cfg, hsw, log_n, mont, 700 + log_n).run(shift=SHIFT, scale=SCALE, pass_log=pass_log)
+    try:
+        for budget, held in ((2 * n * 32, 2), (2 * n * 32 - 1, 1), (1, 1)):    # groups 2, 2, 1; five of one; five of one
+            eng_int.set_option("round_scratch", budget)
+            case = grouped_case(cfg, hsw, log_n, mont, 700 + log_n)          # (column 0 is in place: a fresh buffer per call)
+            outs, status, _ = case.run(shift=SHIFT, scale=SCALE, pass_log=pass_log, held=held)
+            assert not status.any() and all(np.array_equal(a, b) for a, b in zip(outs, whole))
+        # a cell not below p in column 3, the second column of the second group: it alone is refused
+        for budget, held in ((2 * n * 32, 2), (1, 1)):
+            eng_int.set_option("round_scratch", budget)
+            case = grouped_case(cfg, hsw, log_n, mont, 700 + log_n)
+            case.poke(3, 6, 2 ** 250 // 3 + P_INT)
+            outs, status, rep = case.run(shift=SHIFT, scale=SCALE, pass_log=pass_log, held=held)
+            assert status.tolist() == [0, 0, 0, 4, 0] and rep["refused_columns"] == 1 and rep["first_refused"] == 3 and outs[3] is None
+            assert all(np.array_equal(outs[b], whole[b]) for b in (0, 1, 2, 4))
+    finally:
+        eng_int.set_option("round_scratch", 1 << 30)
+    cfg.close()
+
+
+@REPR
+def test_one_launch_holds_no_scratch_whatever_the_budget(hsw, eng_int, mont):
+    """log_n 8 with the default pass_log is one launch: no points lie in the scratch, so the budget cuts nothing"""
+    cfg = gadget(hsw, eng_int, mont)
+    whole, _, rep = grouped_case(cfg, hsw, 8, mont, 708).run(shift=SHIFT, scale=SCALE, launches=1)
+    assert rep["scratch_bytes"] == 0
+    try:
+        eng_int.set_option("round_scratch", 1)
+        outs, status, rep = grouped_case(cfg, hsw, 8, mont, 708).run(shift=SHIFT, scale=SCALE, launches=1)
+        assert rep["scratch_bytes"] == 0 and not status.any() and all(np.array_equal(a, b) for a, b in zip(outs, whole))
+    finally:
+        eng_int.set_option("round_scratch", 1 << 30)
+    cfg.close()
+
+
+# ---- 5c. the other limit of a group: 65,535 columns in a grid dimension ------------------------------------------------------
+@REPR
+def test_more_columns_than_a_grid_dimension_holds(hsw, eng_int, mont):
+    """65,537 columns of two cells (log_n 1, one launch): groups of 65,535 and 2.  The inputs are eight columns read over
+    and over -- a shared input is allowed --, the outputs 65,537 columns of 64 bytes side by side in one buffer."""
+    import torch
+    N, n, K = hsw._native, 65537, 8
+    cfg = gadget(hsw, eng_int, mont)
+    rng = np.random.default_rng(750)
+    vals = [[int.from_bytes(rng.bytes(40), "little") % P_INT for _ in range(2)] for _ in range(K)]
+    omega = root_of_unity(1)
+    want = np.concatenate([limbs([stored(x, mont) for x in ntt_model(v, 1, omega, SHIFT, SCALE, False)]) for v in vals])   # (2 K, 4)
+    src_host = np.full((2 * K + 2 * PAD, 4), np.uint64(SENT), dtype=np.uint64)
+    src_host[PAD: PAD + 2 * K] = np.concatenate([limbs([stored(x, mont) for x in v]) for v in vals])
+    src = torch.from_numpy(src_host.view(np.int64)).cuda()
+    dst = torch.from_numpy(np.full((2 * n + 2 * PAD, 4), np.uint64(SENT), dtype=np.uint64).view(np.int64)).cuda()
+    assert src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0
+    ins = (C.c_void_p * n)(*[src.data_ptr() + 32 * (PAD + 2 * (b % K)) for b in range(n)])
+    outs = (C.c_void_p * n)(*[dst.data_ptr() + 32 * (PAD + 2 * b) for b in range(n)])
+    enc = lambda v: np.array(limbs([stored(v, mont)]))                       # noqa: E731 (a writable copy)
+    om, sh, sc = enc(omega), enc(SHIFT), enc(SCALE)
+    status = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    args = N.Ntt(0, 1, 0, 0, n, ins, None, outs, om.ctypes.data, sh.ctypes.data, sc.ctypes.data, status.ctypes.data_as(C.POINTER(C.c_uint32)))
+    rep = N.NttReport()
+    torch.cuda.synchronize()
+    cfg._ok(cfg.lib.hsw_gadget_ntt(cfg.h, C.byref(args), C.byref(rep)))
+    print("ntt: log_n 1, columns %d (groups of 65535 and 2), launches %d, kernel %.3f ms, scratch %d bytes, refused %d"
+          % (rep.columns, rep.launches, rep.kernel_ms, rep.scratch_bytes, rep.refused_columns))
+    assert not status.any() and (rep.columns, rep.written, rep.refused_columns, rep.launches, rep.scratch_bytes) == (n, 2 * n, 0, 1, 0)
+    got = dst.cpu().numpy().view(np.uint64)
+    assert (got[:PAD] == np.uint64(SENT)).all() and (got[PAD + 2 * n:] == np.uint64(SENT)).all()
+    assert np.array_equal(got[PAD + 2 * (n - 2): PAD + 2 * n], np.concatenate([want[2 * ((n - 2) % K): 2 * ((n - 2) % K) + 2], want[2 * ((n - 1) % K): 2 * ((n - 1) % K) + 2]]))
+    tiled = np.tile(want, (n // K + 1, 1))[:2 * n]
+    assert np.array_equal(got[PAD: PAD + 2 * n], tiled), "column %d differs" % (int(np.nonzero((got[PAD: PAD + 2 * n] != tiled).any(axis=1))[0][0]) // 2)
+    assert np.array_equal(src.cpu().numpy().view(np.uint64), src_host)
     cfg.close()
 
 

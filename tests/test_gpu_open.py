@@ -85,8 +85,9 @@ class Case:
     def enc(self, xs):
         return np.array(limbs([stored(x, self.mont) for x in xs]))            # (a writable copy)
 
-    def evaluate(self, points, queries, tile_rows=0, refused=()):
-        """the call, then every check: returns (evals (queries, 4), status, report)"""
+    def evaluate(self, points, queries, tile_rows=0, refused=(), batches=1):
+        """the call, then every check: returns (evals (queries, 4), status, report).  batches: the batches of columns the
+        call is to take"""
         N, n = self.N, self.n
         cols, hs, before = self._common()
         nq = len(queries)
@@ -98,12 +99,14 @@ class Case:
         rep = N.EvaluateReport()
         rc = N.lib().hsw_gadget_evaluate(self.cfg.h, C.byref(args), C.byref(rep))
         assert rc == N.HSW_OK, rc
+        print("evaluate: rows %d, columns %d, queries %d, tile_rows %d (%d tiles), launches %d, kernel %.3f ms, scratch %d bytes, status %s"
+              % (self.rows, n, nq, rep.tile_rows, rep.tiles, rep.launches, rep.kernel_ms, rep.scratch_bytes, status.tolist()))
         assert np.array_equal(self.buf.cpu().numpy().view(np.uint64), before), "evaluate wrote device memory of the caller"
         refused = sorted(set(refused))
         assert [b for b in range(n) if status[b]] == refused and all(status[b] == N.HSW_OPEN_CELL_NOT_BELOW_P for b in refused)
         assert (rep.columns, rep.queries, rep.refused_columns, rep.first_refused) == (n, nq, len(refused), refused[0] if refused else NONE)
         assert rep.refused_queries == sum(1 for b, _ in queries if b in refused) and rep.thread_rows == N.HSW_OPEN_THREAD_ROWS
-        assert rep.tile_rows == (tile_rows or 2048) and rep.tiles == -(-self.rows // rep.tile_rows) and rep.launches == 2
+        assert rep.tile_rows == (tile_rows or 2048) and rep.tiles == -(-self.rows // rep.tile_rows) and rep.launches == 2 * batches
         for i, (b, t) in enumerate(queries):
             if b in refused:
                 assert (evals[i] == np.uint64(EVAL_FILL)).all(), "query %d of a refused column was written" % i
@@ -111,9 +114,9 @@ class Case:
                 assert evals[i].tolist() == self.enc([evaluate_model(self.values[b], points[t])])[0].tolist(), "query %d: a wrong value" % i
         return evals, status, rep
 
-    def open(self, groups, points, challenges, tile_rows=0, refused=(), expect=None):
+    def open(self, groups, points, challenges, tile_rows=0, refused=(), expect=None, batches=1):
         """the call, then every check: returns (quotient cells per group or None, evals, status, report).  expect: the
-        (q, eval) of every group, if the caller has them already"""
+        (q, eval) of every group, if the caller has them already; batches: the batches of groups the call is to take"""
         N, n, rows = self.N, self.n, self.rows
         ng = len(groups)
         assert ng <= len(self.q_at)
@@ -131,11 +134,13 @@ class Case:
         rep = N.OpenReport()
         rc = N.lib().hsw_gadget_open(self.cfg.h, C.byref(args), C.byref(rep))
         assert rc == N.HSW_OK, rc
+        print("open: rows %d, groups %d, tile_rows %d (%d tiles), batches %d, launches %d, kernel %.3f ms, scratch %d bytes, status %s"
+              % (rows, ng, rep.tile_rows, rep.tiles, rep.batches, rep.launches, rep.kernel_ms, rep.scratch_bytes, status.tolist()))
         after = self.buf.cpu().numpy().view(np.uint64)
         refused = sorted(set(refused))
         assert [k for k in range(ng) if status[k]] == refused and all(status[k] == N.HSW_OPEN_CELL_NOT_BELOW_P for k in refused)
         assert (rep.groups, rep.refused_groups, rep.first_refused, rep.written) == (ng, len(refused), refused[0] if refused else NONE, rows * (ng - len(refused)))
-        assert rep.tile_rows == (tile_rows or 2048) and rep.tiles == -(-rows // rep.tile_rows) and rep.launches == 3 * rep.batches and rep.batches == 1
+        assert rep.tile_rows == (tile_rows or 2048) and rep.tiles == -(-rows // rep.tile_rows) and rep.launches == 3 * rep.batches and rep.batches == batches
         assert rep.thread_rows == N.HSW_OPEN_THREAD_ROWS
         mask = np.ones(len(before), dtype=bool)                               # the guard: everything but the quotients that were to be written
         out = []
@@ -280,6 +285,163 @@ def test_a_cell_not_below_p_refuses_its_groups_and_queries_alone(hsw, eng_int, m
         out, _, _, _ = case.open(groups, points, challenges, tile_rows=tile_rows, refused=bad_groups)
         assert out[0] is not None and out[2] is not None
         case.evaluate(points, [(1, 0), (0, 1), (1, 2), (3, 3), (2, 0)], tile_rows=tile_rows, refused=bad_cols)
+    cfg.close()
+
+
+# ---- 4b. batches: the engine option "round_scratch" lowers the 1 GiB a batch's scratch may take ------------------------------
+@REPR
+def test_evaluate_in_batches_of_columns_under_a_scratch_budget(hsw, eng_int, mont):
+    """773 rows in tiles of 256: 4 tiles, 128 bytes of scratch an item.  Five columns of 1, 3, 0, 2 and 1 items (a
+    duplicate query besides), the queries listed in an order that interleaves the columns; a batch's items lie from 0 in
+    the scratch whatever their place in the call."""
+    T = hsw._native.HSW_OPEN_MIN_TILE_ROWS
+    assert T == 256
+    rows = 3 * T + 5
+    rng = np.random.default_rng(4500)
+    values = [random_column(rng, h) for h in (rows, rows - 1, rows, 1, rows)]
+    points = random_column(rng, 3) + [P_INT - 1]
+    queries = [(1, 0), (0, 1), (3, 2), (1, 3), (4, 0), (3, 0), (1, 1), (1, 0)]
+    cfg = gadget(hsw, eng_int, mont)
+    case = Case(cfg, hsw, rows, mont, values)
+    case.poke(2, 0, P_INT)                                                    # column 2 has no query: not read, not refused
+    whole, _, rep = case.evaluate(points, queries, tile_rows=T)
+    assert rep.scratch_bytes == 7 * 128
+    try:
+        # four items: columns {0, 1} and {3, 4}; a byte short: {0}, {1}, {3, 4}; 1: every column alone, the three items of column 1 together
+        for budget, batches, held in ((4 * 128, 2, 4), (4 * 128 - 1, 3, 3), (1, 4, 3)):
+            eng_int.set_option("round_scratch", budget)
+            ev, _, rep = case.evaluate(points, queries, tile_rows=T, batches=batches)
+            assert np.array_equal(ev, whole) and rep.scratch_bytes == held * 128
+        case.poke(4, rows - 1, P_INT)                                         # a column of the last batch: its one query alone is refused
+        for budget, batches in ((4 * 128, 2), (1, 4)):
+            eng_int.set_option("round_scratch", budget)
+            ev, status, rep = case.evaluate(points, queries, tile_rows=T, refused=(4,), batches=batches)
+            assert status.tolist() == [0, 0, 0, 0, 4] and rep.refused_queries == 1
+            assert np.array_equal(np.delete(ev, 4, 0), np.delete(whole, 4, 0))
+    finally:
+        eng_int.set_option("round_scratch", 1 << 30)
+    cfg.close()
+
+
+FOLDED, SINGLE = 128 + 3328 + 24832, 128 + 3328   # 773 rows, 4 tiles: the tiles' sums, a cell per thread (97, to 256 bytes), c (to 256 bytes)
+
+
+@REPR
+@pytest.mark.parametrize("first", ["folded_first", "single_first"])
+def test_open_in_batches_of_groups_under_a_scratch_budget(hsw, eng_int, mont, first):
+    """773 rows in tiles of 256.  Six groups, folded ones (2, 3, 2 columns) and single columns in turn.  A batch's scratch
+    is all its tiles' sums first, then per group its seeds and, if it is folded, c: a batch of a folded and a single
+    group runs tiles, seeds, c, seeds; one of a single and a folded group tiles, seeds, seeds, c."""
+    T = hsw._native.HSW_OPEN_MIN_TILE_ROWS
+    assert T == 256
+    rows = 3 * T + 5
+    rng = np.random.default_rng(4600)
+    values = [random_column(rng, h) for h in (rows, rows - 5, rows, 1, rows - 1, rows)]
+    groups = [[0, 1], [2], [1, 3, 0], [4], [4, 0], [5]]
+    if first == "single_first":
+        groups = groups[1:] + groups[:1]                                      # ... and [0, 1] last
+    points, challenges = random_column(rng, 6), random_column(rng, 6)
+    expect = [open_model([values[b] for b in grp], z, v, rows) for grp, z, v in zip(groups, points, challenges)]
+    cfg = gadget(hsw, eng_int, mont)
+    case = Case(cfg, hsw, rows, mont, values, n_quotients=6)
+    whole, whole_evals, _, rep = case.open(groups, points, challenges, tile_rows=T, expect=expect)
+    assert rep.scratch_bytes == 3 * FOLDED + 3 * SINGLE == 95232
+    last = 5 if first == "folded_first" else 4                                # the group that is column 5 alone
+    try:
+        # a folded and a single group together: three batches of two; a byte short: every group alone; 1: the same
+        for budget, batches, held in ((FOLDED + SINGLE, 3, 31744), (FOLDED + SINGLE - 1, 6, 28416), (1, 6, 28416)):
+            eng_int.set_option("round_scratch", budget)
+            out, evals, _, rep = case.open(groups, points, challenges, tile_rows=T, expect=expect, batches=batches)
+            assert rep.scratch_bytes == held and np.array_equal(evals, whole_evals)
+            assert all(np.array_equal(a, b) for a, b in zip(out, whole))
+        case.poke(5, 300, P_INT)                                              # column 5: one group of the last batch is refused
+        for budget, batches in ((FOLDED + SINGLE, 3), (1, 6)):
+            eng_int.set_option("round_scratch", budget)
+            out, evals, status, rep = case.open(groups, points, challenges, tile_rows=T, expect=expect, refused=(last,), batches=batches)
+            assert [int(s) for s in status] == [4 if k == last else 0 for k in range(6)] and out[last] is None
+            assert all(np.array_equal(out[k], whole[k]) for k in range(6) if k != last)
+    finally:
+        eng_int.set_option("round_scratch", 1 << 30)
+    cfg.close()
+
+
+# ---- 4c. the other limit of a batch: 65,535 columns or groups in a grid dimension ------------------------------------------------
+def eight_cells(mont, seed):
+    """eight one-row columns side by side with sentinels around them: (device buffer, its host image, the eight stored cells)"""
+    import torch
+    rng = np.random.default_rng(seed)
+    cells = np.array(limbs([stored(x, mont) for x in random_column(rng, 8)]))
+    host = np.full((8 + 2 * PAD, 4), np.uint64(SENT), dtype=np.uint64)
+    host[PAD: PAD + 8] = cells
+    buf = torch.from_numpy(host.view(np.int64)).cuda()
+    assert buf.data_ptr() % 16 == 0
+    return buf, host, cells
+
+
+@REPR
+def test_evaluate_more_columns_than_a_grid_dimension_holds(hsw, eng_int, mont):
+    """65,537 columns of one row, a query each: batches of 65,535 and 2.  The columns are eight cells read over and
+    over; the evaluation of a one-row column is its cell, at any point."""
+    N, n = hsw._native, 65537
+    cfg = gadget(hsw, eng_int, mont)
+    buf, host, cells = eight_cells(mont, 4700)
+    z = np.array(limbs([stored(x, mont) for x in random_column(np.random.default_rng(4701), 2)]))
+    cols = (C.c_void_p * n)(*[buf.data_ptr() + 32 * (PAD + b % 8) for b in range(n)])
+    evals = np.full((n + 2, 4), np.uint64(EVAL_FILL), dtype=np.uint64)         # a row before and a row behind: untouched
+    status = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+    qc = np.arange(n, dtype=np.uint32)
+    qp = (qc & 1).astype(np.uint32)
+    args = N.Evaluate(0, 0, 1, n, cols, None, 2, z.ctypes.data, n, qc.ctypes.data_as(C.POINTER(C.c_uint32)), qp.ctypes.data_as(C.POINTER(C.c_uint32)),
+                      evals[1:].ctypes.data, status.ctypes.data_as(C.POINTER(C.c_uint32)))
+    rep = N.EvaluateReport()
+    rc = N.lib().hsw_gadget_evaluate(cfg.h, C.byref(args), C.byref(rep))
+    assert rc == N.HSW_OK, rc
+    print("evaluate: rows 1, columns %d (batches of 65535 and 2), launches %d, kernel %.3f ms, scratch %d bytes, refused %d"
+          % (rep.columns, rep.launches, rep.kernel_ms, rep.scratch_bytes, rep.refused_columns))
+    assert (rep.columns, rep.queries, rep.refused_columns, rep.refused_queries, rep.launches, rep.tiles) == (n, n, 0, 0, 4, 1)
+    assert rep.scratch_bytes == 65535 * 32 and not status.any()
+    assert (evals[0] == np.uint64(EVAL_FILL)).all() and (evals[n + 1] == np.uint64(EVAL_FILL)).all()
+    assert np.array_equal(evals[n - 1: n + 1], cells[[(n - 2) % 8, (n - 1) % 8]])   # the second batch's
+    assert np.array_equal(evals[1: n + 1], np.tile(cells, (n // 8 + 1, 1))[:n])
+    assert np.array_equal(buf.cpu().numpy().view(np.uint64), host)
+    cfg.close()
+
+
+@REPR
+def test_open_more_groups_than_a_grid_dimension_holds(hsw, eng_int, mont):
+    """65,537 groups of one column of one row: batches of 65,535 and 2.  Every quotient is one zero cell at an address of
+    its own, every evaluation the column's cell."""
+    import torch
+    N, ng = hsw._native, 65537
+    cfg = gadget(hsw, eng_int, mont)
+    buf, host, cells = eight_cells(mont, 4800)
+    quot = torch.from_numpy(np.full((ng + 2 * PAD, 4), np.uint64(SENT), dtype=np.uint64).view(np.int64)).cuda()
+    assert quot.data_ptr() % 16 == 0
+    zv = np.array(limbs([stored(x, mont) for x in random_column(np.random.default_rng(4801), 2)]))
+    z, v = np.tile(zv[0], (ng, 1)), np.tile(zv[1], (ng, 1))
+    cols = (C.c_void_p * 8)(*[buf.data_ptr() + 32 * (PAD + b) for b in range(8)])
+    qs = (C.c_void_p * ng)(*[quot.data_ptr() + 32 * (PAD + k) for k in range(ng)])
+    first = np.arange(ng + 1, dtype=np.uint64)
+    flat = (np.arange(ng, dtype=np.uint32) % 8).astype(np.uint32)
+    evals = np.full((ng + 2, 4), np.uint64(EVAL_FILL), dtype=np.uint64)        # a row before and a row behind: untouched
+    status = np.full(ng, 0xFFFFFFFF, dtype=np.uint32)
+    args = N.Open(0, 0, 1, 8, cols, None, ng, first.ctypes.data_as(C.POINTER(C.c_uint64)), flat.ctypes.data_as(C.POINTER(C.c_uint32)), z.ctypes.data,
+                  v.ctypes.data, qs, evals[1:].ctypes.data, status.ctypes.data_as(C.POINTER(C.c_uint32)))
+    rep = N.OpenReport()
+    torch.cuda.synchronize()
+    rc = N.lib().hsw_gadget_open(cfg.h, C.byref(args), C.byref(rep))
+    assert rc == N.HSW_OK, rc
+    print("open: rows 1, groups %d, batches %d, launches %d, kernel %.3f ms, scratch %d bytes, refused %d"
+          % (rep.groups, rep.batches, rep.launches, rep.kernel_ms, rep.scratch_bytes, rep.refused_groups))
+    assert (rep.groups, rep.refused_groups, rep.written, rep.batches, rep.launches, rep.tiles) == (ng, 0, ng, 2, 6, 1)
+    assert rep.scratch_bytes == 18874112 and not status.any()                 # 65,535 x (a tile's sum, and one seed to 256 bytes), to 256 bytes
+    got = quot.cpu().numpy().view(np.uint64)
+    assert (got[:PAD] == np.uint64(SENT)).all() and (got[PAD + ng:] == np.uint64(SENT)).all()
+    assert not got[PAD + ng - 2: PAD + ng].any() and not got[PAD: PAD + ng].any()   # the second batch's two, then all: q = 0
+    assert (evals[0] == np.uint64(EVAL_FILL)).all() and (evals[ng + 1] == np.uint64(EVAL_FILL)).all()
+    assert np.array_equal(evals[ng - 1: ng + 1], cells[[(ng - 2) % 8, (ng - 1) % 8]])
+    assert np.array_equal(evals[1: ng + 1], np.tile(cells, (ng // 8 + 1, 1))[:ng])
+    assert np.array_equal(buf.cpu().numpy().view(np.uint64), host)
     cfg.close()
 
 
